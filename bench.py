@@ -17,7 +17,9 @@ bench.py ...`) before this process imports torch or touches a GPU, relays rank
 `torch.distributed.run` (WORLD_SIZE set) it is one rank; WORLD_SIZE != --gpus
 is an error.  A rank exits non-zero when fewer devices than ranks are visible.
 
-Prints ONE JSON line (rank 0).  Besides the contract's keys it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the K timed steps of the
+headline SR batch, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  `--full` adds every other
+measurement and check, each after the headline:
   roofline      dominant kernel (tail16), HIP events on the launch stream
   cpu_baseline  torch-CPU (oneDNN) restatement timed on the host cores (N = 1)
   parity_path   the same batch through the f32 kernels (the <= 1e-5 path):
@@ -29,7 +31,15 @@ Prints ONE JSON line (rank 0).  Besides the contract's keys it carries
                 GPU, flat-gradient all-reduce (RCCL) + Adam, samples/s
   tiled         BASELINE config 5: 40x40x3 -> 1600x1600x3 through 4x4 tiles, f16
   host_io       srcfd_predict with host buffers (PCIe + page faults included)
-  env           every SRCFD_* variable seen (diagnostic switches are refused)
+  env           every SRCFD_* variable seen (diagnostic switches are refused), and
+                the device clocks / power before and after the headline
+`--no-extras` / `--no-cpu-baseline` drop parts of what `--full` adds.
+
+`--dump-outputs DIR` (rank 0) writes what the timed path returned in its LAST timed step, as .npy files:
+  y.npy               DUMP_SAMPLES predicted single-channel samples (n, 400, 400, 1), as float32 whatever --out-dtype, at the
+                      indices of y_sample_index.npy (a fixed, seeded sample; all of them when the batch has no more)
+  y_sample_index.npy  those sample indices (float64)
+The inputs depend on the arguments and the rank only (seeded), so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -51,6 +61,7 @@ MACS_PER_SAMPLE = 140_024_128
 PEAK_BF16_TFLOPS = 2500.0         # MI355X dense bf16/f16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP32_TFLOPS = 157.3          # f32-input MFMA
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLES = 64                 # --dump-outputs: 64 f32 fields of 400 x 400 = 41 MB
 PRE_WARM_MS = 120.0               # untimed steps by wall time in front of the counted warm-up of an SR leg (clock ramp; Job.timed)
 REFUSED_ENV = ("SRCFD_TAIL_ABLATE", "SRCFD_MID_ABLATE", "SRCFD_TAIL_PROF", "SRCFD_TAIL32_ABLATE")   # switch work off / add syncs: never a headline
 # A/B switches: each selects a complete second implementation of a stage (results stay right), but a line measured under one is
@@ -155,8 +166,31 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="sr", choices=["sr", "tiled"],
                     help="sr: BASELINE config 2 (headline); tiled: config 5 as the headline line (40x40x3 -> 1600x1600x3, f16)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity_path / train / tiled / host_io sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement besides the headline: roofline / per-kernel times, parity paths, CPU baseline, train, tiled, host_io")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the parity_path / train / tiled / host_io sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32 / float64)")
     return ap.parse_args(argv)
+
+
+def dump_index(n, k=DUMP_SAMPLES, seed=0):
+    """The fixed, seeded sample of result indices --dump-outputs writes (sorted; all n when n <= k)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64 only."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"dump {name}: {a.dtype} is neither float32 nor float64")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def free_port():
@@ -322,7 +356,8 @@ class Job:
         # One-time set-up of every leg's precision (operand packs, activation workspaces) happens here, through the ABI's
         # explicit reserve call, not lazily inside a leg's first warm-up step: a leg then starts on a GPU that the previous
         # leg has just left, instead of one that idled through host-side weight packing and hipMalloc.
-        for prec in dict.fromkeys(([] if args.no_extras or args.precision in ("fp32", "fp32x3") else ["fp32", "fp32x3"]) + [args.precision]):
+        parity_legs = args.full and not args.no_extras and args.precision not in ("fp32", "fp32x3")
+        for prec in dict.fromkeys((["fp32", "fp32x3"] if parity_legs else []) + [args.precision]):
             self.model.precision = prec
             self.model.reserve(self.n)
         self.y_out = {}
@@ -390,7 +425,9 @@ class Job:
         return {k: round(float(np.mean(v)), 4) for k, v in acc.items()}
 
     # -- the SR batch (config 2) at one precision -------------------------------------------------------------
-    def run_sr(self, precision, out_dtype, steps, warmup):
+    def run_sr(self, precision, out_dtype, steps, warmup, keep=None):
+        """keep: sample indices whose results of the last timed step are copied to the host (self.kept) before anything
+        else runs on the result buffer."""
         torch, args = self.torch, self.args
         self.model.precision = precision
         y = self.out_buffer(out_dtype)     # one result buffer per output type, shared by the legs (allocated once)
@@ -400,13 +437,15 @@ class Job:
             self.model.predict_device(self.x, y, in_affine=self.ain, out_affine=self.aout, nan_guard=True, nonfinite=self.bad)
 
         dt = self.timed(step, steps, warmup, pre_ms=PRE_WARM_MS)
+        if keep is not None:
+            self.kept = y[torch.as_tensor(keep, device=self.dev)].float().cpu().numpy()
         ms = dt / steps * 1e3
         rec = {"value": round(self.shard.aggregate_throughput(args.fields, self.world, ms * 1e-3), 2), "unit": "fields/s",
                "ms_per_step": round(ms, 4), "steps": steps, "dtype": precision, "out_dtype": out_dtype,
                "ms_per_step_rank_min_max": list(self.last_rank_ms), "untimed_pre_warm_ms": PRE_WARM_MS,
                "tflops_model": round(2.0 * MACS_PER_SAMPLE * self.n * self.world / (ms * 1e-3) / 1e12, 2),
                "nonfinite": int(self.bad.item()), "last_plan": self.model.last_plan()}   # which kernels the timed calls ran (srcfd_model_last_plan)
-        if self.rank == 0:
+        if self.rank == 0 and args.full:   # the per-kernel pass is a run of its own: --full only
             kernels = self.kernel_profile(step, max(3, min(steps, 10)))
             tot = sum(kernels.values())
             rec["kernels_ms"] = kernels
@@ -547,7 +586,7 @@ class Job:
         return rec
 
     # -- config 5: tiled SR -------------------------------------------------------------------------------------
-    def run_tiled(self, steps=20, warmup=3):
+    def run_tiled(self, steps=20, warmup=3, keep=False):
         """One 40x40x3 field = 4x4 tiles x 3 components = 48 samples -> 1600x1600x3, f16 operands; the tile samples are
         sharded contiguously over the ranks (shard.shard_range), no collective in the timed region."""
         np, torch = self.np, self.torch
@@ -565,6 +604,8 @@ class Job:
                 self.model.predict_device(x, y[:n], nan_guard=True, nonfinite=self.bad)
 
         dt = self.timed(step, steps, warmup, pre_ms=PRE_WARM_MS / 2)
+        if keep:
+            self.kept = y[:n].cpu().numpy()
         ms = dt / steps * 1e3
         return {"ms_per_step_rank_min_max": list(self.last_rank_ms), "metric": "tiled SR fields/s (40x40x3 -> 1600x1600x3 via 4x4 tiles; BASELINE config 5)", "value": round(1.0 / (ms * 1e-3), 2),
                 "unit": "fields/s", "ms_per_field": round(ms, 4), "steps": steps, "warmup": warmup, "dtype": "f16", "tile_samples": 48,
@@ -663,9 +704,9 @@ def dry_run(args, env):
                       "not_counted": "the trainers of the train leg (f32 activations of a micro-batch of 8-32 samples: < 2 GB per rank)"}
         except Exception as e:   # noqa: BLE001 -- the rehearsal must not die on an estimate
             budget = {"error": f"{type(e).__name__}: {e}"}
-    # the tail of a real run: rank 0's own legs (host entry, CPU stand-in, oracle check) while the others wait at one barrier
+    # the tail of a real --full run: rank 0's own legs (host entry, CPU stand-in, oracle check) while the others wait at one barrier
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             import numpy as np
             stats_lr, stats_hr = srcfd.load_stats(STATS_TXT, 10, 400)
@@ -706,10 +747,14 @@ def main():
 
     job = Job(args)
     torch, np = job.torch, job.np
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
+    cpu_leg = args.full and not args.no_cpu_baseline
+    dump = args.dump_outputs is not None and job.rank == 0
 
     if args.workload == "tiled":
-        rec = job.run_tiled(args.steps, args.warmup)
+        rec = job.run_tiled(args.steps, args.warmup, keep=dump)
+        if dump:
+            write_outputs(args.dump_outputs, {"y": job.kept, "y_sample_index": np.arange(len(job.kept), dtype=np.float64)})
         if job.rank == 0:
             print(json.dumps({"metric": rec["metric"], "value": rec["value"], "unit": rec["unit"], "n_gpus": job.world,
                               "world_size_reported": job.world_reported, "steps": args.steps, "warmup": args.warmup,
@@ -750,14 +795,14 @@ def main():
     if extras and args.precision != "fp32":
         def _parity():
             rec, y_par = job.run_sr("fp32", "f32", max(5, min(args.steps, 20)), min(args.warmup, 3))
-            if job.rank == 0 and not args.no_cpu_baseline:
+            if job.rank == 0 and cpu_leg:
                 y_gpu["fp32"] = y_par[:8].cpu().numpy()
             return rec
         parity = leg("parity_path", _parity)
 
         def _parity_x3():   # the same batch at SRCFD_PREC_FP32X3: f32-grade, ConvT#0 / ConvT#1 as six bf16 MFMAs on exactly split operands
             rec, y_par = job.run_sr("fp32x3", "f32", max(5, min(args.steps, 20)), min(args.warmup, 3))
-            if job.rank == 0 and not args.no_cpu_baseline:
+            if job.rank == 0 and cpu_leg:
                 y_gpu["fp32x3"] = y_par[:8].cpu().numpy()
             if "roofline" in rec:   # rank 0 only
                 rec["roofline"]["note"] = ("algorithmic f32 FLOPs over the f32 MFMA peak, as for parity_path -- but ConvT#0 / ConvT#1 (45 % of the MACs) run as 6 bf16 "
@@ -766,15 +811,20 @@ def main():
         parity_x3 = leg("parity_path_x3", _parity_x3)
 
     pci = None
-    try:
-        pr = torch.cuda.get_device_properties(job.local_rank)
-        pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
-    except Exception:   # noqa: BLE001
-        pass
-    gpu_before = gpu_state(pci) if job.rank == 0 else None
-    head, y_head = job.run_sr(args.precision, args.out_dtype, args.steps, args.warmup)
-    gpu_after = gpu_state(pci) if job.rank == 0 else None
-    if job.rank == 0 and not args.no_cpu_baseline and args.out_dtype == "f32":
+    if args.full:
+        try:
+            pr = torch.cuda.get_device_properties(job.local_rank)
+            pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
+        except Exception:   # noqa: BLE001
+            pass
+    gpu_before = gpu_state(pci) if job.rank == 0 and args.full else None
+    keep = dump_index(job.n) if dump else None
+    head, y_head = job.run_sr(args.precision, args.out_dtype, args.steps, args.warmup, keep=keep)
+    gpu_after = gpu_state(pci) if job.rank == 0 and args.full else None
+    if dump:
+        write_outputs(args.dump_outputs, {"y": job.kept, "y_sample_index": keep.astype(np.float64)})
+        del job.kept
+    if job.rank == 0 and cpu_leg and args.out_dtype == "f32":
         y_gpu[args.precision] = y_head[:8].cpu().numpy()
     del y_head
 
@@ -792,7 +842,7 @@ def main():
                 host_io = job.run_host_io()
             except Exception as e:   # noqa: BLE001
                 extra_errors["host_io"] = f"{type(e).__name__}: {e}"[:300]
-        if not args.no_cpu_baseline:
+        if cpu_leg:
             try:
                 cpu = cpu_baseline(job.x_h, job.ain_h, job.aout_h, job.enc_w, job.dec_w, y_gpu)
                 for rec_, key_ in ((parity, "fp32"), (parity_x3, "fp32x3")):
@@ -824,15 +874,19 @@ def main():
                        "fields_per_gpu": args.fields, "samples_per_gpu": job.n, "out_dtype": args.out_dtype,
                        "weights": "encoder: reference multiBC .h5; decoder: random init seed 1 (reference decoder .h5 absent)",
                        "parallelism": f"sample-sharded x{job.world}, no collective", "backend": job.backend if job.world > 1 else None},
-            "tflops_model": head["tflops_model"], "nonfinite": head["nonfinite"],
-            "kernels_ms": head.get("kernels_ms"), "kernels_ms_sum": head.get("kernels_ms_sum"), "kernels_ms_in_step_scale": head.get("kernels_ms_in_step_scale"),
-            "launch_gap_ms": head.get("launch_gap_ms"),
-            "roofline": head.get("roofline"), "last_plan": head.get("last_plan"),
-            "cpu_baseline": cpu,
-            "parity_path": parity, "parity_path_x3": parity_x3, "fastest_path_within_1e-5": best_1e5, "train": train, "tiled": tiled, "host_io": host_io,
+            "tflops_model": head["tflops_model"], "nonfinite": head["nonfinite"], "last_plan": head.get("last_plan"),
             "ms_per_step_rank_min_max": head.get("ms_per_step_rank_min_max"), "untimed_pre_warm_ms": head.get("untimed_pre_warm_ms"),
-            "env": dict(env, gpu_state_before_headline=gpu_before, gpu_state_after_headline=gpu_after),
+            "full": args.full, "env": env,
         }
+        if args.full:
+            out.update({
+                "kernels_ms": head.get("kernels_ms"), "kernels_ms_sum": head.get("kernels_ms_sum"), "kernels_ms_in_step_scale": head.get("kernels_ms_in_step_scale"),
+                "launch_gap_ms": head.get("launch_gap_ms"),
+                "roofline": head.get("roofline"),
+                "cpu_baseline": cpu,
+                "parity_path": parity, "parity_path_x3": parity_x3, "fastest_path_within_1e-5": best_1e5, "train": train, "tiled": tiled, "host_io": host_io,
+                "env": dict(env, gpu_state_before_headline=gpu_before, gpu_state_after_headline=gpu_after),
+            })
         if extra_errors:
             out["sub_record_errors"] = extra_errors
         if bad_env:

@@ -140,7 +140,7 @@ def test_bench_eight_rank_rehearsal():
     the 48 tile samples of config 5 shard 6 per rank, the training legs see global batch 64 (weak) and 32 samples per rank
     (strong, global batch 256), min / max over ranks are both reduced, and the outcome of a leg that fails on ONE rank is known
     on every rank (the all-or-none agreement that keeps the others out of a collective)."""
-    rc, recs, err = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1"], {"SRCFD_BENCH_DRYRUN": "1"})
+    rc, recs, err = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full"], {"SRCFD_BENCH_DRYRUN": "1"})
     assert rc == 0, err[-2000:]
     r = recs[0]
     assert r["n_gpus"] == 8 and r["world_size_reported"] == 8 and r["fields_total"] == 8 * 256
@@ -158,7 +158,7 @@ def test_bench_eight_rank_rehearsal():
     assert legs["tiled_f16"]["device_workspace"] == 2 * 6 * 160000 * 2 + 16 * 6 * 128 * 4
     # rank 0's own legs run behind the collective ones for any N, the other ranks wait at one barrier: the N > 1 line carries them
     assert r["cpu_baseline"]["value"] > 0 and r["cpu_baseline"]["kind"] == "port" and r["cpu_baseline"]["cores"] >= 1, r["cpu_baseline"]
-    rc, recs, err = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1"], {"SRCFD_BENCH_DRYRUN": "1", "SRCFD_BENCH_DRYRUN_FAIL_RANK": "5"})
+    rc, recs, err = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full"], {"SRCFD_BENCH_DRYRUN": "1", "SRCFD_BENCH_DRYRUN_FAIL_RANK": "5"})
     assert rc == 0 and recs[0]["leg_failed_somewhere"] is True
 
 
@@ -204,7 +204,7 @@ def test_bench_refuses_a_stale_traffic_file(tmp_path, monkeypatch):
 def test_bench_two_ranks_share_one_gpu():
     """The full rank path of bench.py (`--gpus 2` -> two child ranks, barrier, MAX over ranks, aggregate) on ONE GPU with the
     gloo backend standing in for RCCL; 8 fields per rank.  n_gpus and the aggregate must reflect both ranks."""
-    rc, recs, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--fields", "16"],
+    rc, recs, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--fields", "16", "--full"],
                                {"SRCFD_BENCH_BACKEND": "gloo", "SRCFD_BENCH_CPU_BUDGET_S": "1"}, timeout=900)
     assert rc == 0, err[-2000:]
     r = recs[0]
@@ -240,7 +240,7 @@ def test_rccl_backend_two_gpus():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip(f"needs 2 GPUs for the RCCL backend, {torch.cuda.device_count()} visible")
-    rc, recs, err = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"], {}, timeout=900)
+    rc, recs, err = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"], {}, timeout=900)
     assert rc == 0, err[-2000:]
     r = recs[0]
     assert r["n_gpus"] == 2 and r["world_size_reported"] == 2 and r["config"]["backend"] == "nccl"

@@ -10,10 +10,10 @@ cd /tmp && export TMPDIR=/tmp
 export SRCFD_BENCH_ALLOW_DIAG=1
 for V in "$@"; do
   export $NAME=$V; mkdir -p $OUT/$V
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$V/stats -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 10 > $OUT/$V/stats_line.json 2> $OUT/$V/stats.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$V/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 10 > $OUT/$V/stats_line.json 2> $OUT/$V/stats.log
   for C in FETCH_SIZE WRITE_SIZE "${EXTRA_PMC:-GRBM_GUI_ACTIVE}"; do
     N=$(echo $C | tr ' ' '_' | cut -c1-40)
-    rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$V/pmc/$N -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 2 > $OUT/$V/pmc_$N.log 2>&1
+    rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$V/pmc/$N -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 2 > $OUT/$V/pmc_$N.log 2>&1
   done
   python3 $R/tools/pmc_summary.py $OUT/$V/pmc > $OUT/$V/pmc.json 2>/dev/null
   F=$(find $OUT/$V/stats -name "*kernel_stats.csv" | head -1)

@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/ablate_tail16s}; mkdir -p $OUT
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for A in ${ABLS:-0 1 2 4 8 16 32 7 56 63 128 256 191 319}; do
-  SRCFD_BENCH_ALLOW_DIAG=1 SRCFD_LIB=$R/sr-for-cfd_amd/lib/libsrcfd_diag.so SRCFD_TAIL_ABLATE=$A timeout -k 10 100 python3 $R/bench.py --no-extras --no-cpu-baseline --steps 30 > $OUT/a$A.json 2> $OUT/a$A.err
+  SRCFD_BENCH_ALLOW_DIAG=1 SRCFD_LIB=$R/sr-for-cfd_amd/lib/libsrcfd_diag.so SRCFD_TAIL_ABLATE=$A timeout -k 10 100 python3 $R/bench.py --full --no-extras --no-cpu-baseline --steps 30 > $OUT/a$A.json 2> $OUT/a$A.err
   python3 - <<PY
 import json
 try:

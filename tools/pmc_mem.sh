@@ -2,7 +2,7 @@
 # HBM traffic pass (inside gpurun): bash tools/pmc_mem.sh <tag> [bench args] -- FETCH_SIZE (KB; x2 on gfx950 for wide reads) / WRITE_SIZE per launch
 TAG=${1:-m}; shift; R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/pmcmem_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras $*"
+BENCH="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras $*"
 # one counter per pass: FETCH_SIZE and WRITE_SIZE together exceed what one pass can collect on gfx950
 timeout -k 10 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/a -- $BENCH > $OUT/a.log 2>&1
 timeout -k 10 150 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/b -- $BENCH > $OUT/b.log 2>&1

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for PREC in bf16 fp32; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/headline_$PREC -- python3 $R/bench.py --no-cpu-baseline --no-extras --precision $PREC --steps 300 --warmup 30 \
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/headline_$PREC -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --precision $PREC --steps 300 --warmup 30 \
       > $OUT/f_headline_only_${PREC}_bench_line.json 2> $OUT/headline_$PREC.log || echo "headline $PREC failed" >> $OUT/errors.txt
   F=$(find $OUT/headline_$PREC -name "*kernel_stats.csv" | head -1)
   [ -n "$F" ] && cp "$F" $OUT/f_headline_only_${PREC}_kernel_stats.csv
