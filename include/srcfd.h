@@ -298,6 +298,35 @@ typedef struct srcfd_coarse_problem {
 } srcfd_coarse_problem;
 int srcfd_coarse_solve(const srcfd_coarse_problem* problem, double* var_out, int* iterations, double rms[3]);
 
+/* ---- fine-mesh solver on the device (the solve the SR warm start is for) --------------------------
+ * Replaces `CFDSolver(...)` + the injection + `solver.solve()` of `run_fine_simulation_with_ml_init` / `run_normal_simulation`
+ * (PyCFD_ML_accelerated.py:882-966, 1126-1184; bfs_ml_accelerated.py:1140-1300): the loop of srcfd_coarse_solve for the same
+ * srcfd_coarse_problem (same validation; max_iterations is ignored, run() takes its own), float64, resident on `device`.
+ * Inner sweeps: momentum Jacobi, pressure red-black (colour (i+j)&1, colour 0 first) -- the one deliberate difference from the
+ * host's serial sweeps; tests/fine_solver_spec.py restates the whole loop in numpy and the device reproduces it bit for bit. */
+typedef struct srcfd_fine_solver srcfd_fine_solver;
+int srcfd_fine_solver_create(const srcfd_coarse_problem* problem, int device, srcfd_fine_solver** out);
+void srcfd_fine_solver_destroy(srcfd_fine_solver* s);
+/* var NULL: `_initialize_fields` (zero fields, :377-390).  Otherwise the interior of var (3, nx+2, ny+2), host float64, is
+ * taken (ghosts and corners start at 0).  Then the injection sequence of :940-953: BCs (BFS: with the inlet), Old = Var,
+ * linear_interpolation.  Resets the iteration count. */
+int srcfd_fine_solver_init(srcfd_fine_solver* s, const double* var);
+/* The srcfd_predict_into_solver_state hand-off (with the solver's own BCs; BFS: its inlet rows as left profiles) written
+ * straight into the solver's device Var, then the priming of srcfd_fine_solver_init.  No field crosses to the host. */
+int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m, srcfd_resampler* r, const float* x,
+                                           const float* in_affine, const float* out_affine, int flags, int64_t* n_nonfinite);
+/* Up to max_iterations more outer iterations (none once converged).  *iterations = outer iterations since init; rms = the
+ * last _convergence_check's residuals; history [history_len][3] receives rms at every iteration count divisible by 100 that
+ * this call reaches, in order (residual_history, :418-421).  run(N) then run(M) equals run(N+M) bit for bit.  NaN / Inf in
+ * the residuals: SRCFD_EINVAL with srcfd_coarse_solve's message (the reference raises ValueError). */
+int srcfd_fine_solver_run(srcfd_fine_solver* s, int max_iterations, int* iterations, double rms[3], double* history, int history_len);
+/* Copies Var (3, nx+2, ny+2) to host memory. */
+int srcfd_fine_solver_get_state(srcfd_fine_solver* s, double* var);
+/* counters: [0] momentum sweeps executed, [1] pressure sweeps executed (one red-black pair each), [2] device operations
+ * enqueued (kernel launches, memsets), [3] host synchronisations; all since create.  last_sweeps: sweeps of the u, v and p
+ * solves of the last outer iteration.  Either may be NULL. */
+int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], int last_sweeps[3]);
+
 /* ---- training -----------------------------------------------------------
  * One optimisation step of SuperResolutionAE, split so that a data-parallel driver can put its
  * gradient all-reduce between the two halves (one flat f32 buffer per step).

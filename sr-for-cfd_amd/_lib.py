@@ -124,6 +124,13 @@ _protos = {
     "srcfd_model_load_superres_h5": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_p)]),
     "srcfd_prepare_inputs_device": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_double, _p, _p, _p]),
     "srcfd_coarse_solve": (C.c_int, [C.POINTER(CoarseProblem), _p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "srcfd_fine_solver_create": (C.c_int, [C.POINTER(CoarseProblem), C.c_int, C.POINTER(_p)]),
+    "srcfd_fine_solver_destroy": (None, [_p]),
+    "srcfd_fine_solver_init": (C.c_int, [_p, _p]),
+    "srcfd_fine_solver_init_from_prediction": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.POINTER(C.c_int64)]),
+    "srcfd_fine_solver_run": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), _p, C.c_int]),
+    "srcfd_fine_solver_get_state": (C.c_int, [_p, _p]),
+    "srcfd_fine_solver_counters": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "srcfd_adam_step": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _p]),
     "srcfd_stats_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "srcfd_stats_save": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),

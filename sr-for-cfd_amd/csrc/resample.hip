@@ -216,6 +216,64 @@ __global__ void __launch_bounds__(256) solver_state_f64(const T* __restrict__ fi
   Var[idx] = v;
 }
 
+// The hand-off behind srcfd_predict_into_solver_state and srcfd_fine_solver_init_from_prediction: predict the u, v, p samples
+// of one field, [resample,] and write the solver state Var into d_var (nullptr: the model's own scratch); host_var, when not
+// nullptr, receives a copy.  want_nx / want_ny >= 0: the mesh the caller expects (mismatch -> SRCFD_EINVAL).  Default stream;
+// returns after the stream has drained.
+int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const float* in_affine, const float* out_affine,
+                         const srcfd_solver_bc bc[3], int want_nx, int want_ny, double* d_var, double* host_var, int flags,
+                         int64_t* n_nonfinite) {
+  Resampler* rr = reinterpret_cast<Resampler*>(r);
+  const int* os = mm->desc.out_shape();
+  if (os[2] != 1) { set_error("srcfd_predict_into_solver_state: single-channel models only"); return SRCFD_EINVAL; }
+  if (rr && (os[0] != rr->H || os[1] != rr->W || mm->device != rr->device)) {
+    set_error("srcfd_predict_into_solver_state: resampler does not match the model");
+    return SRCFD_EINVAL;
+  }
+  const int ny = rr ? rr->OH : os[0], nx = rr ? rr->OW : os[1];
+  if ((want_nx >= 0 && want_nx != nx) || (want_ny >= 0 && want_ny != ny)) {
+    set_error("srcfd_fine_solver_init_from_prediction: the prediction's mesh (" + std::to_string(nx) + " x " + std::to_string(ny) +
+              ") is not the solver's (" + std::to_string(want_nx) + " x " + std::to_string(want_ny) + ")");
+    return SRCFD_EINVAL;
+  }
+  BcDev b{};
+  std::vector<double> prof((size_t)3 * ny, 0.0);
+  bool any_profile = false;
+  for (int k = 0; k < 3; ++k) {
+    for (int s = 0; s < 4; ++s) { b.type[k][s] = bc[k].type[s]; b.value[k][s] = bc[k].value[s]; }
+    b.has_profile[k] = bc[k].left_profile != nullptr;
+    if (bc[k].left_profile) { std::memcpy(&prof[(size_t)k * ny], bc[k].left_profile, sizeof(double) * ny); any_profile = true; }
+  }
+  const size_t var_elems = (size_t)3 * (nx + 2) * (ny + 2);
+  return mm->predict_host(x, 3, in_affine, out_affine, nullptr, flags, n_nonfinite, [&](const float* y_dev, int first, int count) -> int {
+    if (first != 0 || count != 3) { set_error("srcfd_predict_into_solver_state: internal chunking error"); return SRCFD_EINVAL; }
+    const size_t need = (d_var ? 0 : var_elems) + prof.size();
+    if (need > mm->solver_state_elems) {
+      if (mm->d_solver_state) { HIPCHECK(hipFree(mm->d_solver_state)); mm->d_solver_state = nullptr; mm->solver_state_elems = 0; }
+      HIPCHECK(hipMalloc(&mm->d_solver_state, need * sizeof(double)));
+      mm->solver_state_elems = need;
+    }
+    double* d_out = d_var ? d_var : mm->d_solver_state;
+    double* d_prof = any_profile ? mm->d_solver_state + (d_var ? 0 : var_elems) : nullptr;
+    if (any_profile) HIPCHECK(hipMemcpyAsync(d_prof, prof.data(), prof.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    const unsigned blocks = (unsigned)((var_elems + 255) / 256);
+    int rc = SRCFD_OK;
+    if (rr) {
+      rc = rr->reserve(3);
+      if (rc) return rc;
+      rc = rr->run(y_dev, 3, rr->d_out, nullptr);
+      if (rc) return rc;
+      hipLaunchKernelGGL((solver_state_f64<double>), dim3(blocks), dim3(256), 0, nullptr, rr->d_out, ny, nx, b, d_prof, d_out);
+    } else {
+      hipLaunchKernelGGL((solver_state_f64<float>), dim3(blocks), dim3(256), 0, nullptr, y_dev, ny, nx, b, d_prof, d_out);
+    }
+    HIPCHECK(hipGetLastError());
+    if (host_var) HIPCHECK(hipMemcpyAsync(host_var, d_out, var_elems * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipStreamSynchronize(nullptr));
+    return rc;
+  });
+}
+
 }  // namespace srcfd
 
 using srcfd::Resampler;
@@ -392,51 +450,8 @@ int srcfd_predict_into_solver_state(srcfd_model* m, srcfd_resampler* r, const fl
                                     const srcfd_solver_bc bc[3], double* Var, int flags, int64_t* n_nonfinite) {
   return srcfd::abi_guard("srcfd_predict_into_solver_state", [&]() -> int {
     if (!m || !x || !bc || !Var) { set_error("srcfd_predict_into_solver_state: bad arguments"); return SRCFD_EINVAL; }
-    srcfd::Model* mm = reinterpret_cast<srcfd::Model*>(m);
-    Resampler* rr = reinterpret_cast<Resampler*>(r);
-    const int* os = mm->desc.out_shape();
-    if (os[2] != 1) { set_error("srcfd_predict_into_solver_state: single-channel models only"); return SRCFD_EINVAL; }
-    if (rr && (os[0] != rr->H || os[1] != rr->W || mm->device != rr->device)) {
-      set_error("srcfd_predict_into_solver_state: resampler does not match the model");
-      return SRCFD_EINVAL;
-    }
-    const int ny = rr ? rr->OH : os[0], nx = rr ? rr->OW : os[1];
-    srcfd::BcDev b{};
-    std::vector<double> prof((size_t)3 * ny, 0.0);
-    bool any_profile = false;
-    for (int k = 0; k < 3; ++k) {
-      for (int s = 0; s < 4; ++s) { b.type[k][s] = bc[k].type[s]; b.value[k][s] = bc[k].value[s]; }
-      b.has_profile[k] = bc[k].left_profile != nullptr;
-      if (bc[k].left_profile) { std::memcpy(&prof[(size_t)k * ny], bc[k].left_profile, sizeof(double) * ny); any_profile = true; }
-    }
-    const size_t var_elems = (size_t)3 * (nx + 2) * (ny + 2);
-    return mm->predict_host(x, 3, in_affine, out_affine, nullptr, flags, n_nonfinite, [&](const float* y_dev, int first, int count) -> int {
-      if (first != 0 || count != 3) { set_error("srcfd_predict_into_solver_state: internal chunking error"); return SRCFD_EINVAL; }
-      const size_t need = var_elems + prof.size();
-      if (need > mm->solver_state_elems) {
-        if (mm->d_solver_state) { HIPCHECK(hipFree(mm->d_solver_state)); mm->d_solver_state = nullptr; mm->solver_state_elems = 0; }
-        HIPCHECK(hipMalloc(&mm->d_solver_state, need * sizeof(double)));
-        mm->solver_state_elems = need;
-      }
-      double* d_var = mm->d_solver_state;
-      double* d_prof = any_profile ? d_var + var_elems : nullptr;
-      if (any_profile) HIPCHECK(hipMemcpyAsync(d_prof, prof.data(), prof.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
-      const unsigned blocks = (unsigned)((var_elems + 255) / 256);
-      int rc = SRCFD_OK;
-      if (rr) {
-        rc = rr->reserve(3);
-        if (rc) return rc;
-        rc = rr->run(y_dev, 3, rr->d_out, nullptr);
-        if (rc) return rc;
-        hipLaunchKernelGGL((srcfd::solver_state_f64<double>), dim3(blocks), dim3(256), 0, nullptr, rr->d_out, ny, nx, b, d_prof, d_var);
-      } else {
-        hipLaunchKernelGGL((srcfd::solver_state_f64<float>), dim3(blocks), dim3(256), 0, nullptr, y_dev, ny, nx, b, d_prof, d_var);
-      }
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipMemcpyAsync(Var, d_var, var_elems * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-      HIPCHECK(hipStreamSynchronize(nullptr));
-      return rc;
-    });
+    return srcfd::predict_solver_state(reinterpret_cast<srcfd::Model*>(m), r, x, in_affine, out_affine, bc, -1, -1, nullptr, Var, flags,
+                                       n_nonfinite);
   });
 }
 

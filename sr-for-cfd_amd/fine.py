@@ -1,0 +1,277 @@
+"""The fine-mesh solve the SR warm start is for, on the device: `run_fine_simulation_with_ml_init`, `run_normal_simulation` and
+`run_ml_accelerated_fine_simulation` of the reference's lid-driven-cavity solver (PyCFD_ML_accelerated.py:882-966, 1024-1184) and
+of its backward-facing-step solver (bfs_ml_accelerated.py:1140-1300, 1384-1518; `run_bfs_*` here, as
+coarse.run_bfs_coarse_simulation), on libsrcfd's float64 device solver (csrc/fine_solver.hip, C ABI `srcfd_fine_solver_*`).
+
+`FineSolver` keeps the state on the device; `.Var` is a host copy in the reference's layout (3, nx+2, ny+2), and `.mesh` has the
+reference's MeshParameters fields, so the reference's `extract_centerlines(solver, nx, ny)` works on it unchanged.  The loop is
+srcfd_coarse_solve's; its inner sweeps are Jacobi (momentum) and red-black (pressure) -- tests/fine_solver_spec.py is the
+specification.  No plots; `output_name` writes the HDF5 field file in coarse.save_coarse_fields' layout.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import time
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import _lib as L
+from .coarse import BFS_RUN_COARSE_DEFAULT, LDC_SINGLE_LID, SIDES, _bc_dicts, _bc_entry, save_coarse_fields
+
+COMPONENTS = ("u", "v", "p")
+_DEFAULT_CC = {"u": 1e-6, "v": 1e-6, "p": 1e-6, "continuity": 1e-6}
+
+
+class MeshParameters:
+    """PyCFD_ML_accelerated.py:69-77."""
+
+    def __init__(self, nx: int, ny: int, lx: float = 1.0, ly: float = 1.0):
+        self.nx, self.ny, self.lx, self.ly = nx, ny, lx, ly
+        self.dx, self.dy = lx / nx, ly / ny
+        self.volp = self.dx * self.dy
+
+
+def problem(Re: float, nx: int, ny: int, lx: float = 1.0, ly: float = 1.0, dt: float = 0.001, scheme: str = "QUICK",
+            convergence_criteria: Optional[Dict[str, float]] = None, bc=None, rho: float = 1.0, bfs: Optional[Dict[str, float]] = None,
+            relaxation_factors: Optional[Dict[str, float]] = None) -> L.CoarseProblem:
+    """The srcfd_coarse_problem of a solve (the same fields coarse.solve_coarse fills)."""
+    if scheme not in ("QUICK", "UPWIND"):
+        raise ValueError(f"scheme must be 'QUICK' or 'UPWIND', not {scheme!r}")
+    cc = {"u": 1e-6, "v": 1e-6, "p": 1e-6}
+    cc.update(convergence_criteria or {})
+    pb = L.CoarseProblem()
+    pb.nx, pb.ny, pb.lx, pb.ly = int(nx), int(ny), float(lx), float(ly)
+    pb.reynolds, pb.rho, pb.dt = float(Re), float(rho), float(dt)
+    pb.scheme = 0 if scheme == "QUICK" else 1
+    pb.max_iterations = 0
+    d_all = _bc_dicts(bc, BFS_RUN_COARSE_DEFAULT if bfs is not None else LDC_SINGLE_LID)
+    for k, c in enumerate(COMPONENTS):
+        pb.tolerance[k] = float(cc[c])
+        for s_, side in enumerate(SIDES):
+            t, v = _bc_entry(d_all[c][side])
+            pb.bc_type[k][s_] = 0 if t == "dirichlet" else 1
+            pb.bc_value[k][s_] = v
+    if bfs is not None:
+        rf = {"u": 0.5, "v": 0.5, "p": 0.2} if relaxation_factors is None else relaxation_factors
+        pb.case_type = 1
+        for k, c in enumerate(COMPONENTS):
+            pb.relax[k] = float(rf.get(c, 0.2 if c == "p" else 0.5))
+        pb.step_height, pb.channel_height, pb.bulk_velocity = float(bfs["step_height"]), float(bfs["h"]), float(bfs["Ub"])
+    return pb
+
+
+class FineSolver:
+    """Device-resident float64 solver state for one problem (srcfd_fine_solver_*).  Starts from `_initialize_fields`."""
+
+    def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0):
+        self.problem = pb
+        self.max_iterations = int(max_iterations)
+        self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
+        self.residual_history = {"u": [], "v": [], "p": []}
+        self.iterations = 0
+        self.rms = np.zeros(3)
+        self._h = C.c_void_p()
+        L.check(L.lib.srcfd_fine_solver_create(C.byref(pb), int(device), C.byref(self._h)))
+        self.init()
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            L.lib.srcfd_fine_solver_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def shape(self):
+        return (3, self.mesh.nx + 2, self.mesh.ny + 2)
+
+    def _reset(self):
+        self.residual_history = {"u": [], "v": [], "p": []}
+        self.iterations = 0
+
+    def init(self, Var: Optional[np.ndarray] = None) -> None:
+        """Var None: zero fields; otherwise its interior (3, nx+2, ny+2).  Then BCs, Old = Var, linear_interpolation."""
+        if Var is None:
+            L.check(L.lib.srcfd_fine_solver_init(self._h, None))
+        else:
+            Var = np.ascontiguousarray(Var, dtype=np.float64)
+            if Var.shape != self.shape:
+                raise ValueError(f"Var must have shape {self.shape}, not {Var.shape}")
+            L.check(L.lib.srcfd_fine_solver_init(self._h, Var.ctypes.data_as(C.c_void_p)))
+        self._reset()
+
+    def init_fields(self, fields: Dict[str, np.ndarray]) -> None:
+        """The reference's injection `Var[k, 1:-1, 1:-1] = fields[c].T` (fields (ny, nx)), then the priming of `init`."""
+        Var = np.zeros(self.shape)
+        for k, c in enumerate(COMPONENTS):
+            Var[k, 1:-1, 1:-1] = np.asarray(fields[c]).T
+        self.init(Var)
+
+    def init_from_prediction(self, model, x, in_affine=None, out_affine=None, resampler=None, nan_guard: bool = True) -> int:
+        """SR of the (3, lr, lr, 1) batch `x` straight into the device state (srcfd_fine_solver_init_from_prediction).
+        Returns the number of NaN / Inf values the guard replaced."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        aff = [None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(3, 2) for a in (in_affine, out_affine)]
+        bad = C.c_int64(0)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        L.check(L.lib.srcfd_fine_solver_init_from_prediction(self._h, model._h, resampler._h if resampler is not None else None,
+                                                             p(x), p(aff[0]), p(aff[1]), L.FLAG_NAN_GUARD if nan_guard else 0,
+                                                             C.byref(bad)))
+        self._reset()
+        return int(bad.value)
+
+    def run(self, n: int) -> int:
+        """Up to n more outer iterations; returns the outer iterations since init."""
+        it = C.c_int(0)
+        rms = (C.c_double * 3)()
+        hist = np.zeros((n // 100 + 1, 3))
+        before = self.iterations
+        try:
+            L.check(L.lib.srcfd_fine_solver_run(self._h, int(n), C.byref(it), rms, hist.ctypes.data_as(C.c_void_p), hist.shape[0]))
+        except ValueError as e:
+            if "NaN" in str(e):
+                raise ValueError("Solver failed: NaN/Inf in residuals") from e   # what the reference raises (PyCFD...:487-492)
+            raise
+        self.iterations = int(it.value)
+        self.rms = np.array(list(rms))
+        for r in hist[:self.iterations // 100 - before // 100]:
+            for k, c in enumerate(COMPONENTS):
+                self.residual_history[c].append(float(r[k]))
+        return self.iterations
+
+    def solve(self, max_iterations: Optional[int] = None) -> int:
+        """Runs until converged or `max_iterations` outer iterations in all (default: the problem's cap)."""
+        cap = self.max_iterations if max_iterations is None else int(max_iterations)
+        return self.run(max(0, cap - self.iterations))
+
+    @property
+    def Var(self) -> np.ndarray:
+        out = np.empty(self.shape)
+        L.check(L.lib.srcfd_fine_solver_get_state(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def counters(self) -> Dict[str, object]:
+        c = (C.c_int64 * 4)()
+        s = (C.c_int * 3)()
+        L.check(L.lib.srcfd_fine_solver_counters(self._h, c, s))
+        return {"momentum_sweeps": c[0], "pressure_sweeps": c[1], "launches": c[2], "host_syncs": c[3], "last_sweeps": list(s)}
+
+    def fields(self) -> Dict[str, np.ndarray]:
+        V = self.Var
+        return {c: V[k, 1:-1, 1:-1].T.copy() for k, c in enumerate(COMPONENTS)}
+
+    def save(self, path: str, Re: float, bfs_step_height: Optional[float] = None) -> None:
+        save_coarse_fields(path, self.fields(), Re, self.mesh.lx, self.mesh.ly, bfs_step_height=bfs_step_height)
+
+
+def _finish(solver: FineSolver, Re, output_name, suffix, bfs_step_height=None):
+    t0 = time.time()
+    it = solver.solve()
+    elapsed = time.time() - t0
+    if output_name is not None:
+        name = output_name if output_name.endswith(suffix) else f"{output_name}{suffix}"
+        d = os.path.dirname(name)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        solver.save(f"{name}.h5", Re, bfs_step_height=bfs_step_height)
+    return solver, it, elapsed
+
+
+# ---------------------------------------------------------------------------------------------- lid-driven cavity
+def run_fine_simulation_with_ml_init(Re: float, nx: int, ny: int, ml_initial_fields: Dict[str, np.ndarray], dt: float = 0.001,
+                                     scheme: str = "QUICK", convergence_criteria: Optional[Dict[str, float]] = None,
+                                     max_iterations: int = 100000, output_name: Optional[str] = "cavity_accelerated", bc=None) -> tuple:
+    """PyCFD_ML_accelerated.py:882-963: (solver, iterations, time_elapsed); fields (ny, nx) are injected transposed."""
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations)
+    s.init_fields(ml_initial_fields)
+    return _finish(s, Re, output_name, "_accelerated")
+
+
+def run_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.001, scheme: str = "QUICK",
+                          convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
+                          output_name: Optional[str] = "cavity_normal", bc=None) -> tuple:
+    """PyCFD_ML_accelerated.py:1126-1184: the same solve from zero fields."""
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations)
+    return _finish(s, Re, output_name, "_normal")
+
+
+def _model_files(stats_file, encoder_file, decoder_file):
+    for fname, desc in ((stats_file, "Stats file"), (encoder_file, "Encoder model"), (decoder_file, "Decoder model")):
+        if not os.path.exists(fname):
+            raise FileNotFoundError(f"{desc} not found: {fname}")
+
+
+def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re: float, nx: int, ny: int, lr_dim: int = 10,
+                                       dt: float = 0.001, scheme: str = "QUICK", convergence_criteria: Optional[Dict[str, float]] = None,
+                                       max_iterations_fine: int = 100000, output_name: Optional[str] = None, stats_file: Optional[str] = None,
+                                       encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
+                                       precision: Optional[str] = None) -> tuple:
+    """PyCFD_ML_accelerated.py:1024-1123: coarse fields -> SR straight into the device solver state -> fine solve.  The only
+    400x400 field that crosses to the host is the result (`solver.Var`, on demand)."""
+    from . import pipeline
+    stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}.txt"
+    encoder_file = encoder_file or f"vanilla_encoder{lr_dim}_to_{nx}.h5"
+    decoder_file = decoder_file or f"vanilla_decoder{nx}_from_{lr_dim}.h5"
+    output_name = output_name or f"cavity_Re{Re}_{nx}x{ny}"
+    _model_files(stats_file, encoder_file, decoder_file)
+    model, x, ain, aout, back, _ = pipeline._prepare(coarse_fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0,
+                                                     False, 0.3, precision, pipeline._quiet)
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations_fine, model.device)
+    pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
+    return _finish(s, Re, output_name, "_accelerated")
+
+
+# ---------------------------------------------------------------------------------------------- backward-facing step
+def _bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors):
+    return problem(Re, nx, ny, lx, ly, dt, scheme, convergence_criteria or _DEFAULT_CC, bc,
+                   bfs={"step_height": step_height, "h": h, "Ub": Ub}, relaxation_factors=relaxation_factors)
+
+
+def run_bfs_fine_simulation_with_ml_init(Re: float, nx: int, ny: int, ml_initial_fields: Dict[str, np.ndarray], dt: float = 0.002,
+                                         scheme: str = "UPWIND", convergence_criteria: Optional[Dict[str, float]] = None,
+                                         max_iterations: int = 100000, output_name: Optional[str] = "bfs_accelerated", bc=None,
+                                         step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                                         relaxation_factors: Optional[Dict[str, float]] = None) -> tuple:
+    """bfs_ml_accelerated.py:1140-1234."""
+    s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
+                   max_iterations)
+    s.init_fields(ml_initial_fields)
+    return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
+
+
+def run_bfs_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.002, scheme: str = "UPWIND",
+                              convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
+                              output_name: Optional[str] = "bfs_normal", bc=None, step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0,
+                              lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None) -> tuple:
+    """bfs_ml_accelerated.py:1237-1307."""
+    s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
+                   max_iterations)
+    return _finish(s, Re, output_name, "_normal", bfs_step_height=step_height)
+
+
+def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re: float, nx: int, ny: int, lr_dim: int = 10,
+                                           dt: float = 0.002, scheme: str = "UPWIND", convergence_criteria: Optional[Dict[str, float]] = None,
+                                           max_iterations_fine: int = 100000, output_name: Optional[str] = None,
+                                           stats_file: Optional[str] = None, encoder_file: Optional[str] = None,
+                                           decoder_file: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0,
+                                           Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                                           relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
+                                           use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
+                                           precision: Optional[str] = None) -> tuple:
+    """bfs_ml_accelerated.py:1384-1518 (the BFS `ml_super_resolution`: adaptive normalisation, optional aspect-ratio resampling)."""
+    from . import pipeline
+    stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}_swish_trained_upto_700_multiBC.txt"
+    encoder_file = encoder_file or f"vanilla_encoder{lr_dim}_to_{nx}_swish_trained_upto_700_multiBC.h5"
+    decoder_file = decoder_file or f"vanilla_decoder{nx}_from_{lr_dim}_swish_trained_upto_700_multiBC.h5"
+    output_name = output_name or f"bfs_Re{Re}_{nx}x{ny}"
+    _model_files(stats_file, encoder_file, decoder_file)
+    model, x, ain, aout, back, _ = pipeline._prepare(coarse_fields, lr_dim, nx, stats_file, encoder_file, decoder_file,
+                                                     use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor, precision,
+                                                     pipeline._quiet)
+    s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
+                   max_iterations_fine, model.device)
+    pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
+    return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
