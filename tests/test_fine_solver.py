@@ -1,5 +1,6 @@
 """The fine-mesh solver's specification and C ABI without a GPU: the numpy restatement (tests/fine_solver_spec.py, the bits the
-device must produce) has the host solver's fixed point, and srcfd_fine_solver_create validates problems as srcfd_coarse_solve does."""
+device must produce) has the host solver's fixed point, its vectorised reduction orders and far-read indices are those of scalar
+restatements of the kernels' loops, and srcfd_fine_solver_create validates problems as srcfd_coarse_solve does."""
 import ctypes as C
 import importlib
 import os
@@ -52,6 +53,96 @@ def test_spec_inner_exit_rule_and_reduction_order():
     sp.run(3)
     assert all(1 <= n <= spec.CAP for sw in sp.sweeps for n in sw)
     assert sp.count == 3 and len(sp.sweeps) == 3
+
+
+# Scalar restatements of csrc/fine_solver.hip's loops, one thread at a time, in plain Python floats (IEEE float64): the
+# vectorised helpers of the specification must add in exactly these orders.
+def _block_sum(v):
+    """block_sum: lds[t] = v[t], then lds[t] += lds[t + s] for s = 128 .. 1; returns lds[0]."""
+    lds = list(v)
+    s = spec.NT // 2
+    while s > 0:
+        for t in range(s):
+            lds[t] = lds[t] + lds[t + s]
+        s //= 2
+    return lds[0]
+
+
+def _sum_partials(p):
+    """sum_partials: thread t adds p[t], p[t + 256], ... to 0.0, then block_sum."""
+    acc = []
+    for t in range(spec.NT):
+        a = 0.0
+        for q in range(t, len(p), spec.NT):
+            a = a + float(p[q])
+        acc.append(a)
+    return _block_sum(acc)
+
+
+def _pressure_row_partials(R2, colour):
+    """pressure_half_sweep's partials of one colour: row i (workgroup i - 1) starts at j0, thread t takes j0 + 2t, then + 512."""
+    nx, ny = R2.shape
+    out = []
+    for i in range(1, nx + 1):
+        j0 = 1 if ((i + 1) & 1) == colour else 2
+        acc = []
+        for t in range(spec.NT):
+            a = 0.0
+            for j in range(j0 + 2 * t, ny + 1, 2 * spec.NT):
+                a = a + float(R2[i - 1, j - 1])
+            acc.append(a)
+        out.append(_block_sum(acc))
+    return np.array(out)
+
+
+def _atw(nx, ny, k, i, j):
+    """atw (Grid::vw): the flat index a far read of plane k at (i, j) loads."""
+    sy, sx = ny + 2, (nx + 2) * (ny + 2)
+    if i < 0:
+        i += nx + 2
+    if j < 0:
+        j += ny + 2
+    idx = k * sx + i * sy + j
+    return min(idx, 3 * sx - 1)
+
+
+def _spanning(rng, n):
+    """n positive values whose magnitudes span 1e-8 .. 1e8, in random order."""
+    return 10.0 ** rng.uniform(-8.0, 8.0, n) * rng.uniform(1.0, 2.0, n)
+
+
+def test_spec_sum_order_is_the_kernels_block_and_partial_sums():
+    rng = np.random.default_rng(11)
+    differs_from_np_sum = 0
+    for n in (1, 2, 255, 256, 257, 511, 512, 513, 800, 1030):
+        v = _spanning(rng, n)
+        want = _sum_partials(v)
+        got = spec._sum256(v[None, :])[0]
+        assert np.float64(got).view(np.uint64) == np.float64(want).view(np.uint64), (n, got, want)
+        differs_from_np_sum += np.sum(v) != want
+    # the order is observable: a plain sum rounds differently somewhere, so equal bits above pin the order itself
+    assert differs_from_np_sum > 0
+
+
+def test_spec_colour_partials_are_the_pressure_kernels_order():
+    rng = np.random.default_rng(12)
+    for nx, ny in ((3, 3), (4, 5), (7, 512), (5, 513), (3, 1030)):
+        sp = spec.Spec(nx, ny, 1.0, 1.0, 100.0, 1.0, 0.001, "QUICK", [1e-6] * 3, [[0] * 4] * 3, [[0] * 4] * 3)
+        R2 = _spanning(rng, nx * ny).reshape(nx, ny)
+        for colour in (0, 1):
+            want = _pressure_row_partials(R2, colour)
+            got = sp._colour_partials(R2, colour)
+            np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64), err_msg=f"{nx}x{ny} colour {colour}")
+
+
+def test_spec_far_indices_are_the_kernels_wrapped_and_run_on_reads():
+    offsets = {"e": (2, 0), "w": (-2, 0), "n": (0, 2), "s": (0, -2)}
+    for nx, ny in ((3, 3), (4, 7), (9, 5)):
+        sp = spec.Spec(nx, ny, 1.0, 1.0, 100.0, 1.0, 0.001, "QUICK", [1e-6] * 3, [[0] * 4] * 3, [[0] * 4] * 3)
+        for k in (0, 1):
+            for name, (di, dj) in offsets.items():
+                want = np.array([[_atw(nx, ny, k, i + di, j + dj) for j in range(1, ny + 1)] for i in range(1, nx + 1)])
+                np.testing.assert_array_equal(sp._far[k, name], want, err_msg=f"{nx}x{ny} k={k} {name}")
 
 
 def _bad_problems(fine, coarse):

@@ -1,6 +1,7 @@
 """The device fine-mesh solver (csrc/fine_solver.hip, sr-for-cfd_amd/fine.py) on an MI355X: the same bits as its numpy
-specification (tests/fine_solver_spec.py), pinned to the reference's stored coarse field, the SR hand-off straight into the
-device state, resumable and deterministic runs, and the reference's drop-in functions."""
+specification (tests/fine_solver_spec.py) at the meshes and controls where the kernels branch, through convergence, divergence
+and re-init; pinned to the reference's stored coarse field, the SR hand-off straight into the device state, resumable and
+deterministic runs, and the reference's drop-in functions."""
 import importlib
 import os
 import signal
@@ -55,36 +56,201 @@ def _smooth_state(nx, ny, seed):
     return var
 
 
-def _cases(fine, coarse):
-    return {
-        "ldc_quick_double_lid": fine.problem(1000.0, 37, 29, 1.0, 1.0, 0.001, "QUICK", None, coarse.LDC_DOUBLE_LID),
-        "bfs_upwind": fine.problem(400.0, 37, 29, 10.0, 3.0, 0.002, "UPWIND", None, None,
-                                   bfs={"step_height": 1.0, "h": 2.0, "Ub": 1.0}),
-        # QUICK at the Neumann outlet with backflow reads past the plane (Grid::vw's run-on reads)
-        "bfs_quick_outlet_backflow": fine.problem(400.0, 37, 29, 10.0, 3.0, 0.002, "QUICK", None, None,
-                                                  bfs={"step_height": 1.0, "h": 2.0, "Ub": 1.0}),
-    }
+_BFS = {"step_height": 1.0, "h": 2.0, "Ub": 1.0}
+NT, CAP = spec.NT, spec.CAP
 
 
-@pytest.mark.parametrize("case", ["ldc_quick_double_lid", "bfs_upwind", "bfs_quick_outlet_backflow"])
+def _blocks(n):
+    """Workgroups of 256 threads that cover n (bc_kernel's grid for n = max(nx, ny))."""
+    return -(-n // NT)
+
+
+def _backflow(sp, ff0):
+    """The start state has backflow at the outlet, so QUICK's far east reads run on past the plane."""
+    return (ff0[0, sp.nx, 1:-1] < 0).any()
+
+
+def _quick_reads_ghosts(sp, ff0):
+    """The start fluxes select QUICK's far read (i±2 or j±2) at some cell where that read leaves the interior."""
+    sy = sp.ny + 2
+    for f, name in enumerate("enws"):
+        idx = sp._far[0, name]
+        i, j = idx // sy, idx % sy
+        off = (i < 1) | (i > sp.nx) | (j < 1) | (j > sp.ny)
+        if (off & (ff0[f, 1:-1, 1:-1] < 0)).any():
+            return True
+    return False
+
+
+def _momentum_chunks(sp, ff0):
+    """A momentum solve ran past the first 16-sweep chunk, and one ran past the chunk predicted from the previous solve."""
+    mom = [sw[:2] for sw in sp.sweeps]
+    past_first = any(n > 16 for n in mom[0])
+    past_predicted = any(mom[m][k] > min(mom[m - 1][k] + 2 + mom[m - 1][k] // 8, CAP) for m in range(1, len(mom)) for k in (0, 1))
+    return past_first and past_predicted
+
+
+def _momentum_cap(sp, ff0):
+    """A momentum solve stopped at the cap with finite values; final counts of both parities (the result in Jb or in Var)."""
+    mom = [n for sw in sp.sweeps for n in sw[:2]]
+    return CAP in mom and any(n % 2 for n in mom) and np.isfinite(sp.rms).all()
+
+
+# id: (problem(fine, coarse), outer iterations from _smooth_state(nx, ny, 7),
+#      reaches(spec after the run, spec.Ff after init): the case reaches the kernel path it is there for)
+CASES = {
+    "ldc_quick_double_lid": (lambda f, c: f.problem(1000.0, 37, 29, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID), 5,
+                             None),
+    "bfs_upwind": (lambda f, c: f.problem(400.0, 37, 29, 10.0, 3.0, 0.002, "UPWIND", None, None, bfs=_BFS), 5, None),
+    # QUICK at the Neumann outlet with backflow reads past the plane (Grid::vw's run-on reads)
+    "bfs_quick_outlet_backflow": (lambda f, c: f.problem(400.0, 37, 29, 10.0, 3.0, 0.002, "QUICK", None, None, bfs=_BFS), 5,
+                                  _backflow),
+    # a thread takes cells j, j + 256 of a row (momentum, correct_velocity); sum_partials adds partials q, q + 256 (momentum and
+    # convergence_check: 400, pressure: 800, also q + 512); bc_kernel on two workgroups
+    "ldc400_quick": (lambda f, c: f.problem(1000.0, 400, 400, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID), 3,
+                     lambda sp, ff0: sp.ny > NT and sp.nx > NT and 2 * sp.nx > 3 * NT and _blocks(max(sp.nx, sp.ny)) == 2),
+    # ... and the BFS inlet rows, the wall below the step in workgroup 0 and the parabola in both, with under-relaxation
+    "bfs400_upwind": (lambda f, c: f.problem(400.0, 400, 400, 10.0, 3.0, 0.002, "UPWIND", None, None, bfs=_BFS), 2,
+                      lambda sp, ff0: sp.ny > NT and sp.nx > NT and _blocks(sp.ny) == 2 and 0.5 * sp.dy < sp.bfs[0] < (NT + 0.5) * sp.dy),
+    # ny > 512: a thread takes 2 cells of one colour in a row (j += 2 * 256); odd nx, even ny; 262 pressure partials
+    "tall_131x530": (lambda f, c: f.problem(1000.0, 131, 530, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_SINGLE_LID), 3,
+                     lambda sp, ff0: sp.ny // 2 > NT and sp.nx % 2 == 1 and sp.ny % 2 == 0 and NT < 2 * sp.nx < 2 * NT),
+    # nx > 256 with ny < 256: multi-pass sum_partials and convergence_check; the second BC workgroup along i only
+    "wide_301x61": (lambda f, c: f.problem(400.0, 301, 61, 1.0, 1.0, 0.001, "UPWIND", None, c.LDC_DOUBLE_LID), 3,
+                    lambda sp, ff0: sp.nx > NT > sp.ny and _blocks(sp.nx) == 2),
+    # the exact bound where thread 0 first takes a second cell of a row
+    "ny256": (lambda f, c: f.problem(1000.0, 40, 256, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_SINGLE_LID), 3,
+              lambda sp, ff0: sp.ny == NT),
+    "ny257": (lambda f, c: f.problem(1000.0, 40, 257, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_SINGLE_LID), 3,
+              lambda sp, ff0: sp.ny == NT + 1),
+    # the smallest meshes create accepts: QUICK's far reads land on ghosts, most threads of a row have no cell
+    "edge_3x3": (lambda f, c: f.problem(100.0, 3, 3, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID), 5,
+                 lambda sp, ff0: sp.nx == sp.ny == 3 and _quick_reads_ghosts(sp, ff0)),
+    "edge_3x40": (lambda f, c: f.problem(100.0, 3, 40, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID), 5,
+                  lambda sp, ff0: sp.nx == 3 and _quick_reads_ghosts(sp, ff0)),
+    "edge_40x3": (lambda f, c: f.problem(100.0, 40, 3, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID), 5,
+                  lambda sp, ff0: sp.ny == 3 and _quick_reads_ghosts(sp, ff0)),
+    "momentum_chunks": (lambda f, c: f.problem(100.0, 40, 30, 1.0, 1.0, 0.05, "QUICK", None, c.LDC_DOUBLE_LID), 6,
+                        _momentum_chunks),
+    "momentum_cap": (lambda f, c: f.problem(10.0, 40, 30, 1.0, 1.0, 0.1, "QUICK", None, c.LDC_DOUBLE_LID), 4, _momentum_cap),
+}
+
+
+def _problem_and_start(fine, coarse, case):
+    pb = CASES[case][0](fine, coarse)
+    return pb, _smooth_state(pb.nx, pb.ny, seed=7)
+
+
+@pytest.mark.parametrize("case", list(CASES))
 def test_device_equals_the_specification_bit_for_bit(fine, coarse, case):
-    pb = _cases(fine, coarse)[case]
-    var0 = _smooth_state(37, 29, seed=7)
+    _, iterations, reaches = CASES[case]
+    pb, var0 = _problem_and_start(fine, coarse, case)
     sp = spec.from_problem(pb)
     sp.init(var0)
+    ff0 = sp.Ff.copy()
     s = fine.FineSolver(pb)
     s.init(var0)
     np.testing.assert_array_equal(_bits(s.Var), _bits(sp.Var))
-    if case == "bfs_quick_outlet_backflow":
-        f0 = sp.Ff[0, 37, 1:-1]
-        assert (f0 < 0).any(), "the state has no backflow at the outlet: the run-on reads are not exercised"
-    for n in range(1, 6):
+    for n in range(1, iterations + 1):
         assert s.run(1) == n
         sp.run(1)
         assert s.counters()["last_sweeps"] == sp.sweeps[-1], (n, s.counters()["last_sweeps"], sp.sweeps[-1])
         np.testing.assert_array_equal(_bits(s.rms), _bits(sp.rms))
     np.testing.assert_array_equal(_bits(s.Var), _bits(sp.Var))
-    assert s.iterations == sp.count == 5
+    assert s.iterations == sp.count == iterations
+    if reaches is not None:
+        assert reaches(sp, ff0), f"{case} does not reach the path it is there for (sweeps {sp.sweeps})"
+
+
+def _trace(s, n):
+    """n single outer iterations of a device solver: per iteration (rms bits, inner sweeps), or the NaN/Inf error and the
+    sweeps of the iteration that raised it."""
+    out = []
+    for _ in range(n):
+        try:
+            s.run(1)
+        except ValueError as e:
+            out.append((str(e), s.counters()["last_sweeps"]))
+            break
+        out.append((_bits(s.rms).tolist(), s.counters()["last_sweeps"]))
+    return out
+
+
+def test_convergence_history_and_reuse_of_a_handle(fine, coarse):
+    """12x10 from zero with a loose tolerance: the spec converges at iteration 584 with 5 residual_history entries."""
+    pb = fine.problem(100.0, 12, 10, 1.0, 1.0, 0.01, "QUICK", {"u": 1e-3, "v": 1e-3, "p": 1e-3}, coarse.LDC_DOUBLE_LID)
+    sp = spec.from_problem(pb)
+    sp.init()
+    sp.run(100000)
+    assert sp.converged and sp.count == 584 and len(sp.history) == 5
+    s = fine.FineSolver(pb)
+    assert s.run(150) == 150
+    assert s.run(1000) == sp.count          # split across a history entry: none may be lost or repeated
+    np.testing.assert_array_equal(_bits(s.rms), _bits(sp.rms))
+    np.testing.assert_array_equal(_bits(s.Var), _bits(sp.Var))
+    assert s.counters()["last_sweeps"] == sp.sweeps[-1]
+    hist = np.array([s.residual_history[c] for c in "uvp"]).T
+    np.testing.assert_array_equal(_bits(hist), _bits(np.array(sp.history)))
+    # converged: a further run does nothing
+    cnt, rms, var = s.counters(), s.rms.copy(), s.Var
+    assert s.run(10) == sp.count
+    assert s.counters() == cnt
+    np.testing.assert_array_equal(_bits(s.rms), _bits(rms))
+    np.testing.assert_array_equal(_bits(s.Var), _bits(var))
+    assert [len(s.residual_history[c]) for c in "uvp"] == [5, 5, 5]
+    # re-init of the used handle: no stop flag, chunk prediction or converged state survives
+    var0 = _smooth_state(12, 10, seed=7)
+    s.init(var0)
+    fresh = fine.FineSolver(pb)
+    fresh.init(var0)
+    assert _trace(s, 5) == _trace(fresh, 5)
+    np.testing.assert_array_equal(_bits(s.Var), _bits(fresh.Var))
+    assert s.iterations == fresh.iterations == 5
+
+
+def test_divergence_raises_refuses_and_recovers_after_init(fine, coarse):
+    """40x30 UPWIND at dt 0.1 from zero: the spec's iteration 1 is finite ([33, 1, 280] sweeps), iteration 2 is not."""
+    pb = fine.problem(100.0, 40, 30, 1.0, 1.0, 0.1, "UPWIND", None, coarse.LDC_DOUBLE_LID)
+    sp = spec.from_problem(pb)
+    sp.init()
+    sp.run(1)
+    first = (_bits(sp.rms).tolist(), sp.sweeps[-1])
+    var1 = sp.Var.copy()
+    with pytest.raises(ValueError, match="NaN/Inf"), np.errstate(over="ignore", invalid="ignore"):
+        sp.run(1)
+    assert sp.sweeps[-1] == [CAP] * 3
+    s = fine.FineSolver(pb)
+    assert _trace(s, 1) == [first]
+    np.testing.assert_array_equal(_bits(s.Var), _bits(var1))
+    with pytest.raises(ValueError, match=r"^Solver failed: NaN/Inf in residuals$"):
+        s.run(1)
+    assert s.counters()["last_sweeps"] == sp.sweeps[-1]
+    with pytest.raises(ValueError, match="srcfd_fine_solver_init"):
+        s.run(1)
+    s.init()
+    assert _trace(s, 1) == [first]
+    np.testing.assert_array_equal(_bits(s.Var), _bits(var1))
+    assert s.iterations == 1
+
+
+def test_two_live_handles_do_not_share_state(fine, coarse):
+    """Alternating outer iterations of a 400x400 and a 40x30 solver equal each one's solo run."""
+    solo, pair = {}, {}
+    for case in ("ldc400_quick", "momentum_chunks"):
+        pb, var0 = _problem_and_start(fine, coarse, case)
+        s = fine.FineSolver(pb)
+        s.init(var0)
+        solo[case] = (_trace(s, 3), s.Var)
+        s.close()
+        pair[case] = fine.FineSolver(pb)
+        pair[case].init(var0)
+    got = {case: [] for case in pair}
+    for _ in range(3):
+        for case, s in pair.items():
+            got[case] += _trace(s, 1)
+    for case, s in pair.items():
+        assert got[case] == solo[case][0], case
+        np.testing.assert_array_equal(_bits(s.Var), _bits(solo[case][1]))
 
 
 def test_pinned_to_the_reference_field(srcfd, fine, coarse):
@@ -117,6 +283,14 @@ def _sr_inputs(srcfd, name):
     return x, np.array([lr[c] for c in "uvp"], np.float32), np.array([hr[c] for c in "uvp"], np.float32)
 
 
+def _same_two_iterations(s, t):
+    """The solver primed by init_from_prediction runs as the one primed by init(host): the same Var, Old and fluxes.  The
+    synthetic decoder's BFS field (|u| up to 16 at dx 0.025, dt 0.002) overflows, in the specification too: its second
+    iteration is the NaN/Inf error, after 1 000 sweeps of each inner solve, in both."""
+    assert _trace(s, 2) == _trace(t, 2)
+    np.testing.assert_array_equal(_bits(s.Var), _bits(t.Var))
+
+
 def test_hand_off_into_the_device_state_ldc(srcfd, fine, coarse, model):
     pipeline = importlib.import_module("sr-for-cfd_amd.pipeline")
     x, ain, aout = _sr_inputs(srcfd, "coarse_ldc_Re800_double_lid.h5")
@@ -130,6 +304,7 @@ def test_hand_off_into_the_device_state_ldc(srcfd, fine, coarse, model):
     t = fine.FineSolver(pb)
     t.init(host)
     np.testing.assert_array_equal(_bits(t.Var), _bits(dev))
+    _same_two_iterations(s, t)
 
 
 def test_hand_off_into_the_device_state_bfs(srcfd, fine, model):
@@ -151,6 +326,7 @@ def test_hand_off_into_the_device_state_bfs(srcfd, fine, model):
     t = fine.FineSolver(pb)
     t.init(host)
     np.testing.assert_array_equal(_bits(t.Var), _bits(dev))
+    _same_two_iterations(s, t)
 
 
 def test_resume_and_determinism_at_400(fine, coarse):
