@@ -338,6 +338,10 @@ int srcfd_trainer_create(const srcfd_model* m, int max_batch, srcfd_trainer** ou
 void srcfd_trainer_destroy(srcfd_trainer* t);
 int64_t srcfd_trainer_num_params(const srcfd_trainer* t);
 int srcfd_trainer_get_params(const srcfd_trainer* t, float* params_host);
+/* Which training path create chose (read-only): *fused_tail = 1 when the last four layers run as the two fused launches
+ * (tail32 forward, tail_bwd32 backward), *fused_encoder = 1 when the encoder's forward pass runs fused (train_enc); 0 = layer
+ * by layer.  Either pointer may be NULL. */
+int srcfd_trainer_get_plan(const srcfd_trainer* t, int* fused_tail, int* fused_encoder);
 /* Forward + backward on n <= max_batch samples: x_dev (n,h,w,c) inputs, y_dev targets of the model's
  * output shape.  ADDS d/dparams of loss_scale * sum((pred - y)^2) into grads_dev (zero it first; pass
  * loss_scale = 1 / (global batch * output elements) for Keras' reduce_mean(mse)) and adds the local sum of

@@ -754,7 +754,11 @@ size_t gemm_group_ws_floats(const GemmDesc* ds, int count, bool batch_invariant)
   return total;
 }
 
-bool gemm_supports_epi_aux(const GemmDesc& d) { return uses_generic_gemm(d) || (is_ci1_conv(d) && d.M > 0 && d.K > 0); }
+// the kernels launch_gemm_mfma picks that apply an EpiAux: the generic GEMM and conv_ci1_f32 -- the latter only where the N == 1
+// kernels in front of it do not take the layer first (a 1 -> 1 channel conv goes to conv_n1_f32, which has no training epilogue)
+bool gemm_supports_epi_aux(const GemmDesc& d) {
+  return uses_generic_gemm(d) || (is_ci1_conv(d) && d.M > 0 && d.K > 0 && !is_tiled_n1_conv(d) && !(d.N == 1 && d.K <= 512 && d.nphx == 1));
+}
 
 hipError_t launch_gemm_mfma_group(const GemmDesc* ds, int count, const float* X, const float* const* Bs, const float* const* biases, float* Y,
                                   hipStream_t s, float* ws, size_t ws_floats, bool batch_invariant, EpiAux aux) {

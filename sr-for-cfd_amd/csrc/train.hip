@@ -665,10 +665,25 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   ModelDesc im = index_model(t.desc, t.layers, t.n_params, t.init_params);
   if (t.n_params >= (1 << 24)) { set_error("training: more than 2^24 parameters"); return SRCFD_EINVAL; }
   if (t.layers.empty()) { set_error("training: model has no weights"); return SRCFD_EINVAL; }
+  for (const LayerInfo& L : t.layers) {   // the backward pass knows swish' and the identity only
+    const Layer& dl = t.desc.layers[L.desc_index];
+    if (dl.act != SRCFD_ACT_LINEAR && dl.act != SRCFD_ACT_SWISH) { set_error("training: layer '" + dl.name + "': only linear and swish activations are supported"); return SRCFD_EINVAL; }
+  }
   // forward plan over the index model: same descriptors and packed layout as inference
   std::vector<Op> iops;
   std::vector<float> ipack;
   build_plan(im, iops, ipack);
+  // Refused here, before anything runs: the step groups the GEMMs of one layer four at a time and the slab sums give a layer at
+  // most four ops (a strided transposed convolution whose kernel is not its stride plans into stride^2 output phases, e.g. 9 for
+  // stride 3), and the slab-sum table holds MAX_FINISH_OPS ops (+1 for the fused tail's slabs).
+  for (size_t i = 0, j = 0; i < iops.size(); i = j) {
+    while (j < iops.size() && iops[j].layer == iops[i].layer) ++j;
+    if (j - i > 4) {
+      set_error("training: layer '" + im.layers[iops[i].layer].name + "' plans into " + std::to_string(j - i) + " GEMMs; at most four per layer");
+      return SRCFD_EINVAL;
+    }
+  }
+  if (iops.size() + 1 > (size_t)MAX_FINISH_OPS) { set_error("training: more weight-gradient GEMMs than the slab-sum table holds"); return SRCFD_EINVAL; }
   // the fused tail's operands ride behind the forward pack, gathered by the same launch
   t.num_cus = model.num_cus > 0 ? model.num_cus : 256;
   {
@@ -998,6 +1013,16 @@ int srcfd_trainer_get_params(const srcfd_trainer* t, float* params_host) {
     if (!t || !params_host) { set_error("bad arguments"); return SRCFD_EINVAL; }
     const Trainer* tt = reinterpret_cast<const Trainer*>(t);
     std::memcpy(params_host, tt->init_params.data(), tt->init_params.size() * sizeof(float));
+    return SRCFD_OK;
+  });
+}
+
+int srcfd_trainer_get_plan(const srcfd_trainer* t, int* fused_tail, int* fused_encoder) {
+  return srcfd::abi_guard("srcfd_trainer_get_plan", [&]() -> int {
+    if (!t) { set_error("srcfd_trainer_get_plan: bad arguments"); return SRCFD_EINVAL; }
+    const Trainer* tt = reinterpret_cast<const Trainer*>(t);
+    if (fused_tail) *fused_tail = tt->use_tail ? 1 : 0;
+    if (fused_encoder) *fused_encoder = tt->use_enc ? 1 : 0;
     return SRCFD_OK;
   });
 }

@@ -388,7 +388,8 @@ hipError_t launch_tail_bwd32(const TailBwdParams& p, int num_cus, hipStream_t s)
   if (p.n <= 0) return hipSuccess;
   // x / d as umulhi(x, ceil(2^32 / d)): exact while x (ceil(2^32 / d) d - 2^32) < 2^32, i.e. for every x < 2^32 / d
   const uint64_t hw = (uint64_t)p.H * p.W;
-  if (p.W < 1 || p.H < 1 || (uint64_t)p.n * hw * hw >= (1ull << 32)) return hipErrorInvalidValue;
+  // W == 1 would make ceil(2^32 / W) = 2^32, which truncates to a magic of 0 (and H W == 1 likewise): train_tail_plan declines it
+  if (p.W < 2 || p.H < 1 || (uint64_t)p.n * hw * hw >= (1ull << 32)) return hipErrorInvalidValue;
   TailBwdParams q = p;
   q.magic_hw = (unsigned)(((1ull << 32) + hw - 1) / hw);
   q.magic_w = (unsigned)(((1ull << 32) + p.W - 1) / p.W);
@@ -418,6 +419,7 @@ void train_tail_plan(const ModelDesc& desc, const int* desc_index, const size_t*
     return;
   if (desc_index[f + 1] != desc_index[f] + 1 || desc_index[f + 2] != desc_index[f] + 2 || desc_index[f + 3] != desc_index[f] + 3) return;
   if (L1.in_shape[1] > 50) return;   // tail32's LDS ring holds rows of up to 400 pixels
+  if (L1.in_shape[1] < 2) return;    // tail_bwd32 divides by W and by H W as multiplies by ceil(2^32 / d): d = 1 does not fit 32 bits
   // the four layers' parameters must be one contiguous run in flat order (they are: kernel, bias per layer)
   const size_t o = kernel_off[f];
   if (bias_off[f] != o + TT_O_B1 || kernel_off[f + 1] != o + TT_O_W2 || bias_off[f + 1] != o + TT_O_B2 || kernel_off[f + 2] != o + TT_O_W3 ||

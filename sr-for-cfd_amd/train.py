@@ -94,6 +94,13 @@ class Trainer:
         except Exception:
             pass
 
+    @property
+    def plan(self) -> Dict[str, int]:
+        """The training path create chose: {"fused_tail": 0|1, "fused_encoder": 0|1} (srcfd_trainer_get_plan)."""
+        tail, enc = C.c_int(-1), C.c_int(-1)
+        L.check(L.lib.srcfd_trainer_get_plan(self._h, C.byref(tail), C.byref(enc)))
+        return {"fused_tail": tail.value, "fused_encoder": enc.value}
+
     def forward_backward(self, x, y, global_batch: Optional[int] = None, overwrite: bool = False, same_params: bool = False) -> None:
         """Accumulates this rank's gradient of the GLOBAL mean-squared error into self.grads (and the squared-error sum into
         self.sse); overwrite=True stores them instead (SRCFD_TRAIN_OVERWRITE: no zero-fill launches in front of the step).

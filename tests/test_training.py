@@ -151,6 +151,7 @@ def test_fused_stages_match_layer_by_layer_step(srcfd, enc_weights, dec_weights,
     def run(env):
         monkeypatch.setenv(switch, env)
         t = tr.Trainer(srcfd.SRModel.from_weights(enc_weights, dec_weights, device=0), max_batch=max(8, n))
+        assert t.plan[{"SRCFD_TRAIN_TAIL": "fused_tail", "SRCFD_TRAIN_ENC": "fused_encoder"}[switch]] == int(env)   # the path that runs
         out = []
         for _ in range(3):   # the third call replays the captured graph
             t.grads.zero_()
@@ -165,7 +166,6 @@ def test_fused_stages_match_layer_by_layer_step(srcfd, enc_weights, dec_weights,
     sse0, g0 = run("0")
     sse1, g1 = run("1")
     assert abs(sse1 - sse0) <= 2e-6 * abs(sse0)
-    assert not np.array_equal(g0, g1)      # the switch did select other kernels
     off = 0
     both = {**enc_weights, **dec_weights}
     for name in ag.flat_order(enc_weights, dec_weights):
@@ -268,6 +268,7 @@ def test_fused_tail_on_other_image_sizes(srcfd, monkeypatch, hw, n):
         m = srcfd.SRModel.from_layers(specs, (h, w, 3), device=0)
         assert m.output_shape == (8 * h, 8 * w, 1)
         t = tr.Trainer(m, max_batch=8)
+        assert t.plan["fused_tail"] == int(env)
         t.grads.zero_()
         t.sse.zero_()
         t.forward_backward(x, y)
