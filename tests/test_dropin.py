@@ -521,6 +521,7 @@ def test_tiled_sr_config5(srcfd, oracle, enc_weights, dec_weights):
     m = srcfd.SRModel.from_weights(enc_weights, dec_weights, device=0)
     m.precision = "f16"
     y = pl.tiled_super_resolution(field, m, lr_dim=10, in_affine=ain, out_affine=aout)
+    seg_tiled = int(m.last_plan()["tail_seg"])
     assert y.shape == (1600, 1600, 3) and np.isfinite(y).all()
     for ty in range(4):
         for tx in range(4):
@@ -528,12 +529,23 @@ def test_tiled_sr_config5(srcfd, oracle, enc_weights, dec_weights):
                 t = np.ascontiguousarray(field[10 * ty:10 * ty + 10, 10 * tx:10 * tx + 10, c])[None, ..., None]
                 one = m.predict(t, in_affine=ain[c:c + 1], out_affine=aout[c:c + 1])[0, ..., 0]
                 np.testing.assert_array_equal(y[400 * ty:400 * ty + 400, 400 * tx:400 * tx + 400, c], one)
+    xs, refs, gots = [], [], []
     for ty, tx, c in ((1, 2, 1), (0, 0, 0), (3, 3, 2), (2, 0, 1)):
         t = field[10 * ty:10 * ty + 10, 10 * tx:10 * tx + 10, c][None, ..., None]
         ts = ((t - ain[c, 0]) / ain[c, 1]).astype(np.float32)
         ref = oracle.superres_forward(ts, enc_weights, dec_weights, np.float64)[0, ..., 0]
         got = (y[400 * ty:400 * ty + 400, 400 * tx:400 * tx + 400, c] - aout[c, 0]) / aout[c, 1]
         assert oracle.rel_l2(got[None], ref[None]) <= 3e-3, (ty, tx, c)
+        xs.append(ts[0]); refs.append(ref); gots.append(got)
+    # a tile border is an image border for the network: a padding error would show as a grid in the stitched field, and the
+    # whole-field 3e-3 above would not see it.  The per-position class table of tests/error_maps.py on the same four tiles, with
+    # the seam classes of the segmentation the stitched call ran; margin from the two CPU emulations (error_maps.SPREAD), f16.
+    import error_maps as em
+    T = np.stack(refs)
+    E, _ = em.emulation(np.stack(xs), enc_weights, dec_weights, "f16")
+    ok, report, _, _ = em.class_check(np.stack(gots).astype(np.float64) - T, E - T, em.output_classes(seg_tiled), em.MARGIN["f16"], "tiled f16")
+    print(report)
+    assert ok, report
 
 
 @pytest.mark.gpu
