@@ -10,21 +10,22 @@
 #include "abi_guard.h"
 #include "kernels.h"
 #include "model.h"
+#include "operand_pack.h"
 
 namespace srcfd {
 
 extern thread_local std::string g_last_error;
 void set_error(const std::string& m);
 
-struct Op {
-  GemmDesc d;           // M filled per call (rows per image * batch)
-  size_t w_off = 0;     // into the packed float buffer: B[K][Npad]
-  size_t b_off = 0;     // bias[Npad]
-  int layer = 0;        // index into ModelDesc::layers
-  std::string name;
-};
-
-void build_plan(const ModelDesc& desc, std::vector<Op>& ops, std::vector<float>& pack);
+// a failed HIP call of a function that returns a status: message into the thread's last error, SRCFD_EHIP out
+#define HIPCHECK(expr)                                                               \
+  do {                                                                               \
+    hipError_t _e = (expr);                                                          \
+    if (_e != hipSuccess) {                                                          \
+      srcfd::set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));    \
+      return SRCFD_EHIP;                                                             \
+    }                                                                                \
+  } while (0)
 
 struct ProfEvent {
   hipEvent_t a, b;
@@ -77,17 +78,17 @@ struct Model {
   // ops[pair_op], ops[pair_op + 1]: two kernel == stride == 2 transposed convolutions (32 -> 16 -> 8 channels) that run as
   // one kernel (kernels.h, PairDesc); -1: none.  Offsets into `pack`.
   int pair_op = -1;
-  size_t pair_wa = 0, pair_ba = 0, pair_wb = 0, pair_bb = 0;
+  PairPack pair;
   // ops[triple_op .. +2]: the same with a 64 -> 32 layer in front (kernels.h, TripleDesc); takes precedence over the pair
   int triple_op = -1;
-  size_t tri_w1 = 0, tri_b1 = 0, tri_w2 = 0, tri_b2 = 0, tri_w3 = 0, tri_b3 = 0;
+  TriplePack tri;
   // ops[tail32_op .. +3]: that chain followed by the network's last layer, a 3x3 SAME conv 8 -> 1 (kernels.h, Tail32Params):
   // one streaming kernel; takes precedence over the triple
   int tail32_op = -1;
   // ops[0..3] = conv2d (1->64, s2) -> conv2d_1 (64->128 on 5x5) -> dense (3200->128) -> latent (128->nl) run as one launch (kernels.h, Enc32Params)
   bool enc32_ok = false;
   size_t enc32_w2 = 0;     // conv2d_1 A fragments in `pack`
-  size_t t32_w1 = 0, t32_b1 = 0, t32_w2 = 0, t32_b2 = 0, t32_w3 = 0, t32_b3 = 0, t32_wc = 0;
+  Tail32Pack t32;
   int num_cus = 256;
   float* d_pack = nullptr;
   // SRCFD_PREC_FP32X3: ops the split-bf16 GEMM takes (kernels_x3.hip): x3_off[i] = offset of op i's three weight planes in pack_x3

@@ -18,191 +18,43 @@ namespace srcfd {
 thread_local std::string g_last_error;
 void set_error(const std::string& m) { g_last_error = m; }
 
-#define HIPCHECK(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) {                                                                         \
-      set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));                          \
-      return SRCFD_EHIP;                                                                            \
-    }                                                                                               \
-  } while (0)
-
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // ---------------------------------------------------------------------------
-// plan
+// plan: which fused kernels the graph qualifies for; their operand layouts are operand_pack.cpp's
 // ---------------------------------------------------------------------------
-static void pack_B(std::vector<float>& pack, Op& op, const std::vector<float>& Bmat /*[K][N]*/, const std::vector<float>& bias_n) {
-  const GemmDesc& d = op.d;
-  while (pack.size() % 64) pack.push_back(0.f);  // 256-byte aligned sub-buffers
-  op.w_off = pack.size();
-  pack.resize(pack.size() + (size_t)std::max(d.K, 1) * d.Npad, 0.f);
-  for (int k = 0; k < d.K; ++k)
-    std::memcpy(&pack[op.w_off + (size_t)k * d.Npad], &Bmat[(size_t)k * d.N], sizeof(float) * d.N);
-  while (pack.size() % 64) pack.push_back(0.f);
-  op.b_off = pack.size();
-  pack.resize(pack.size() + d.Npad, 0.f);
-  std::memcpy(&pack[op.b_off], bias_n.data(), sizeof(float) * d.N);
-}
+static bool is_k2s2(const Layer& L) { return L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2; }
 
-void build_plan(const ModelDesc& desc, std::vector<Op>& ops, std::vector<float>& pack) {
-  ops.clear();
-  pack.clear();
-  for (size_t li = 0; li < desc.layers.size(); ++li) {
-    const Layer& L = desc.layers[li];
-    if (L.kind == SRCFD_LAYER_FLATTEN || L.kind == SRCFD_LAYER_RESHAPE) continue;  // views of NHWC buffers
-    const int IH = L.in_shape[0], IW = L.in_shape[1], OH = L.out_shape[0], OW = L.out_shape[1];
-    GemmDesc d{};
-    d.act = L.act;
-    d.OH = OH; d.OW = OW; d.OC = L.cout; d.CO = L.cout;
-    d.nphx = 1; d.os = 1;
-    d.IH = IH; d.IW = IW; d.CI = L.cin;
-    if (L.kind == SRCFD_LAYER_DENSE) {
-      d.IH = d.IW = 1; d.CI = L.cin; d.OH = d.OW = 1;
-      d.MH = d.MW = 1; d.TY = d.TX = 1;
-      d.K = L.cin; d.N = L.cout; d.Npad = round_up(d.N, 32);
-      Op op; op.d = d; op.layer = (int)li; op.name = L.name;
-      pack_B(pack, op, L.kernel, L.bias);
-      ops.push_back(op);
-    } else if (L.kind == SRCFD_LAYER_CONV2D) {
-      int pt = 0, pl = 0;
-      if (L.same) {
-        int th = std::max((OH - 1) * L.stride + L.kh - IH, 0), tw = std::max((OW - 1) * L.stride + L.kw - IW, 0);
-        pt = th / 2; pl = tw / 2;  // TF SAME: the extra pixel goes after
-      }
-      d.MH = OH; d.MW = OW; d.TY = L.kh; d.TX = L.kw;
-      d.ay = d.ax = L.stride; d.by = d.bx = 1; d.cy = -pt; d.cx = -pl;
-      d.K = L.kh * L.kw * L.cin; d.N = L.cout; d.Npad = round_up(d.N, 32);
-      Op op; op.d = d; op.layer = (int)li; op.name = L.name;
-      pack_B(pack, op, L.kernel, L.bias);  // (kh,kw,Cin,Cout) is already [K][N]
-      ops.push_back(op);
-    } else {  // Conv2DTranspose, VALID, kernel (kh,kw,Cout,Cin)
-      const int s = L.stride;
-      auto W = [&](int a, int b, int co, int ci) { return L.kernel[(((size_t)a * L.kw + b) * L.cout + co) * L.cin + ci]; };
-      if (L.kh == s && L.kw == s) {
-        d.MH = IH; d.MW = IW; d.TY = d.TX = 1;
-        d.ay = d.ax = 1; d.by = d.bx = 0; d.cy = d.cx = 0;
-        d.K = L.cin; d.N = s * s * L.cout; d.Npad = round_up(d.N, 32);
-        d.nphx = s; d.os = s;
-        std::vector<float> B((size_t)d.K * d.N), bn(d.N);
-        for (int ci = 0; ci < L.cin; ++ci)
-          for (int py = 0; py < s; ++py)
-            for (int px = 0; px < s; ++px)
-              for (int co = 0; co < L.cout; ++co) B[(size_t)ci * d.N + (py * s + px) * L.cout + co] = W(py, px, co, ci);
-        for (int n = 0; n < d.N; ++n) bn[n] = L.bias[n % L.cout];
-        Op op; op.d = d; op.layer = (int)li; op.name = L.name;
-        pack_B(pack, op, B, bn);
-        ops.push_back(op);
-      } else {
-        for (int py = 0; py < s; ++py)
-          for (int px = 0; px < s; ++px) {
-            GemmDesc p = d;
-            p.TY = py < L.kh ? (L.kh - py + s - 1) / s : 0;
-            p.TX = px < L.kw ? (L.kw - px + s - 1) / s : 0;
-            p.MH = py < OH ? (OH - py + s - 1) / s : 0;
-            p.MW = px < OW ? (OW - px + s - 1) / s : 0;
-            if (p.MH == 0 || p.MW == 0) continue;
-            p.ay = p.ax = 1; p.by = p.bx = -1; p.cy = p.cx = 0;
-            p.K = p.TY * p.TX * L.cin; p.N = L.cout; p.Npad = round_up(p.N, 32);
-            p.os = s; p.oy0 = py; p.ox0 = px;
-            std::vector<float> B((size_t)std::max(p.K, 1) * p.N, 0.f);
-            for (int ty = 0; ty < p.TY; ++ty)
-              for (int tx = 0; tx < p.TX; ++tx)
-                for (int ci = 0; ci < L.cin; ++ci)
-                  for (int co = 0; co < L.cout; ++co)
-                    B[((size_t)(ty * p.TX + tx) * L.cin + ci) * p.N + co] = W(py + s * ty, px + s * tx, co, ci);
-            Op op; op.d = p; op.layer = (int)li;
-            op.name = L.name + ".ph" + std::to_string(py) + std::to_string(px);
-            pack_B(pack, op, B, L.bias);
-            ops.push_back(op);
-          }
-      }
-    }
-  }
-}
-
-// Operands of the fused ConvT pair (kernels_fp32.hip, convt_pair_f32), appended to `pack`:
-//   wa[(T*16 + s)*64 + lane]: first layer, row i = lane & 31 of tile T -> tap 2T + (i >> 4), channel i & 15; k = 16 (lane >> 5) + s
-//   wb[u*64 + lane]:          second layer, row j = lane & 31 -> tap j >> 3, channel j & 7; k = (u & 3) + 8 (u >> 2) + 4 (lane >> 5)
-// Conv2DTranspose kernels are (kh, kw, Cout, Cin).
+// Operands of the fused ConvT pair (kernels_fp32.hip, convt_pair_f32), appended to `pack`
 static void plan_convt_pair(Model& m) {
   m.pair_op = -1;
   for (size_t i = 0; i + 1 < m.ops.size(); ++i) {
     const Op &a = m.ops[i], &b = m.ops[i + 1];
     const Layer &La = m.desc.layers[a.layer], &Lb = m.desc.layers[b.layer];
-    auto is_k2s2 = [](const Layer& L) { return L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2; };
     if (a.layer + 1 != b.layer || !is_k2s2(La) || !is_k2s2(Lb)) continue;
     if (a.d.nphx != 2 || b.d.nphx != 2) continue;  // one op per layer (the merged-phase form)
     if (La.cin != 32 || La.cout != 16 || Lb.cin != 16 || Lb.cout != 8) continue;
-    auto& pk = m.pack;
-    auto align = [&]() { while (pk.size() % 64) pk.push_back(0.f); };
-    align(); m.pair_wa = pk.size(); pk.resize(pk.size() + 2 * 16 * 64);
-    for (int T = 0; T < 2; ++T)
-      for (int s = 0; s < 16; ++s)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int row = lane & 31, tap = 2 * T + (row >> 4), ch = row & 15, k = 16 * (lane >> 5) + s;
-          pk[m.pair_wa + (size_t)(T * 16 + s) * 64 + lane] = La.kernel[((size_t)tap * 16 + ch) * 32 + k];
-        }
-    align(); m.pair_ba = pk.size(); pk.insert(pk.end(), La.bias.begin(), La.bias.end());
-    align(); m.pair_wb = pk.size(); pk.resize(pk.size() + 8 * 64);
-    for (int u = 0; u < 8; ++u)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int row = lane & 31, tap = row >> 3, ch = row & 7, k = (u & 3) + 8 * (u >> 2) + 4 * (lane >> 5);
-        pk[m.pair_wb + (size_t)u * 64 + lane] = Lb.kernel[((size_t)tap * 8 + ch) * 16 + k];
-      }
-    align(); m.pair_bb = pk.size(); pk.insert(pk.end(), Lb.bias.begin(), Lb.bias.end());
-    align();
+    m.pair = pack_convt_pair(m.pack, La, Lb);
     m.pair_op = (int)i;
     return;
   }
 }
 
-// Operands of the three-layer chain (convt_triple_f32): w1[(T*32 + s)*64 + lane]: tap T, channel lane & 31, k = 32 (lane >> 5) + s;
-// w2[(T*16 + u)*64 + lane]: tap 2T + (row >> 4), channel row & 15, k = (u & 3) + 8 (u >> 2) + 4 (lane >> 5); w3 as the pair's wb.
+// Operands of the three-layer chain (convt_triple_f32)
 static void plan_convt_triple(Model& m) {
   m.triple_op = -1;
-  auto is_k2s2 = [](const Layer& L) { return L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2; };
   for (size_t i = 0; i + 2 < m.ops.size(); ++i) {
     const Op &a = m.ops[i], &b = m.ops[i + 1], &c = m.ops[i + 2];
     if (a.layer + 1 != b.layer || b.layer + 1 != c.layer) continue;
     const Layer &L1 = m.desc.layers[a.layer], &L2 = m.desc.layers[b.layer], &L3 = m.desc.layers[c.layer];
     if (!is_k2s2(L1) || !is_k2s2(L2) || !is_k2s2(L3) || a.d.nphx != 2 || b.d.nphx != 2 || c.d.nphx != 2) continue;
     if (L1.cin != 64 || L1.cout != 32 || L2.cin != 32 || L2.cout != 16 || L3.cin != 16 || L3.cout != 8) continue;
-    auto& pk = m.pack;
-    auto align = [&]() { while (pk.size() % 64) pk.push_back(0.f); };
-    align(); m.tri_w1 = pk.size(); pk.resize(pk.size() + 4 * 32 * 64);
-    for (int T = 0; T < 4; ++T)
-      for (int s = 0; s < 32; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-          pk[m.tri_w1 + (size_t)(T * 32 + s) * 64 + lane] = L1.kernel[((size_t)T * 32 + (lane & 31)) * 64 + 32 * (lane >> 5) + s];
-    align(); m.tri_b1 = pk.size(); pk.insert(pk.end(), L1.bias.begin(), L1.bias.end());
-    align(); m.tri_w2 = pk.size(); pk.resize(pk.size() + 2 * 16 * 64);
-    for (int T = 0; T < 2; ++T)
-      for (int u = 0; u < 16; ++u)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int row = lane & 31, tap = 2 * T + (row >> 4), ch = row & 15, k = (u & 3) + 8 * (u >> 2) + 4 * (lane >> 5);
-          pk[m.tri_w2 + (size_t)(T * 16 + u) * 64 + lane] = L2.kernel[((size_t)tap * 16 + ch) * 32 + k];
-        }
-    align(); m.tri_b2 = pk.size(); pk.insert(pk.end(), L2.bias.begin(), L2.bias.end());
-    align(); m.tri_w3 = pk.size(); pk.resize(pk.size() + 8 * 64);
-    for (int u = 0; u < 8; ++u)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int row = lane & 31, tap = row >> 3, ch = row & 7, k = (u & 3) + 8 * (u >> 2) + 4 * (lane >> 5);
-        pk[m.tri_w3 + (size_t)u * 64 + lane] = L3.kernel[((size_t)tap * 8 + ch) * 16 + k];
-      }
-    align(); m.tri_b3 = pk.size(); pk.insert(pk.end(), L3.bias.begin(), L3.bias.end());
-    align();
+    m.tri = pack_convt_triple(m.pack, L1, L2, L3);
     m.triple_op = (int)i;
     return;
   }
 }
 
 // Operands of the fused f32 tail (kernels_tail32.hip): the ConvT 64 -> 32 -> 16 -> 8 chain + the 3x3 SAME conv 8 -> 1 that
-// ends the network, v_mfma_f32_16x16x4_f32 fragments (lane = (m = lane & 15, kg = lane >> 4)):
-//   w1[((tap1*2 + t)*16 + s)*64 + lane] = W1[tap1][co 16t + m][ci 16kg + s]
-//   w2[(tap2*8 + 4t + i)*64 + lane]     = W2[tap2][co m][ci 16t + 4kg + i]      (k order = the first layer's accumulator order)
-//   w3[(u*4 + i)*64 + lane]             = W3[tap3 2u + (m >> 3)][co m & 7][ci 4kg + i]
-// Conv2DTranspose kernels are (kh, kw, Cout, Cin); the Conv2D kernel (3, 3, 8, 1) is already (ty, tx, ci).
+// ends the network
 static void plan_tail32(Model& m) {
   m.tail32_op = -1;
   if (m.triple_op < 0 || (size_t)m.triple_op + 4 != m.ops.size()) return;
@@ -214,41 +66,12 @@ static void plan_tail32(Model& m) {
   if (LO.kind != SRCFD_LAYER_CONV2D || LO.kh != 3 || LO.kw != 3 || LO.stride != 1 || !LO.same || LO.cin != 8 || LO.cout != 1) return;
   if (m.ops[i].d.MW > 50) return;  // the LDS ring holds rows of up to 400 pixels
   if (L1.act != SRCFD_ACT_SWISH || L2.act != SRCFD_ACT_SWISH || L3.act != SRCFD_ACT_SWISH || LO.act != SRCFD_ACT_LINEAR) return;
-  const double LOG2E = 1.4426950408889634;   // swish layers produce log2(e) x (kernels_tail32.hip, swish_l2e)
-  auto& pk = m.pack;
-  auto align = [&]() { while (pk.size() % 64) pk.push_back(0.f); };
-  align(); m.t32_w1 = pk.size(); pk.resize(pk.size() + 4 * 2 * 16 * 64);
-  for (int tap = 0; tap < 4; ++tap)
-    for (int t = 0; t < 2; ++t)
-      for (int s = 0; s < 16; ++s)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int mm = lane & 15, kg = lane >> 4;
-          pk[m.t32_w1 + (size_t)((tap * 2 + t) * 16 + s) * 64 + lane] = (float)(L1.kernel[((size_t)tap * 32 + 16 * t + mm) * 64 + 16 * kg + s] * LOG2E);
-        }
-  align(); m.t32_b1 = pk.size(); for (float v : L1.bias) pk.push_back((float)(v * LOG2E));
-  align(); m.t32_w2 = pk.size(); pk.resize(pk.size() + 4 * 8 * 64);
-  for (int tap = 0; tap < 4; ++tap)
-    for (int t = 0; t < 2; ++t)
-      for (int ii = 0; ii < 4; ++ii)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int mm = lane & 15, kg = lane >> 4;
-          pk[m.t32_w2 + (size_t)(tap * 8 + 4 * t + ii) * 64 + lane] = L2.kernel[((size_t)tap * 16 + mm) * 32 + 16 * t + 4 * kg + ii];
-        }
-  align(); m.t32_b2 = pk.size(); for (float v : L2.bias) pk.push_back((float)(v * LOG2E));
-  align(); m.t32_w3 = pk.size(); pk.resize(pk.size() + 2 * 4 * 64);
-  for (int u = 0; u < 2; ++u)
-    for (int ii = 0; ii < 4; ++ii)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int mm = lane & 15, kg = lane >> 4;
-        pk[m.t32_w3 + (size_t)(u * 4 + ii) * 64 + lane] = L3.kernel[((size_t)(2 * u + (mm >> 3)) * 8 + (mm & 7)) * 16 + 4 * kg + ii];
-      }
-  align(); m.t32_b3 = pk.size(); for (float v : L3.bias) pk.push_back((float)(v * LOG2E));
-  align(); m.t32_wc = pk.size(); for (float v : LO.kernel) pk.push_back((float)(v / LOG2E)); pk.push_back(LO.bias[0]);
-  align();
+  m.t32 = pack_tail32(m.pack, L1, L2, L3, LO);
   m.tail32_op = (int)i;
 }
 
-// SRCFD_PREC_FP32X3: the ops gemm_x3 takes get their weights split into three bf16 planes (kernels_x3.hip).
+// SRCFD_PREC_FP32X3: the ops gemm_x3 takes get their weights split into three bf16 planes (kernels_x3.hip), and the streaming
+// tail's first two layers likewise (kernels_tail32.hip, X3)
 static void plan_x3(Model& m) {
   m.x3_off.assign(m.ops.size(), -1);
   m.pack_x3.clear();
@@ -256,71 +79,18 @@ static void plan_x3(Model& m) {
     GemmDesc d = m.ops[i].d;
     d.M = 0;
     if (!gemm_x3_qualifies(d)) continue;
-    while (m.pack_x3.size() % 64) m.pack_x3.push_back(0);
+    align64(m.pack_x3);
     m.x3_off[i] = (int64_t)m.pack_x3.size();
     m.pack_x3.resize(m.pack_x3.size() + (size_t)3 * d.N * gemm_x3_kpad(d));
     gemm_x3_split_weights(d, m.pack.data() + m.ops[i].w_off, m.pack_x3.data() + m.x3_off[i]);
   }
-  // the streaming tail's first layer (kernels_tail32.hip, X3): w1 x log2(e), rounded to f32 as in plan_tail32, then split
-  //   w1x[((((ty1*2 + tx1)*2 + t)*2 + c)*3 + plane)*64 + lane][j] = plane(W1[2 ty1 + tx1][co 16t + m][ci 32c + 8 kg + j]),  lane = (m, kg)
   m.t32_w1x = m.t32_w2x = -1;
-  auto split3 = [](float w, uint16_t (&o)[3]) {
-    uint32_t b0, b1, b2;
-    std::memcpy(&b0, &w, 4); b0 &= 0xffff0000u;
-    float hi; std::memcpy(&hi, &b0, 4);
-    const float r1 = w - hi;
-    std::memcpy(&b1, &r1, 4); b1 &= 0xffff0000u;
-    float mid; std::memcpy(&mid, &b1, 4);
-    const float r2 = r1 - mid;
-    std::memcpy(&b2, &r2, 4);
-    o[0] = (uint16_t)(b0 >> 16); o[1] = (uint16_t)(b1 >> 16); o[2] = (uint16_t)(b2 >> 16);
-  };
-  if (m.tail32_op >= 0) {
-    const Layer& L2 = m.desc.layers[m.ops[m.tail32_op + 1].layer];
-    while (m.pack_x3.size() % 64) m.pack_x3.push_back(0);
-    m.t32_w2x = (int64_t)m.pack_x3.size();
-    m.pack_x3.resize(m.pack_x3.size() + (size_t)4 * 3 * 64 * 8);
-    for (int tap = 0; tap < 4; ++tap)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int mm = lane & 15, kg = lane >> 4, ci = j < 4 ? 4 * kg + j : 16 + 4 * kg + (j - 4);
-          uint16_t o[3];
-          split3(L2.kernel[((size_t)tap * 16 + mm) * 32 + ci], o);
-          for (int pl = 0; pl < 3; ++pl) m.pack_x3[m.t32_w2x + ((size_t)(tap * 3 + pl) * 64 + lane) * 8 + j] = o[pl];
-        }
-    const Layer& L1 = m.desc.layers[m.ops[m.tail32_op].layer];
-    const double LOG2E = 1.4426950408889634;
-    while (m.pack_x3.size() % 64) m.pack_x3.push_back(0);
-    m.t32_w1x = (int64_t)m.pack_x3.size();
-    m.pack_x3.resize(m.pack_x3.size() + (size_t)2 * 2 * 2 * 2 * 3 * 64 * 8);
-    uint16_t* out = m.pack_x3.data() + m.t32_w1x;
-    for (int ty1 = 0; ty1 < 2; ++ty1)
-      for (int tx1 = 0; tx1 < 2; ++tx1)
-        for (int t = 0; t < 2; ++t)
-          for (int c = 0; c < 2; ++c)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int j = 0; j < 8; ++j) {
-                const int mm = lane & 15, kg = lane >> 4, tap = 2 * ty1 + tx1;
-                const float w = (float)(L1.kernel[((size_t)tap * 32 + 16 * t + mm) * 64 + 32 * c + 8 * kg + j] * LOG2E);
-                uint32_t b0, b1, b2;
-                std::memcpy(&b0, &w, 4); b0 &= 0xffff0000u;
-                float hi; std::memcpy(&hi, &b0, 4);
-                const float r1 = w - hi;
-                std::memcpy(&b1, &r1, 4); b1 &= 0xffff0000u;
-                float mid; std::memcpy(&mid, &b1, 4);
-                const float r2 = r1 - mid;
-                std::memcpy(&b2, &r2, 4);
-                const size_t frag = (size_t)((((ty1 * 2 + tx1) * 2 + t) * 2 + c) * 3);
-                out[((frag + 0) * 64 + lane) * 8 + j] = (uint16_t)(b0 >> 16);
-                out[((frag + 1) * 64 + lane) * 8 + j] = (uint16_t)(b1 >> 16);
-                out[((frag + 2) * 64 + lane) * 8 + j] = (uint16_t)(b2 >> 16);
-              }
-  }
+  if (m.tail32_op >= 0)
+    pack_tail32_x3(m.pack_x3, m.desc.layers[m.ops[m.tail32_op].layer], m.desc.layers[m.ops[m.tail32_op + 1].layer], m.t32_w1x, m.t32_w2x);
 }
 
 // enc32 (kernels_enc32.hip): the encoder's four compute layers as one launch.  conv2d_1's weights are re-ordered into
-// v_mfma_f32_16x16x4_f32 A fragments: frag[((w*36 + tap*4 + q)*64 + lane)*4 + j] = W[tap][ci = 16 q + 4 (lane / 16) + j][co = 16 w + lane % 16]
-// (Keras Conv2D kernel (kh, kw, cin, cout)); the other three layers use their ordinary B[K][Npad] operands.
+// v_mfma_f32_16x16x4_f32 A fragments; the other three layers use their ordinary B[K][Npad] operands.
 static void plan_enc32(Model& m) {
   m.enc32_ok = false;
   if (m.ops.size() < 4 || m.desc.in_shape[0] != 10 || m.desc.in_shape[1] != 10 || m.desc.in_shape[2] != 1) return;
@@ -334,19 +104,7 @@ static void plan_enc32(Model& m) {
   if (de.MH != 1 || de.MW != 1 || de.K != 3200 || de.N != 128 || de.Npad != 128) return;
   if (la.MH != 1 || la.MW != 1 || la.K != 128 || la.N > 128 || la.OC != la.N) return;
   if (!act_ok(c1.act) || !act_ok(c2.act) || !act_ok(de.act) || !act_ok(la.act)) return;
-  auto& pk = m.pack;
-  while (pk.size() % 64) pk.push_back(0.f);
-  m.enc32_w2 = pk.size();
-  pk.resize(pk.size() + (size_t)8 * 36 * 64 * 4);
-  for (int w = 0; w < 8; ++w)
-    for (int tap = 0; tap < 9; ++tap)
-      for (int q = 0; q < 4; ++q)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 4; ++j) {
-            const int ci = 16 * q + 4 * (lane >> 4) + j, co = 16 * w + (lane & 15);
-            pk[m.enc32_w2 + ((size_t)((w * 36 + tap * 4 + q) * 64 + lane)) * 4 + j] = L1.kernel[((size_t)tap * 64 + ci) * 128 + co];
-          }
-  while (pk.size() % 64) pk.push_back(0.f);
+  m.enc32_w2 = pack_enc32(m.pack, L1);
   m.enc32_ok = true;
 }
 
@@ -546,8 +304,8 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
     if (!naive && !tail32_disabled() && (int)i == tail32_op) {  // ConvT#2 -> #3 -> #4 -> output conv + finalize: one streaming kernel
       Tail32Params tp;
       tp.in = X; tp.out = y_dev; tp.n = n; tp.H = d.MH; tp.W = d.MW;
-      tp.w1f = d_pack + t32_w1; tp.b1 = d_pack + t32_b1; tp.w2f = d_pack + t32_w2; tp.b2 = d_pack + t32_b2;
-      tp.w3f = d_pack + t32_w3; tp.b3 = d_pack + t32_b3; tp.wc = d_pack + t32_wc;
+      tp.w1f = d_pack + t32.w1; tp.b1 = d_pack + t32.b1; tp.w2f = d_pack + t32.w2; tp.b2 = d_pack + t32.b2;
+      tp.w3f = d_pack + t32.w3; tp.b3 = d_pack + t32.b3; tp.wc = d_pack + t32.wc;
       tp.aff_out = aff_out; tp.nan_guard = flags & SRCFD_FLAG_NAN_GUARD; tp.nonfinite = nonfinite; tp.out_dtype = out_dtype;
       tp.seg = tail32_segments(n, d.MH, num_cus);
       if (x3 && d_pack_x3 && t32_w1x >= 0 && t32_w2x >= 0 && n >= 64) {   // SRCFD_PREC_FP32X3: the first two layers on the bf16 matrix cores
@@ -567,8 +325,8 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
       td.n = n; td.H = d.MH; td.W = d.MW; td.act1 = d.act; td.act2 = ops[i + 1].d.act; td.act3 = ops[i + 2].d.act;
       const std::string nm = op.name + "+" + ops[i + 1].name + "+" + ops[i + 2].name;
       rc = launch(nm.c_str(), s, [&] {
-        return launch_convt_triple_f32(td, X, d_pack + tri_w1, d_pack + tri_b1, d_pack + tri_w2, d_pack + tri_b2, d_pack + tri_w3,
-                                       d_pack + tri_b3, Y, s);
+        return launch_convt_triple_f32(td, X, d_pack + tri.w1, d_pack + tri.b1, d_pack + tri.w2, d_pack + tri.b2, d_pack + tri.w3,
+                                       d_pack + tri.b3, Y, s);
       });
       if (rc) return rc;
       prev_layer = ops[i + 2].layer;
@@ -580,7 +338,7 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
       pd.n = n; pd.H = d.MH; pd.W = d.MW; pd.act_a = d.act; pd.act_b = ops[i + 1].d.act;
       const std::string nm = op.name + "+" + ops[i + 1].name;
       rc = launch(nm.c_str(), s, [&] {
-        return launch_convt_pair_f32(pd, X, d_pack + pair_wa, d_pack + pair_ba, d_pack + pair_wb, d_pack + pair_bb, Y, s);
+        return launch_convt_pair_f32(pd, X, d_pack + pair.wa, d_pack + pair.ba, d_pack + pair.wb, d_pack + pair.bb, Y, s);
       });
       if (rc) return rc;
       prev_layer = ops[i + 1].layer;  // the pair's output sits where the first layer's would: the next layer toggles once

@@ -504,15 +504,6 @@ bool fine_problem_ok(const srcfd_coarse_problem* pb) {
 }
 }  // namespace srcfd
 
-#define HIPCHECK(expr)                                                               \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));           \
-      return SRCFD_EHIP;                                                             \
-    }                                                                                \
-  } while (0)
-
 extern "C" {
 
 int srcfd_fine_solver_create(const srcfd_coarse_problem* problem, int device, srcfd_fine_solver** out) {

@@ -17,41 +17,6 @@
 
 namespace srcfd {
 
-#define HIPCHECK(expr)                                                               \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));           \
-      return SRCFD_EHIP;                                                             \
-    }                                                                                \
-  } while (0)
-
-static const double LOG2E = 1.4426950408889634;
-
-static uint16_t to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                           // round to nearest even
-  return (uint16_t)(u >> 16);
-}
-static uint16_t to_f16(float f) {
-  _Float16 hv = (_Float16)f;
-  uint16_t r;
-  std::memcpy(&r, &hv, 2);
-  return r;
-}
-static uint16_t to16(float f, bool f16) { return f16 ? to_f16(f) : to_bf16(f); }
-
-struct Op16 {
-  GemmDesc d;
-  size_t w_off = 0;  // elements into Pack16::d_w
-  size_t b_off = 0;  // floats into FusedState::d_f32
-  int Kpad = 0;
-  std::string name;
-  int layer = 0;
-};
-
 struct Pack16 {  // one per operand type (bf16, f16)
   uint16_t* d_w = nullptr;
   void* d_consts = nullptr;
@@ -66,11 +31,7 @@ struct Pack16 {  // one per operand type (bf16, f16)
   bool built = false;
 };
 
-struct FusedState {
-  std::vector<int> cl;  // indices of the 11 compute layers in ModelDesc::layers
-  std::vector<Op16> ops;
-  std::vector<float> f32;  // conv1 weights [9][64], conv1 bias [64], per-op biases
-  size_t c1w_off = 0, c1b_off = 0;
+struct FusedState : Fused32Pack {   // host side: operand_pack.h
   float* d_f32 = nullptr;
   Pack16 packs[2];
   uint16_t* act[2] = {nullptr, nullptr};
@@ -82,60 +43,20 @@ struct FusedState {
   bool enc_ok = false;     // the encoder has the shape enc16 is written for
 };
 
-static double scale_in(const ModelDesc& md, const std::vector<int>& cl, int i) {
-  return (i > 0 && md.layers[cl[i - 1]].act == SRCFD_ACT_SWISH) ? 1.0 / LOG2E : 1.0;
-}
-static double scale_out(const ModelDesc& md, const std::vector<int>& cl, int i) {
-  return md.layers[cl[i]].act == SRCFD_ACT_SWISH ? LOG2E : 1.0;
-}
-static double scale_w(const ModelDesc& md, const std::vector<int>& cl, int i) {
-  double si = scale_in(md, cl, i), so = scale_out(md, cl, i);
-  return (si != 1.0 && so != 1.0) ? 1.0 : si * so;  // swish -> swish: the factors cancel exactly
-}
-
 int fused_init(Model& m) {
   FusedState* fs = new FusedState();
   m.fused = fs;
-  const ModelDesc& md = m.desc;
-  for (size_t i = 0; i < md.layers.size(); ++i)
-    if (md.layers[i].kind != SRCFD_LAYER_FLATTEN && md.layers[i].kind != SRCFD_LAYER_RESHAPE) fs->cl.push_back((int)i);
   hipDeviceProp_t prop;
   HIPCHECK(hipGetDeviceProperties(&prop, m.device));
   fs->num_cus = prop.multiProcessorCount;
-
-  // conv1 (VALU kernel): f32 weights, scaled
-  {
-    const Layer& L = md.layers[fs->cl[0]];
-    double sw = scale_w(md, fs->cl, 0), so = scale_out(md, fs->cl, 0);
-    fs->c1w_off = fs->f32.size();
-    for (float v : L.kernel) fs->f32.push_back((float)(v * sw));
-    fs->c1b_off = fs->f32.size();
-    for (float v : L.bias) fs->f32.push_back((float)(v * so));
-  }
-  // GEMM ops: compute layers 1..6 (conv2d_1, dense, latent_vector, dense_1, conv2d_transpose, conv2d_transpose_1)
-  for (const Op& op : m.ops) {
-    int ci = -1;
-    for (size_t k = 0; k < fs->cl.size(); ++k) if (fs->cl[k] == op.layer) ci = (int)k;
-    if (ci < 1 || ci > 6) continue;
-    Op16 o;
-    o.d = op.d;
-    o.name = op.name;
-    o.layer = ci;
-    if (ci == 3) { o.d.N = 64; o.d.CO = 64; o.d.OC = 64; }   // latent 50 -> 64 zero-padded channels
-    if (ci == 4) { o.d.CI = 64; o.d.K = 64; }                // dense_1 reads the padded latent
-    o.d.Npad = (o.d.N + 63) / 64 * 64;
-    o.Kpad = (o.d.K + 63) / 64 * 64;
-    if (o.d.CI % 64 != 0 || o.d.K % 64 != 0 || o.d.N % 4 != 0 || o.d.CO % 4 != 0) { set_error("fused path: unsupported channel count in " + op.name); return SRCFD_EINVAL; }
-    const double so = scale_out(md, fs->cl, ci);
-    while (fs->f32.size() % 4) fs->f32.push_back(0.f);
-    o.b_off = fs->f32.size();
-    for (int n = 0; n < o.d.Npad; ++n) fs->f32.push_back(n < op.d.N ? (float)(m.pack[op.b_off + n] * so) : 0.f);
-    fs->ops.push_back(o);
-  }
+  // conv1's f32 weights and the GEMM ops of compute layers 1..6 (conv2d_1, dense, latent_vector, dense_1, conv2d_transpose, conv2d_transpose_1)
+  pack_fused_f32(m.desc, m.ops, m.pack, *fs);
+  for (const Op16& o : fs->ops)
+    if (o.d.CI % 64 != 0 || o.d.K % 64 != 0 || o.d.N % 4 != 0 || o.d.CO % 4 != 0) { set_error("fused path: unsupported channel count in " + o.name); return SRCFD_EINVAL; }
   if (fs->ops.size() != 9) { set_error("fused path: unexpected plan shape"); return SRCFD_EINVAL; }
   {  // enc16 is written for encoder_10 exactly: 3x3 s1 pad-1 conv 64->128 on 5x5, dense 3200->128, latent 128->64 (padded)
     const GemmDesc& c2 = fs->ops[0].d; const GemmDesc& de = fs->ops[1].d; const GemmDesc& la = fs->ops[2].d;
-    const Layer& l0 = md.layers[fs->cl[0]];
+    const Layer& l0 = m.desc.layers[fs->cl[0]];
     fs->enc_ok = fs->ops[0].layer == 1 && fs->ops[1].layer == 2 && fs->ops[2].layer == 3 && l0.act == SRCFD_ACT_SWISH &&
                  l0.kernel.size() == 9 * 64 && c2.act == SRCFD_ACT_SWISH &&
                  c2.TY == 3 && c2.TX == 3 && c2.CI == 64 && c2.N == 128 && c2.IH == 5 && c2.IW == 5 && c2.MH == 5 && c2.MW == 5 && c2.ay == 1 &&
@@ -148,175 +69,30 @@ int fused_init(Model& m) {
   return SRCFD_OK;
 }
 
+template <class T, class D> static int upload(const std::vector<T>& v, D** d) {
+  if (v.empty()) return SRCFD_OK;
+  HIPCHECK(hipMalloc(d, v.size() * sizeof(T)));
+  HIPCHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return SRCFD_OK;
+}
+
+// the 16-bit operands of one type (operand_pack.cpp, pack_fused16), uploaded
 static int build_pack(Model& m, FusedState* fs, bool f16) {
   Pack16& P = fs->packs[f16 ? 1 : 0];
   if (P.built) return SRCFD_OK;
-  const ModelDesc& md = m.desc;
-  // ---- GEMM weights, transposed: Wt[Npad][Kpad] ----
-  std::vector<uint16_t> w;
-  size_t oi = 0;
-  for (const Op& op : m.ops) {
-    int ci = -1;
-    for (size_t k = 0; k < fs->cl.size(); ++k) if (fs->cl[k] == op.layer) ci = (int)k;
-    if (ci < 1 || ci > 6) continue;
-    Op16& o = fs->ops[oi++];
-    const double sw = scale_w(md, fs->cl, ci);
-    while (w.size() % 8) w.push_back(0);
-    o.w_off = w.size();
-    w.resize(w.size() + (size_t)o.d.Npad * o.Kpad, 0);
-    for (int n = 0; n < op.d.N; ++n)
-      for (int k = 0; k < op.d.K; ++k)
-        w[o.w_off + (size_t)n * o.Kpad + k] = to16((float)(m.pack[op.w_off + (size_t)k * op.d.Npad + n] * sw), f16);
-  }
-  HIPCHECK(hipMalloc(&P.d_w, w.size() * sizeof(uint16_t)));
-  HIPCHECK(hipMemcpy(P.d_w, w.data(), w.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  if (fs->enc_ok) {
-    // ---- enc16 operands: the same 16-bit values, re-ordered so that one lane's MFMA A operand is one 16-byte load ----
-    const uint16_t* W2 = w.data() + fs->ops[0].w_off;   // [128][576]
-    const uint16_t* WD = w.data() + fs->ops[1].w_off;   // [128][3200]
-    const uint16_t* WL = w.data() + fs->ops[2].w_off;   // [64][128]
-    std::vector<uint16_t> ef;
-    ef.reserve((size_t)(4 * 36 + 8 * 100 + 4 * 4) * 512);
-    for (int mt = 0; mt < 4; ++mt)         // 32x32x16: lane l = row l % 32, k = 16 ks + 8 (l / 32) + j
-      for (int ks = 0; ks < 36; ++ks)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) ef.push_back(W2[(size_t)(mt * 32 + (l & 31)) * 576 + ks * 16 + (l >> 5) * 8 + j]);
-    P.enc_wd_off = ef.size() * 2;
-    for (int ft = 0; ft < 8; ++ft)         // 16x16x32: lane l = row l % 16, k = 32 ks + 8 (l / 16) + j
-      for (int ks = 0; ks < 100; ++ks)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) ef.push_back(WD[(size_t)(ft * 16 + (l & 15)) * 3200 + ks * 32 + (l >> 4) * 8 + j]);
-    P.enc_wl_off = ef.size() * 2;
-    for (int ft = 0; ft < 4; ++ft)
-      for (int ks = 0; ks < 4; ++ks)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) ef.push_back(WL[(size_t)(ft * 16 + (l & 15)) * 128 + ks * 32 + (l >> 4) * 8 + j]);
-    HIPCHECK(hipMalloc(&P.d_encf, ef.size() * sizeof(uint16_t)));
-    HIPCHECK(hipMemcpy(P.d_encf, ef.data(), ef.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    std::vector<float> eb(128);
-    for (int mt = 0; mt < 4; ++mt)
-      for (int hh = 0; hh < 2; ++hh)
-        for (int r = 0; r < 16; ++r) eb[(mt * 2 + hh) * 16 + r] = fs->f32[fs->ops[0].b_off + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hh];
-    HIPCHECK(hipMalloc(&P.d_encb, eb.size() * sizeof(float)));
-    HIPCHECK(hipMemcpy(P.d_encb, eb.data(), eb.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-
-  // ---- tail constants ----
-  const Layer& L2 = md.layers[fs->cl[7]];   // ConvT 64->32, kernel (2,2,32,64)
-  const Layer& L3 = md.layers[fs->cl[8]];   // ConvT 32->16, kernel (2,2,16,32)
-  const Layer& L4 = md.layers[fs->cl[9]];   // ConvT 16->8,  kernel (2,2,8,16)
-  const Layer& LO = md.layers[fs->cl[10]];  // Conv 8->1,    kernel (3,3,8,1)
-  auto rowof = [](int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; };  // 32x32 accumulator row of register r
-  std::vector<uint8_t> cst(TAIL_CONST_BYTES, 0);
-  uint16_t* wc = reinterpret_cast<uint16_t*>(cst.data() + TC_OFF_WC);
-  for (int kk = 0; kk < 10; ++kk)
-    for (int l = 0; l < 64; ++l) {
-      int n = l & 15, kg = l >> 4, oy = n >> 3, ox = n & 7;
-      int wy = 2 * (kk / 5) + (kg & 1), wx = 2 * (kk % 5) + (kg >> 1);
-      int ky = wy - oy, kx = wx - ox;
-      for (int c = 0; c < 8; ++c) {
-        float v = 0.f;
-        if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) v = (float)(LO.kernel[(size_t)(ky * 3 + kx) * 8 + c] / LOG2E);
-        wc[((size_t)kk * 64 + l) * 8 + c] = to16(v, f16);
-      }
-    }
-  uint16_t* w3 = reinterpret_cast<uint16_t*>(cst.data() + TC_OFF_W3);
-  for (int m3 = 0; m3 < 2; ++m3)
-    for (int kk = 0; kk < 2; ++kk)
-      for (int l = 0; l < 64; ++l) {
-        int i = l & 31, hh = l >> 5, tap = 2 * m3 + (i >> 4), co = i & 15;
-        for (int j = 0; j < 8; ++j) {
-          int ci = 16 * kk + 8 * hh + j;
-          w3[(((size_t)m3 * 2 + kk) * 64 + l) * 8 + j] = to16(L3.kernel[((size_t)tap * 16 + co) * 32 + ci], f16);
-        }
-      }
-  uint16_t* w4 = reinterpret_cast<uint16_t*>(cst.data() + TC_OFF_W4);
-  for (int l = 0; l < 64; ++l) {
-    int i = l & 31, hh = l >> 5, tap = i >> 3, co = i & 7;
-    for (int j = 0; j < 8; ++j) {
-      int ci = (j & 3) + 8 * (j >> 2) + 4 * hh;  // k order of an accumulator used as the next B operand
-      w4[(size_t)l * 8 + j] = to16(L4.kernel[((size_t)tap * 8 + co) * 16 + ci], f16);
-    }
-  }
-  float* b2 = reinterpret_cast<float*>(cst.data() + TC_OFF_B2);
-  float* b3 = reinterpret_cast<float*>(cst.data() + TC_OFF_B3);
-  float* b4 = reinterpret_cast<float*>(cst.data() + TC_OFF_B4);
-  for (int hh = 0; hh < 2; ++hh)
-    for (int r = 0; r < 16; ++r) {
-      int row = rowof(r, hh);
-      b2[hh * 16 + r] = (float)(L2.bias[row] * LOG2E);
-      b3[hh * 16 + r] = (float)(L3.bias[row & 15] * LOG2E);
-      b4[hh * 16 + r] = (float)(L4.bias[row & 7] * LOG2E);
-    }
-  *reinterpret_cast<float*>(cst.data() + TC_OFF_BC) = LO.bias[0];
-  HIPCHECK(hipMalloc(&P.d_consts, cst.size()));
-  HIPCHECK(hipMemcpy(P.d_consts, cst.data(), cst.size(), hipMemcpyHostToDevice));
-
-  std::vector<uint16_t> w2((size_t)4 * 4 * 64 * 8);
-  for (int mt = 0; mt < 4; ++mt)
-    for (int kk = 0; kk < 4; ++kk)
-      for (int l = 0; l < 64; ++l) {
-        int co = l & 31, hh = l >> 5;
-        for (int j = 0; j < 8; ++j) {
-          int ci = 16 * kk + 8 * hh + j;
-          w2[(((size_t)mt * 4 + kk) * 64 + l) * 8 + j] = to16(L2.kernel[((size_t)mt * 32 + co) * 64 + ci], f16);
-        }
-      }
-  HIPCHECK(hipMalloc(&P.d_w2f, w2.size() * sizeof(uint16_t)));
-  HIPCHECK(hipMemcpy(P.d_w2f, w2.data(), w2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  // ---- mid16 (ConvT#0 -> ConvT#1) operands ----
-  {
-    const Layer& L0 = md.layers[fs->cl[5]];  // ConvT 256->128 (bias only; weights reuse the per-phase GEMM packing)
-    const Layer& L1 = md.layers[fs->cl[6]];  // ConvT 128->64, kernel (2,2,64,128)
-    std::vector<uint16_t> w1((size_t)8 * 8 * 64 * 8);
-    for (int j8 = 0; j8 < 8; ++j8)
-      for (int st = 0; st < 8; ++st)
-        for (int l = 0; l < 64; ++l) {
-          int i = l & 31, hh = l >> 5, tap = j8 >> 1, co = 32 * (j8 & 1) + i;
-          for (int j = 0; j < 8; ++j) {
-            // k-step st consumes accumulator tile st>>1, registers 8*(st&1)+j: channel of that register
-            int ci = 32 * (st >> 1) + 16 * (st & 1) + 8 * (j >> 2) + 4 * hh + (j & 3);
-            w1[(((size_t)j8 * 8 + st) * 64 + l) * 8 + j] = to16(L1.kernel[((size_t)tap * 64 + co) * 128 + ci], f16);
-          }
-        }
-    // ConvT#0 weights, stage by stage, in the order the kernel's LDS tile holds them: stage (chunk c, tap t) of a phase = [128 rows][64 k]
-    // = 1024 sixteen-byte pieces, piece row * 8 + slot holding k-piece slot ^ ((row >> 1) & 7) (the bank swizzle of the fragment reads).
-    // A tile is then 16 KB of CONSECUTIVE memory.  Read from the GEMM layout Wt[128][Kpad] instead, its 128 row segments lie Kpad * 2 =
-    // 512 / 1024 / 2048 bytes apart -- powers of two: every workgroup of a phase asks the same one or two L2 channels for the same tile
-    // at the same time (round 3: the tile loads' cost did not hide behind anything, whatever the prefetch depth).
-    {
-      std::vector<uint16_t> wt;
-      int ph = 0;
-      for (const Op16& o : fs->ops) {
-        if (o.layer != 5 || ph >= 4) continue;
-        const int NT = o.d.K / 256;
-        P.w0t_off[ph++] = wt.size();
-        const uint16_t* W = w.data() + o.w_off;
-        for (int st = 0; st < 4 * NT; ++st) {
-          const int c = st / NT, t = st - c * NT;
-          for (int i = 0; i < 1024; ++i) {
-            const int row = i >> 3, kc = (i & 7) ^ ((row >> 1) & 7);
-            for (int j = 0; j < 8; ++j) wt.push_back(W[(size_t)row * o.Kpad + t * 256 + c * 64 + kc * 8 + j]);
-          }
-        }
-      }
-      if (!wt.empty()) {
-        HIPCHECK(hipMalloc(&P.d_w0t, wt.size() * sizeof(uint16_t)));
-        HIPCHECK(hipMemcpy(P.d_w0t, wt.data(), wt.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      }
-    }
-    HIPCHECK(hipMalloc(&P.d_w1f, w1.size() * sizeof(uint16_t)));
-    HIPCHECK(hipMemcpy(P.d_w1f, w1.data(), w1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    std::vector<float> mb(128 + 64);
-    for (int mt = 0; mt < 4; ++mt)
-      for (int hh = 0; hh < 2; ++hh)
-        for (int r = 0; r < 16; ++r) mb[(mt * 2 + hh) * 16 + r] = (float)(L0.bias[32 * mt + rowof(r, hh)] * LOG2E);
-    for (int jj = 0; jj < 2; ++jj)
-      for (int hh = 0; hh < 2; ++hh)
-        for (int r = 0; r < 16; ++r) mb[128 + (jj * 2 + hh) * 16 + r] = (float)(L1.bias[32 * jj + rowof(r, hh)] * LOG2E);
-    HIPCHECK(hipMalloc(&P.d_midb, mb.size() * sizeof(float)));
-    HIPCHECK(hipMemcpy(P.d_midb, mb.data(), mb.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  Pack16Host h;
+  pack_fused16(m.desc, m.ops, m.pack, *fs, fs->enc_ok, f16, h);
+  P.enc_wd_off = h.enc_wd_off; P.enc_wl_off = h.enc_wl_off;
+  std::copy(h.w0t_off, h.w0t_off + 4, P.w0t_off);
+  int rc = upload(h.w, &P.d_w);
+  if (!rc) rc = upload(h.encf, &P.d_encf);
+  if (!rc) rc = upload(h.encb, &P.d_encb);
+  if (!rc) rc = upload(h.consts, &P.d_consts);
+  if (!rc) rc = upload(h.w2f, &P.d_w2f);
+  if (!rc) rc = upload(h.w0t, &P.d_w0t);
+  if (!rc) rc = upload(h.w1f, &P.d_w1f);
+  if (!rc) rc = upload(h.midb, &P.d_midb);
+  if (rc) return rc;
   P.built = true;
   return SRCFD_OK;
 }

@@ -23,6 +23,7 @@
 #include "dev16.h"
 #include "kernels.h"
 #include "kernels16.h"   // lds_attr_once
+#include "operand_pack.h"
 
 namespace srcfd {
 
@@ -355,27 +356,7 @@ bool gemm_x3_qualifies(const GemmDesc& d) {
 int gemm_x3_kpad(const GemmDesc& d) { return (d.K + X3_BK - 1) / X3_BK * X3_BK; }
 
 // B[K][Npad] f32 (the f32 engine's operand) -> Wt[plane 3][N][Kpad] bf16, exact three-way split by truncation
-void gemm_x3_split_weights(const GemmDesc& d, const float* B, uint16_t* out) {
-  const int Kpad = gemm_x3_kpad(d);
-  const size_t plane = (size_t)d.N * Kpad;
-  std::memset(out, 0, 3 * plane * sizeof(uint16_t));
-  for (int k = 0; k < d.K; ++k)
-    for (int n = 0; n < d.N; ++n) {
-      const float w = B[(size_t)k * d.Npad + n];
-      uint32_t b0, b1, b2;
-      std::memcpy(&b0, &w, 4);
-      b0 &= 0xffff0000u;
-      float hi; std::memcpy(&hi, &b0, 4);
-      const float r1 = w - hi;
-      std::memcpy(&b1, &r1, 4);
-      b1 &= 0xffff0000u;
-      float mid; std::memcpy(&mid, &b1, 4);
-      const float r2 = r1 - mid;
-      std::memcpy(&b2, &r2, 4);
-      const size_t o = (size_t)n * Kpad + k;
-      out[o] = (uint16_t)(b0 >> 16); out[plane + o] = (uint16_t)(b1 >> 16); out[2 * plane + o] = (uint16_t)(b2 >> 16);
-    }
-}
+void gemm_x3_split_weights(const GemmDesc& d, const float* B, uint16_t* out) { split_planes(B, d.K, d.N, d.Npad, gemm_x3_kpad(d), out); }
 
 hipError_t launch_gemm_x3(const GemmDesc& d, const float* X, const uint16_t* Wt, const float* bias, float* Y, hipStream_t s, int num_cus) {
   if (d.M <= 0) return hipSuccess;

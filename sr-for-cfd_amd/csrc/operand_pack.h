@@ -1,0 +1,98 @@
+// Host-side operand packing: every layout a kernel reads its weights in, as pure functions from the layer graph to host vectors
+// and offsets.  These layouts are the contract between host and kernel.  No HIP runtime calls in this unit: engine.hip (plan_*),
+// fused_bf16.hip (fused_init, build_pack), train_tail.hip (train_tail_plan) and train.hip (trainer_build) decide what qualifies and
+// upload what these functions return; tools/pack_digest.cpp links the same functions on a CPU and tests/test_operand_pack.py pins
+// their bytes.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "model.h"
+#include "train_tail.h"
+
+namespace srcfd {
+
+constexpr double LOG2E = 1.4426950408889634;   // swish layers produce log2(e) x (kernels_tail32.hip, swish_l2e)
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+template <class T> void align64(std::vector<T>& v) { v.resize((v.size() + 63) / 64 * 64, T(0)); }   // 64-element aligned sections
+inline int rowof(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 accumulator row of register r in lane half h
+uint16_t to_bf16(float f);   // round to nearest even, NaN stays NaN
+uint16_t to_f16(float f);
+inline uint16_t to16(float f, bool f16) { return f16 ? to_f16(f) : to_bf16(f); }
+// f32 -> three bf16 terms (hi, mid, lo) by truncation; the two subtractions are exact
+void split3(float w, uint16_t (&o)[3]);
+// B[K][Npad] f32 -> Wt[plane 3][N][Kpad] bf16 (kernels_x3.hip, gemm_x3_split_weights)
+void split_planes(const float* B, int K, int N, int Npad, int Kpad, uint16_t* out);
+
+// ---- f32 engine: Model::pack ----
+struct Op {
+  GemmDesc d;                   // M filled per call (rows per image * batch)
+  size_t w_off = 0, b_off = 0;  // into the packed float buffer: B[K][Npad], bias[Npad]
+  int layer = 0;                // index into ModelDesc::layers
+  std::string name;
+};
+void build_plan(const ModelDesc& desc, std::vector<Op>& ops, std::vector<float>& pack);
+
+// Offsets of the fused f32 kernels' operands, appended to the pack in 64-float aligned sections (layouts: operand_pack.cpp)
+struct PairPack { size_t wa = 0, ba = 0, wb = 0, bb = 0; };
+struct TriplePack { size_t w1 = 0, b1 = 0, w2 = 0, b2 = 0, w3 = 0, b3 = 0; };
+struct Tail32Pack { size_t w1 = 0, b1 = 0, w2 = 0, b2 = 0, w3 = 0, b3 = 0, wc = 0; };
+PairPack pack_convt_pair(std::vector<float>& pk, const Layer& La, const Layer& Lb);
+TriplePack pack_convt_triple(std::vector<float>& pk, const Layer& L1, const Layer& L2, const Layer& L3);
+Tail32Pack pack_tail32(std::vector<float>& pk, const Layer& L1, const Layer& L2, const Layer& L3, const Layer& LO);
+size_t pack_enc32(std::vector<float>& pk, const Layer& conv2d_1);
+// tail32<X3>: the first two layers' fragments as three bf16 planes, appended to pack_x3
+void pack_tail32_x3(std::vector<uint16_t>& px, const Layer& L1, const Layer& L2, int64_t& w1x, int64_t& w2x);
+
+// One slot of the streaming tail's operands: which parameter of its four layers (flat order, TT_O_*; -1: padding, value 0) times
+// which factor.  Inference materialises the slots from the weights, the trainer turns the same slots into its gather map + scale.
+enum Scale : uint8_t { SC_ONE, SC_LOG2E, SC_INV_LOG2E };
+struct Slot { int src; Scale sc; };
+Tail32Pack tail32_slots(std::vector<Slot>& s);
+// map / scale / offsets of TrainTailPlan for a tail whose first parameter has flat index param_off
+void train_tail_slots(size_t param_off, TrainTailPlan& plan);
+
+// ---- bf16 / f16 path (fused_bf16.hip) ----
+struct Op16 {
+  GemmDesc d;
+  size_t w_off = 0, b_off = 0;  // elements into Pack16Host::w, floats into Fused32Pack::f32
+  int Kpad = 0, layer = 0;
+  std::string name;
+};
+struct Fused32Pack {
+  std::vector<int> cl;  // indices of the 11 compute layers in ModelDesc::layers
+  std::vector<Op16> ops;
+  std::vector<float> f32;  // conv1 weights [9][64], conv1 bias [64], per-op biases
+  size_t c1w_off = 0, c1b_off = 0;
+};
+void pack_fused_f32(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs);
+struct Pack16Host {  // one per operand type (bf16, f16); the device copies are fused_bf16.hip's Pack16
+  std::vector<uint16_t> w;                    // GEMM weights, transposed: Wt[Npad][Kpad] per op
+  std::vector<uint16_t> encf, w2f, w0t, w1f;  // enc16 fragments (one blob); tail ConvT#2; mid16 ConvT#0 LDS images per phase, ConvT#1
+  size_t enc_wd_off = 0, enc_wl_off = 0;      // byte offsets of the dense / latent fragments in encf
+  size_t w0t_off[4] = {0, 0, 0, 0};
+  std::vector<uint8_t> consts;                // tail constants (kernels16.h, TC_OFF_*)
+  std::vector<float> encb, midb;              // enc16 conv2d_1 bias fragments [128]; mid16 bias fragments b0f [128] | b1f [64]
+};
+// sets fs.ops[].w_off; the enc16 fragments only when `enc` (FusedState::enc_ok)
+void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs, bool enc, bool f16, Pack16Host& P);
+
+// ---- trainer (train.hip) ----
+// a compute layer: its index in ModelDesc::layers, elements per sample, flat parameter offsets
+struct LayerInfo { int desc_index; size_t in_elems, out_elems; bool swish; size_t kernel_off, bias_off; };
+struct DgradOp { GemmDesc d; size_t w_off; int layer; };   // w_off into the packed dgrad buffer; layer: compute layer whose INPUT gradient this produces
+// Replaces every weight by (its flat index + 1) as a float: running the ordinary packers on this
+// "index model" yields, for each packed slot, which parameter lands there (0 = padding).
+ModelDesc index_model(const ModelDesc& src, std::vector<LayerInfo>& layers, int64_t& n_params, std::vector<float>& init);
+// dgrad descriptors + packed operands (values taken from `md`, which may be the index model)
+void build_dgrad(const ModelDesc& md, const std::vector<LayerInfo>& layers, std::vector<DgradOp>& dops, std::vector<float>& pack);
+// weight-gradient map of one forward op: rows 0..K-1 = operand rows, row K = bias; flat param index + 1 (0: padding)
+std::vector<int> wgrad_gmap(const Op& op, const std::vector<float>& ipack);
+// The trainer's gather map [forward operands | data-gradient operands | the fused tail's slots], every part 64-aligned
+struct GatherMap { std::vector<int> map; size_t dpack_off = 0, dpack_elems = 0, tail_off = 0; };
+GatherMap gather_map(const std::vector<float>& ipack, const std::vector<float>& dpack, const std::vector<int>* tail_map);
+
+}  // namespace srcfd

@@ -19,15 +19,6 @@
 
 namespace srcfd {
 
-#define HIPCHECK(expr)                                                               \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));           \
-      return SRCFD_EHIP;                                                             \
-    }                                                                                \
-  } while (0)
-
 // C[z] (M x N) = A[z] (M x K) * B[z] (K x N), row-major, float64 accumulation on the matrix cores.
 // One wave per 32 x 32 tile of C (2 x 2 v_mfma_f64_16x16x4_f64 tiles), operands straight from global memory (they are
 // L2-resident: <= 1.3 MB per matrix at 400 x 400), the next 16-deep k chunk prefetched into registers while the current

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -32,15 +33,6 @@
 namespace srcfd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define HIPCHECK(expr)                                                               \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e));           \
-      return SRCFD_EHIP;                                                             \
-    }                                                                                \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // element-wise kernels
@@ -460,24 +452,9 @@ struct TrainOp {
   GemmDesc fwd;           // forward descriptor (act forced linear)
   size_t w_off, b_off;    // into the packed forward buffer (same layout as Model::pack)
   int layer;              // compute-layer ordinal
-  // dgrad (absent for the first layer)
-  // wgrad
   std::vector<int> gmap;  // (K+1) x Npad -> flat param index + 1 (0: padding)
   int* d_gmap = nullptr;
   size_t part_off = 0, part_cap = 0;   // this op's own slab space in Trainer::d_part (floats)
-};
-
-struct DgradOp {
-  GemmDesc d;
-  size_t w_off;  // into the packed dgrad buffer
-  int layer;     // compute layer whose INPUT gradient this produces
-};
-
-struct LayerInfo {
-  int desc_index;              // into ModelDesc::layers
-  size_t in_elems, out_elems;  // per sample
-  bool swish;
-  size_t kernel_off, bias_off; // flat param offsets
 };
 
 struct Trainer {
@@ -570,88 +547,7 @@ Trainer::~Trainer() {
   for (auto& o : ops) if (o.d_gmap) (void)hipFree(o.d_gmap);
 }
 
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// Replaces every weight by (its flat index + 1) as a float: running the ordinary packers on this
-// "index model" yields, for each packed slot, which parameter lands there (0 = padding).
-static ModelDesc index_model(const ModelDesc& src, std::vector<LayerInfo>& layers, int64_t& n_params, std::vector<float>& init) {
-  ModelDesc im = src;
-  int64_t off = 0;
-  layers.clear();
-  init.clear();
-  for (size_t li = 0; li < im.layers.size(); ++li) {
-    Layer& L = im.layers[li];
-    if (L.kernel.empty()) continue;
-    LayerInfo info;
-    info.desc_index = (int)li;
-    info.in_elems = (size_t)L.in_shape[0] * L.in_shape[1] * L.in_shape[2];
-    info.out_elems = (size_t)L.out_shape[0] * L.out_shape[1] * L.out_shape[2];
-    info.swish = L.act == SRCFD_ACT_SWISH;
-    info.kernel_off = (size_t)off;
-    init.insert(init.end(), L.kernel.begin(), L.kernel.end());
-    for (size_t i = 0; i < L.kernel.size(); ++i) L.kernel[i] = (float)(off + (int64_t)i + 1);
-    off += (int64_t)L.kernel.size();
-    info.bias_off = (size_t)off;
-    init.insert(init.end(), L.bias.begin(), L.bias.end());
-    for (size_t i = 0; i < L.bias.size(); ++i) L.bias[i] = (float)(off + (int64_t)i + 1);
-    off += (int64_t)L.bias.size();
-    layers.push_back(info);
-  }
-  n_params = off;
-  return im;
-}
-
-// dgrad descriptors + packed operands (values taken from `md`, which may be the index model)
-static void build_dgrad(const ModelDesc& md, const std::vector<LayerInfo>& layers, std::vector<DgradOp>& dops, std::vector<float>& pack) {
-  dops.clear();
-  pack.clear();
-  for (size_t ci = 1; ci < layers.size(); ++ci) {  // the first layer's input needs no gradient
-    const Layer& L = md.layers[layers[ci].desc_index];
-    const int IH = L.in_shape[0], IW = L.in_shape[1], OH = L.out_shape[0], OW = L.out_shape[1];
-    GemmDesc d{};
-    d.act = SRCFD_ACT_LINEAR;
-    d.nphx = 1; d.os = 1;
-    d.N = L.cin; d.Npad = round_up(d.N, 32); d.CO = L.cin; d.OC = L.cin;
-    std::vector<float> B;
-    if (L.kind == SRCFD_LAYER_DENSE) {
-      d.MH = d.MW = 1; d.TY = d.TX = 1; d.CI = L.cout; d.IH = d.IW = 1; d.OH = d.OW = 1;
-      d.K = L.cout;
-      B.resize((size_t)d.K * d.N);
-      for (int co = 0; co < L.cout; ++co)
-        for (int c = 0; c < L.cin; ++c) B[(size_t)co * d.N + c] = L.kernel[(size_t)c * L.cout + co];
-    } else if (L.kind == SRCFD_LAYER_CONV2D) {
-      if (L.stride != 1) throw std::runtime_error("training: strided Conv2D is only supported as the first layer");
-      int pt = 0, pl = 0;
-      if (L.same) { pt = std::max((OH - 1) + L.kh - IH, 0) / 2; pl = std::max((OW - 1) + L.kw - IW, 0) / 2; }
-      d.MH = IH; d.MW = IW; d.TY = L.kh; d.TX = L.kw; d.CI = L.cout; d.IH = OH; d.IW = OW; d.OH = IH; d.OW = IW;
-      d.ay = d.ax = 1; d.by = d.bx = -1; d.cy = pt; d.cx = pl;
-      d.K = L.kh * L.kw * L.cout;
-      B.resize((size_t)d.K * d.N);
-      for (int ky = 0; ky < L.kh; ++ky)
-        for (int kx = 0; kx < L.kw; ++kx)
-          for (int co = 0; co < L.cout; ++co)
-            for (int c = 0; c < L.cin; ++c)
-              B[((size_t)(ky * L.kw + kx) * L.cout + co) * d.N + c] = L.kernel[(((size_t)ky * L.kw + kx) * L.cin + c) * L.cout + co];
-    } else {  // Conv2DTranspose VALID, kernel (kh,kw,Cout,Cin): dX[i,j,ci] = sum dZ[s i + a, s j + b, co] W[a,b,co,ci]
-      d.MH = IH; d.MW = IW; d.TY = L.kh; d.TX = L.kw; d.CI = L.cout; d.IH = OH; d.IW = OW; d.OH = IH; d.OW = IW;
-      d.ay = d.ax = L.stride; d.by = d.bx = 1; d.cy = d.cx = 0;
-      d.K = L.kh * L.kw * L.cout;
-      B = L.kernel;  // already [(a,b,co)][ci]
-    }
-    DgradOp op;
-    op.d = d;
-    op.layer = (int)ci;
-    while (pack.size() % 64) pack.push_back(0.f);
-    op.w_off = pack.size();
-    pack.resize(pack.size() + (size_t)d.K * d.Npad, 0.f);
-    for (int k = 0; k < d.K; ++k) std::memcpy(&pack[op.w_off + (size_t)k * d.Npad], &B[(size_t)k * d.N], sizeof(float) * d.N);
-    dops.push_back(op);
-  }
-}
-
-static int upload_map(const std::vector<float>& as_float, int** d_map) {
-  std::vector<int> m(as_float.size());
-  for (size_t i = 0; i < as_float.size(); ++i) m[i] = (int)as_float[i];
+static int upload_map(const std::vector<int>& m, int** d_map) {
   HIPCHECK(hipMalloc(d_map, std::max<size_t>(m.size(), 1) * sizeof(int)));
   HIPCHECK(hipMemcpy(*d_map, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice));
   return SRCFD_OK;
@@ -693,13 +589,12 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     const char* e = getenv("SRCFD_TRAIN_TAIL");
     t.use_tail = t.tail.ok && !(e && atoi(e) == 0) && (uint64_t)max_batch * t.tail.H * t.tail.W * t.tail.H * t.tail.W < (1ull << 32);
   }
-  while (ipack.size() % 64) ipack.push_back(0.f);
   if (t.use_tail) {
     HIPCHECK(hipMalloc(&t.d_pack_scale, t.tail.scale.size() * sizeof(float)));
     HIPCHECK(hipMemcpy(t.d_pack_scale, t.tail.scale.data(), t.tail.scale.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(hipMalloc(&t.d_tail_slabs, (size_t)t.num_cus * TT_PARAMS * sizeof(float)));
     std::vector<int> gm(TT_PARAMS);
-    for (int i = 0; i < TT_PARAMS; ++i) gm[i] = (int)(t.tail.param_off + i + 1);
+    std::iota(gm.begin(), gm.end(), (int)t.tail.param_off + 1);
     HIPCHECK(hipMalloc(&t.d_tail_gmap, TT_PARAMS * sizeof(int)));
     HIPCHECK(hipMemcpy(t.d_tail_gmap, gm.data(), TT_PARAMS * sizeof(int), hipMemcpyHostToDevice));
   }
@@ -712,12 +607,8 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     int ci = -1;
     for (size_t k = 0; k < t.layers.size(); ++k) if (t.layers[k].desc_index == op.layer) ci = (int)k;
     to.layer = ci;
-    // gradient map: rows 0..K-1 = operand rows, row K = bias
     const GemmDesc& d = op.d;
-    to.gmap.assign((size_t)(d.K + 1) * d.Npad, 0);
-    for (int k = 0; k < d.K; ++k)
-      for (int n = 0; n < d.N; ++n) to.gmap[(size_t)k * d.Npad + n] = (int)ipack[op.w_off + (size_t)k * d.Npad + n];
-    for (int n = 0; n < d.N; ++n) to.gmap[(size_t)d.K * d.Npad + n] = (int)ipack[op.b_off + n];
+    to.gmap = wgrad_gmap(op, ipack);
     HIPCHECK(hipMalloc(&to.d_gmap, to.gmap.size() * sizeof(int)));
     HIPCHECK(hipMemcpy(to.d_gmap, to.gmap.data(), to.gmap.size() * sizeof(int), hipMemcpyHostToDevice));
     size_t op_need = 1;
@@ -745,15 +636,10 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   // dgrad plan
   std::vector<float> dpack;
   build_dgrad(im, t.layers, t.dops, dpack);
-  while (!dpack.empty() && dpack.size() % 64) dpack.push_back(0.f);
-  t.dpack_off = ipack.size();
-  t.dpack_elems = dpack.size();
-  ipack.insert(ipack.end(), dpack.begin(), dpack.end());
-  t.tail_pack_off = ipack.size();            // the scaled slots come last (gather_pack_f32: one scale region)
-  if (t.use_tail) for (int k : t.tail.map) ipack.push_back((float)k);
-  while (ipack.size() % 64) ipack.push_back(0.f);
-  t.pack_elems = ipack.size();
-  int rc = upload_map(ipack, &t.d_pack_map);
+  const GatherMap gm = gather_map(ipack, dpack, t.use_tail ? &t.tail.map : nullptr);
+  t.dpack_off = gm.dpack_off; t.dpack_elems = gm.dpack_elems; t.tail_pack_off = gm.tail_off;
+  t.pack_elems = gm.map.size();
+  int rc = upload_map(gm.map, &t.d_pack_map);
   if (rc) return rc;
   HIPCHECK(hipMalloc(&t.d_pack, t.pack_elems * sizeof(float)));
   t.d_dpack = t.d_pack + t.dpack_off;

@@ -32,6 +32,7 @@
 #include <stdexcept>
 
 #include "kernels16.h"  // lds_attr_once
+#include "operand_pack.h"
 #include "train_tail.h"
 
 namespace srcfd {
@@ -428,76 +429,7 @@ void train_tail_plan(const ModelDesc& desc, const int* desc_index, const size_t*
   plan.first_layer = f;
   plan.H = L1.in_shape[0]; plan.W = L1.in_shape[1];
   plan.param_off = o;
-  const double LOG2E = 1.4426950408889634;
-  auto& mp = plan.map;
-  auto& sc = plan.scale;
-  auto align = [&]() { while (mp.size() % 64) { mp.push_back(0); sc.push_back(0.f); } };
-  auto put = [&](size_t flat, double scale) { mp.push_back((int)(flat + 1)); sc.push_back((float)scale); };
-  const size_t W1 = o + TT_O_W1, B1 = o + TT_O_B1, W2 = o + TT_O_W2, B2 = o + TT_O_B2, W3 = o + TT_O_W3, B3 = o + TT_O_B3, WC = o + TT_O_WC,
-               BC = o + TT_O_BC;
-  // Conv2DTranspose kernels are (kh, kw, Cout, Cin): flat (tap*Cout + co)*Cin + ci
-  auto w1 = [&](int tap, int co, int ci) { return W1 + ((size_t)tap * 32 + co) * 64 + ci; };
-  auto w2 = [&](int tap, int co, int ci) { return W2 + ((size_t)tap * 16 + co) * 32 + ci; };
-  auto w3 = [&](int tap, int co, int ci) { return W3 + ((size_t)tap * 8 + co) * 16 + ci; };
-  // fragment lane maps of engine.hip plan_tail32 (lane = (m = lane & 15, kg = lane >> 4)), with factor `s1` on the first layer
-  auto fwd_frags = [&](double s1) {
-    for (int tap = 0; tap < 4; ++tap)
-      for (int t = 0; t < 2; ++t)
-        for (int s = 0; s < 16; ++s)
-          for (int lane = 0; lane < 64; ++lane) put(w1(tap, 16 * t + (lane & 15), 16 * (lane >> 4) + s), s1);
-  };
-  auto fwd_frags2 = [&]() {
-    for (int tap = 0; tap < 4; ++tap)
-      for (int t = 0; t < 2; ++t)
-        for (int i = 0; i < 4; ++i)
-          for (int lane = 0; lane < 64; ++lane) put(w2(tap, lane & 15, 16 * t + 4 * (lane >> 4) + i), 1.0);
-  };
-  auto fwd_frags3 = [&]() {
-    for (int u = 0; u < 2; ++u)
-      for (int i = 0; i < 4; ++i)
-        for (int lane = 0; lane < 64; ++lane) put(w3(2 * u + ((lane & 15) >> 3), lane & 7, 4 * (lane >> 4) + i), 1.0);
-  };
-  // ---- tail32's operands (swish layers produce log2(e) x: kernels_tail32.hip, swish_l2e) ----
-  align(); plan.t32_w1 = mp.size(); fwd_frags(LOG2E);
-  align(); plan.t32_b1 = mp.size(); for (int c = 0; c < 32; ++c) put(B1 + c, LOG2E);
-  align(); plan.t32_w2 = mp.size(); fwd_frags2();
-  align(); plan.t32_b2 = mp.size(); for (int c = 0; c < 16; ++c) put(B2 + c, LOG2E);
-  align(); plan.t32_w3 = mp.size(); fwd_frags3();
-  align(); plan.t32_b3 = mp.size(); for (int c = 0; c < 8; ++c) put(B3 + c, LOG2E);
-  align(); plan.t32_wc = mp.size(); for (int k = 0; k < 72; ++k) put(WC + k, 1.0 / LOG2E); put(BC, 1.0);
-  // ---- tail_bwd32: unscaled forward fragments, data-gradient fragments, biases ----
-  align(); plan.wf = mp.size(); fwd_frags(1.0); fwd_frags2(); fwd_frags3();
-  align(); plan.wb = mp.size();
-  for (int tap = 0; tap < 4; ++tap)      // a1b[tap][t][c][i][lane] = W1[tap][co 16c + 4kg + i][ci 16t + m]
-    for (int t = 0; t < 4; ++t)
-      for (int c = 0; c < 2; ++c)
-        for (int i = 0; i < 4; ++i)
-          for (int lane = 0; lane < 64; ++lane) put(w1(tap, 16 * c + 4 * (lane >> 4) + i, 16 * t + (lane & 15)), 1.0);
-  for (int tap = 0; tap < 4; ++tap)      // a2b[tap][t][i][lane] = W2[tap][co 4kg + i][ci 16t + m]
-    for (int t = 0; t < 2; ++t)
-      for (int i = 0; i < 4; ++i)
-        for (int lane = 0; lane < 64; ++lane) put(w2(tap, 4 * (lane >> 4) + i, 16 * t + (lane & 15)), 1.0);
-  for (int u = 0; u < 2; ++u)            // a3b[u][i][lane] = W3[tap3 = 2u + (r >> 3)][co r & 7][ci m], r = 4kg + i
-    for (int i = 0; i < 4; ++i)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int r = 4 * (lane >> 4) + i;
-        put(w3(2 * u + (r >> 3), r & 7, lane & 15), 1.0);
-      }
-  align(); plan.wt = mp.size();
-  for (int s3 = 0; s3 < 3; ++s3)         // wt[s][lane] = Wc[2 - s][2 - (b' - tx3)][co] for 0 <= b' - tx3 <= 2, else 0; m = 8 tx3 + co, b' = kg
-    for (int lane = 0; lane < 64; ++lane) {
-      const int m = lane & 15, tx3 = m >> 3, co = m & 7, d = (lane >> 4) - tx3;
-      if (d >= 0 && d <= 2) put(WC + (size_t)((2 - s3) * 3 + (2 - d)) * 8 + co, 1.0);
-      else { mp.push_back(0); sc.push_back(0.f); }
-    }
-  align(); plan.bias = mp.size();
-  for (int c = 0; c < 32; ++c) put(B1 + c, 1.0);
-  for (int c = 0; c < 16; ++c) put(B2 + c, 1.0);
-  for (int c = 0; c < 8; ++c) put(B3 + c, 1.0);
-  for (int k = 0; k < 72; ++k) put(WC + k, 1.0);
-  put(BC, 1.0);
-  align();
-  if (mp.size() - plan.wf < (size_t)TT_WF || plan.wt - plan.wb != (size_t)TT_WB || plan.bias - plan.wt != (size_t)TT_WT) throw std::runtime_error("train_tail_plan: pack sizes");
+  train_tail_slots(o, plan);   // operand_pack.cpp: the same slots inference materialises (engine.hip, plan_tail32)
   plan.ok = true;
 }
 

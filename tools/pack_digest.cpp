@@ -1,0 +1,241 @@
+// Host-only harness for the operand packers (sr-for-cfd_amd/csrc/operand_pack.cpp): packs a whole-model .h5 (loaded through
+// model.cpp) the way the engine, the 16-bit path and the trainer do, plus three small graphs built here from a seeded generator,
+// and prints JSON: per named section its offset, length (elements) and sha256.  Built by `make -C sr-for-cfd_amd/csrc pack_digest`
+// with -fsanitize=address,undefined; tests/test_operand_pack.py compares the output with tests/golden/operand_pack_digests.json.
+//   pack_digest <superres.h5> [dump-dir]     dump-dir: raw arrays for the test's property checks
+// Which fused kernels a graph qualifies for is decided in engine.hip / fused_bf16.hip / train_tail.hip (HIP translation units this
+// harness does not link); find_chain() and the shape tests below restate those decisions for the graphs at hand, and the recorded
+// `plan` / `fused.c1_off` / `train.tail_plan` sections pin them.
+#include <cstdio>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../sr-for-cfd_amd/csrc/operand_pack.h"
+#include "sha256.h"
+
+namespace srcfd {
+thread_local std::string g_last_error;
+void set_error(const std::string& m) { g_last_error = m; }
+}  // namespace srcfd
+using namespace srcfd;
+
+static bool g_first = true;
+static std::string g_dump;
+template <class T> static void section(const std::string& name, const T* p, size_t len, size_t off = 0) {
+  std::printf("%s\n  {\"name\": \"%s\", \"off\": %zu, \"len\": %zu, \"sha256\": \"%s\"}", g_first ? "" : ",", name.c_str(), off, len,
+              sha256_hex(p, len * sizeof(T)).c_str());
+  g_first = false;
+}
+template <class T> static void whole(const std::string& name, const std::vector<T>& v, bool dump = false) {
+  section(name, v.data(), v.size());
+  if (dump && !g_dump.empty()) {
+    FILE* f = std::fopen((g_dump + "/" + name + ".bin").c_str(), "wb");
+    if (!f || std::fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); std::exit(2); }
+    std::fclose(f);
+  }
+}
+static void ints(const std::string& name, const std::vector<int64_t>& v) { section(name, v.data(), v.size()); }
+
+// first op of a run of kernel == stride == 2 transposed convolutions on consecutive layers with these channel counts, or -1
+static int find_chain(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<int>& ch) {
+  const size_t n = ch.size() - 1;
+  for (size_t i = 0; i + n <= ops.size(); ++i) {
+    bool ok = true;
+    for (size_t q = 0; q < n && ok; ++q) {
+      const Layer& L = md.layers[ops[i + q].layer];
+      ok = L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2 && L.cin == ch[q] && L.cout == ch[q + 1] &&
+           ops[i + q].d.nphx == 2 && ops[i + q].layer == ops[i].layer + (int)q;
+    }
+    if (ok) return (int)i;
+  }
+  return -1;
+}
+
+// the f32 engine's operands: finish_create() of engine.hip
+static void f32_sections(const std::string& tag, const ModelDesc& md, std::vector<Op>& ops, std::vector<float>& pack) {
+  build_plan(md, ops, pack);
+  auto L = [&](int op) -> const Layer& { return md.layers[ops[op].layer]; };
+  PairPack pair; TriplePack tri; Tail32Pack t32;
+  const int pair_op = find_chain(md, ops, {32, 16, 8});
+  if (pair_op >= 0) pair = pack_convt_pair(pack, L(pair_op), L(pair_op + 1));
+  const int triple_op = find_chain(md, ops, {64, 32, 16, 8});
+  if (triple_op >= 0) tri = pack_convt_triple(pack, L(triple_op), L(triple_op + 1), L(triple_op + 2));
+  int tail32_op = -1;
+  if (triple_op >= 0 && (size_t)triple_op + 4 == ops.size() && L(triple_op + 3).kind == SRCFD_LAYER_CONV2D && L(triple_op + 3).cin == 8 && L(triple_op + 3).cout == 1) {
+    tail32_op = triple_op;
+    t32 = pack_tail32(pack, L(tail32_op), L(tail32_op + 1), L(tail32_op + 2), L(tail32_op + 3));
+  }
+  size_t enc32_w2 = 0;
+  const bool enc32_ok = ops.size() >= 4 && md.in_shape[0] == 10 && md.in_shape[2] == 1 && L(1).kind == SRCFD_LAYER_CONV2D && L(1).cin == 64 && L(1).cout == 128;
+  if (enc32_ok) enc32_w2 = pack_enc32(pack, L(1));
+  // SRCFD_PREC_FP32X3: gemm_x3_qualifies() / gemm_x3_kpad() of kernels_x3.hip (32-deep k tiles, 128-channel blocks)
+  std::vector<int64_t> x3_off(ops.size(), -1);
+  std::vector<uint16_t> px;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    const GemmDesc& d = ops[i].d;
+    if (!(d.K >= 128 && d.CI % 32 == 0 && d.N % 128 == 0 && d.CO % 32 == 0 && d.OC % 4 == 0 && (d.act == SRCFD_ACT_SWISH || d.act == SRCFD_ACT_LINEAR))) continue;
+    const int Kpad = round_up(d.K, 32);
+    align64(px);
+    x3_off[i] = (int64_t)px.size();
+    px.resize(px.size() + (size_t)3 * d.N * Kpad);
+    split_planes(pack.data() + ops[i].w_off, d.K, d.N, d.Npad, Kpad, px.data() + x3_off[i]);
+  }
+  int64_t w1x = -1, w2x = -1;
+  if (tail32_op >= 0) pack_tail32_x3(px, L(tail32_op), L(tail32_op + 1), w1x, w2x);
+
+  whole(tag + "pack", pack, tag.empty());
+  std::vector<int64_t> oo;
+  for (const Op& o : ops) { oo.push_back((int64_t)o.w_off); oo.push_back((int64_t)o.b_off); }
+  ints(tag + "ops_off", oo);
+  ints(tag + "plan", {pair_op, triple_op, tail32_op, (int64_t)enc32_ok});
+  auto sec = [&](const char* n, size_t off, size_t len) { section(tag + "pack." + n, pack.data() + off, len, off); };
+  if (enc32_ok) sec("enc32_w2", enc32_w2, 73728);
+  if (pair_op >= 0) { sec("pair_wa", pair.wa, 2048); sec("pair_ba", pair.ba, 16); sec("pair_wb", pair.wb, 512); sec("pair_bb", pair.bb, 8); }
+  if (triple_op >= 0) { sec("tri_w1", tri.w1, 8192); sec("tri_b1", tri.b1, 32); sec("tri_w2", tri.w2, 2048); sec("tri_b2", tri.b2, 16); sec("tri_w3", tri.w3, 512); sec("tri_b3", tri.b3, 8); }
+  if (tail32_op >= 0) { sec("t32_w1", t32.w1, 8192); sec("t32_b1", t32.b1, 32); sec("t32_w2", t32.w2, 2048); sec("t32_b2", t32.b2, 16); sec("t32_w3", t32.w3, 512); sec("t32_b3", t32.b3, 8); sec("t32_wc", t32.wc, 73); }
+  whole(tag + "pack_x3", px);
+  ints(tag + "x3_off", x3_off);
+  if (w1x >= 0) section(tag + "pack_x3.t32_w1x", px.data() + w1x, 24576, (size_t)w1x);
+  if (w2x >= 0) section(tag + "pack_x3.t32_w2x", px.data() + w2x, 6144, (size_t)w2x);
+}
+
+// fused_init() + build_pack() of fused_bf16.hip for both operand types
+static void fused_sections(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack) {
+  Fused32Pack fs;
+  pack_fused_f32(md, ops, pack, fs);
+  const bool enc_ok = true;   // encoder_10: fused_init's shape test
+  whole("fused.f32", fs.f32);
+  std::vector<int64_t> bo;
+  for (const Op16& o : fs.ops) bo.push_back((int64_t)o.b_off);
+  ints("fused.b_off", bo);
+  ints("fused.c1_off", {(int64_t)fs.c1w_off, (int64_t)fs.c1b_off, (int64_t)enc_ok});
+  for (int f16 = 0; f16 < 2; ++f16) {
+    const std::string px = f16 ? "f16." : "bf16.";
+    Pack16Host P;
+    pack_fused16(md, ops, pack, fs, enc_ok, f16 != 0, P);
+    whole(px + "Wt", P.w);
+    std::vector<int64_t> wo;
+    for (const Op16& o : fs.ops) wo.push_back((int64_t)o.w_off);
+    ints(px + "w_off", wo);
+    whole(px + "encf", P.encf);
+    ints(px + "enc_off", {(int64_t)P.enc_wd_off, (int64_t)P.enc_wl_off});
+    whole(px + "encb", P.encb);
+    whole(px + "consts", P.consts);
+    whole(px + "w2f", P.w2f);
+    whole(px + "w0t", P.w0t);
+    ints(px + "w0t_off", {(int64_t)P.w0t_off[0], (int64_t)P.w0t_off[1], (int64_t)P.w0t_off[2], (int64_t)P.w0t_off[3]});
+    whole(px + "w1f", P.w1f);
+    whole(px + "midb", P.midb);
+  }
+}
+
+// trainer_build() of train.hip with the fused tail (train_tail_plan accepts decoder_400's last four layers)
+static void train_sections(const ModelDesc& md) {
+  std::vector<LayerInfo> layers;
+  int64_t n_params = 0;
+  std::vector<float> init;
+  const ModelDesc im = index_model(md, layers, n_params, init);
+  std::vector<Op> iops;
+  std::vector<float> ipack;
+  build_plan(im, iops, ipack);
+  TrainTailPlan tail;
+  tail.first_layer = (int)layers.size() - 4;
+  const Layer& L1 = md.layers[layers[tail.first_layer].desc_index];
+  tail.H = L1.in_shape[0]; tail.W = L1.in_shape[1];
+  tail.param_off = layers[tail.first_layer].kernel_off;
+  train_tail_slots(tail.param_off, tail);
+  whole("train.scale", tail.scale, true);
+  whole("train.tail_map", tail.map, true);
+  ints("train.tail_plan", {tail.first_layer, tail.H, tail.W, (int64_t)tail.param_off, (int64_t)tail.t32_w1, (int64_t)tail.t32_b1, (int64_t)tail.t32_w2,
+                           (int64_t)tail.t32_b2, (int64_t)tail.t32_w3, (int64_t)tail.t32_b3, (int64_t)tail.t32_wc, (int64_t)tail.wf, (int64_t)tail.wb,
+                           (int64_t)tail.wt, (int64_t)tail.bias});
+  std::vector<int> tg(TT_PARAMS);
+  std::iota(tg.begin(), tg.end(), (int)tail.param_off + 1);
+  whole("train.tail_gmap", tg);
+  for (size_t i = 0; i < iops.size(); ++i) whole("train.op" + std::to_string(i) + ".gmap", wgrad_gmap(iops[i], ipack), true);
+  std::vector<DgradOp> dops;
+  std::vector<float> dpack;
+  build_dgrad(im, layers, dops, dpack);
+  const GatherMap gm = gather_map(ipack, dpack, &tail.map);
+  whole("train.init_params", init, true);
+  ints("train.offsets", {(int64_t)gm.dpack_off, (int64_t)gm.dpack_elems, (int64_t)gm.tail_off, (int64_t)gm.map.size(), n_params});
+  std::vector<int64_t> doff;
+  for (const DgradOp& o : dops) doff.push_back((int64_t)o.w_off);
+  ints("train.dops_off", doff);
+  whole("train.map", gm.map);
+  if (!g_dump.empty()) {   // per op: K N Npad layer-kind, for the bijection check
+    FILE* f = std::fopen((g_dump + "/train.ops.txt").c_str(), "w");
+    if (!f) std::exit(2);
+    for (const Op& o : iops) std::fprintf(f, "%d %d %d %d %d\n", o.d.K, o.d.N, o.d.Npad, o.layer, o.d.nphx);
+    std::fclose(f);
+  }
+}
+
+// small graphs from a seeded generator (the same sequence is easy to write in any language: a 32-bit LCG, top 24 bits - 0.5)
+struct Lcg {
+  uint32_t s;
+  std::vector<float> take(size_t n) {
+    std::vector<float> v(n);
+    for (float& x : v) { s = s * 1664525u + 1013904223u; x = (float)((double)(s >> 8) / 16777216.0 - 0.5); }
+    return v;
+  }
+};
+static Layer layer(Lcg& g, int kind, int act, int k, int stride, int same, int cin, int cout, const char* name) {
+  Layer L;
+  L.kind = kind; L.act = act; L.kh = L.kw = k; L.stride = stride; L.same = same; L.cin = cin; L.cout = cout; L.name = name;
+  if (kind != SRCFD_LAYER_FLATTEN) { L.kernel = g.take((size_t)k * k * cin * cout); L.bias = g.take(cout); }
+  return L;
+}
+static void small_graph(const std::string& tag, ModelDesc md) {
+  md.infer_shapes();
+  std::vector<Op> ops;
+  std::vector<float> pack;
+  f32_sections(tag, md, ops, pack);
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) { std::fprintf(stderr, "usage: pack_digest <superres.h5> [dump-dir]\n"); return 2; }
+  if (argc > 2) g_dump = argv[2];
+  try {
+    std::printf("{\"sections\": [");
+    ModelDesc md;
+    append_h5_whole(md, argv[1]);
+    md.infer_shapes();
+    std::vector<Op> ops;
+    std::vector<float> pack;
+    f32_sections("", md, ops, pack);
+    if (!md.is_sr_10_400()) { std::fprintf(stderr, "not the encoder_10 + decoder_400 graph\n"); return 2; }
+    fused_sections(md, ops, pack);
+    train_sections(md);
+    const int CT = SRCFD_LAYER_CONV2D_TRANSPOSE, CV = SRCFD_LAYER_CONV2D, DE = SRCFD_LAYER_DENSE, SW = SRCFD_ACT_SWISH;
+    {  // a 3x3 stride-2 ConvT: four output phases with 4 / 2 / 2 / 1 taps
+      Lcg g{1};
+      ModelDesc m; m.in_shape[0] = 4; m.in_shape[1] = 4; m.in_shape[2] = 8;
+      m.layers = {layer(g, CT, SW, 3, 2, 0, 8, 4, "ct")};
+      small_graph("convt3.", m);
+    }
+    {  // 32 -> 16 -> 8 with no 64 -> 32 in front: the pair without the triple
+      Lcg g{2};
+      ModelDesc m; m.in_shape[0] = 5; m.in_shape[1] = 5; m.in_shape[2] = 32;
+      m.layers = {layer(g, CT, SW, 2, 2, 0, 32, 16, "a"), layer(g, CT, SW, 2, 2, 0, 16, 8, "b")};
+      small_graph("pair.", m);
+    }
+    {  // an encoder whose second convolution has 64 channels, not 128: plan_enc32 declines
+      Lcg g{3};
+      ModelDesc m; m.in_shape[0] = 10; m.in_shape[1] = 10; m.in_shape[2] = 1;
+      Layer fl; fl.kind = SRCFD_LAYER_FLATTEN; fl.name = "f";
+      m.layers = {layer(g, CV, SW, 3, 2, 1, 1, 64, "c1"), layer(g, CV, SW, 3, 1, 1, 64, 64, "c2"), fl, layer(g, DE, SW, 1, 1, 0, 1600, 128, "d"),
+                  layer(g, DE, SRCFD_ACT_LINEAR, 1, 1, 0, 128, 50, "l")};
+      small_graph("noenc32.", m);
+    }
+    std::printf("\n]}\n");
+  } catch (const FileError& e) {
+    std::fprintf(stderr, "pack_digest: %s\n", e.msg.c_str());
+    return 1;
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "pack_digest: %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}
