@@ -327,6 +327,37 @@ int srcfd_fine_solver_get_state(srcfd_fine_solver* s, double* var);
  * solves of the last outer iteration.  Either may be NULL. */
 int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], int last_sweeps[3]);
 
+/* ---- batches of fine-mesh cases (the sweeps that make training data) ---------------------------------
+ * Replaces the loop over Reynolds numbers of sr-simulation-data-creation.ipynb cell 2: n_cases problems with one nx, ny, scheme
+ * and case_type (everything else may differ per case) advance together, the case index as the second grid dimension of every
+ * launch (csrc/fine_batch.hip).  Each case computes what a srcfd_fine_solver of its own computes, bit for bit, whatever the
+ * batch size and its position in it.  A case that converges, or whose residuals stop being finite, is frozen; the others go on. */
+typedef struct srcfd_fine_batch srcfd_fine_batch;
+#define SRCFD_CASE_RUNNING 0   /* also: stopped only because run()'s iteration budget ended; resumable */
+#define SRCFD_CASE_CONVERGED 1
+#define SRCFD_CASE_DIVERGED 2
+/* SRCFD_EINVAL, naming the case and the field, when a problem is invalid or differs from case 0 in nx, ny, scheme or
+ * case_type, and when n_cases is outside 1..64. */
+int srcfd_fine_batch_create(const srcfd_coarse_problem* problems, int n_cases, int device, srcfd_fine_batch** out);
+void srcfd_fine_batch_destroy(srcfd_fine_batch* b);
+/* var NULL: zero fields; otherwise (n_cases, 3, nx+2, ny+2) host float64, each case as srcfd_fine_solver_init takes its own.
+ * Every case is RUNNING again, at iteration 0. */
+int srcfd_fine_batch_init(srcfd_fine_batch* b, const double* var);
+/* Up to max_iterations more outer iterations of every case that is RUNNING; returns when none is, or when the budget is
+ * spent.  Per case: iterations[n] (a frozen case keeps the count at which it froze), status[n] (SRCFD_CASE_*), rms[n][3] of
+ * its last convergence check, history[n][history_len][3] = its rms at its iteration counts divisible by 100 that this call
+ * reaches.  A diverged case is no error: the call returns SRCFD_OK and reports SRCFD_CASE_DIVERGED for it. */
+int srcfd_fine_batch_run(srcfd_fine_batch* b, int max_iterations, int* iterations, int* status, double* rms, double* history,
+                         int history_len);
+/* Copies Var of case case_index (3, nx+2, ny+2), or of all cases (n_cases, 3, nx+2, ny+2) for -1, to host memory. */
+int srcfd_fine_batch_get_state(srcfd_fine_batch* b, int case_index, double* var);
+/* counters as srcfd_fine_solver_counters, with [0] and [1] counting per inner solve the sweeps of the live case that took the
+ * most (the launches that did work); last_sweeps[n][3]: each case's own sweeps in its last outer iteration. */
+int srcfd_fine_batch_counters(const srcfd_fine_batch* b, int64_t counters[4], int* last_sweeps);
+/* Device bytes a batch allocates: n_cases x ((14 planes x (nx+2)(ny+2) + 9 nx) x 8 + one status block + one parameter
+ * block).  Needs no device. */
+int srcfd_fine_batch_footprint(int nx, int ny, int n_cases, int64_t* device_bytes);
+
 /* ---- training -----------------------------------------------------------
  * One optimisation step of SuperResolutionAE, split so that a data-parallel driver can put its
  * gradient all-reduce between the two halves (one flat f32 buffer per step).

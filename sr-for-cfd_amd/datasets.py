@@ -9,11 +9,13 @@ of length n*n (row-major (ny, nx)).
 """
 from __future__ import annotations
 
+import os
 import re
-from typing import Dict, Iterable, List, Sequence, Tuple, Union
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from .coarse import LDC_DOUBLE_LID
 from .h5 import H5File, H5Writer
 from .stats import save_stats
 
@@ -153,8 +155,10 @@ def save_component_stats(path, lr_dim: int, hr_dim: int, stats_lr, stats_hr) -> 
     save_stats(path, lr_dim, hr_dim, stats_lr, stats_hr)
 
 
-def append_solution(writer: H5Writer, Re: int, n: int, fields: Dict[str, np.ndarray], bc_type: str, case_name: str = "") -> None:
-    """One `Re{Re}_mesh{n}x{n}` group in the data-creation notebook's schema (save_solution, r262-285)."""
+def append_solution(writer: H5Writer, Re: int, n: int, fields: Dict[str, np.ndarray], bc_type: str, case_name: str = "",
+                    lx: Optional[float] = None, ly: Optional[float] = None) -> None:
+    """One `Re{Re}_mesh{n}x{n}` group in the data-creation notebook's schema (save_solution, r262-285).  With `lx` and `ly`
+    also its `x` and `y` datasets: np.meshgrid(np.linspace(0, lx, n), np.linspace(0, ly, n)), flattened."""
     g = f"Re{Re}_mesh{n}x{n}"
     writer.group(g)
     writer.attr(g, "bc_type", bc_type)
@@ -164,6 +168,10 @@ def append_solution(writer: H5Writer, Re: int, n: int, fields: Dict[str, np.ndar
     writer.attr(g, "nx", np.int64(n))
     writer.attr(g, "ny", np.int64(n))
     writer.attr(g, "total_points", np.int64(n * n))
+    if lx is not None and ly is not None:
+        X, Y = np.meshgrid(np.linspace(0, lx, n), np.linspace(0, ly, n))
+        writer.dataset(f"{g}/x", X.flatten())
+        writer.dataset(f"{g}/y", Y.flatten())
     for c in COMPONENTS:
         writer.dataset(f"{g}/{c}", np.asarray(fields[c], np.float64).reshape(-1))
 
@@ -184,3 +192,64 @@ def prepare_training_set(file_paths: Iterable[str], lr_dim: int, hr_dim: int, re
                 x_lr_test=tl, x_hr_test=th, res_test=res[test], comps_test=comps[test],
                 x_lr_test_raw=x_lr[test], x_hr_test_raw=x_hr[test],
                 stats_lr=stats_lr, stats_hr=stats_hr, reynolds_to_evaluate=evaluate)
+
+
+_INT_ATTRS = ("nx", "ny", "total_points")
+
+
+def _copy_groups(path, writer: H5Writer, skip=()) -> None:
+    """Every top-level group of an existing file that is not in `skip` into `writer`: datasets with their type and shape,
+    string attributes as strings, the schema's nx / ny / total_points as int64, other numeric attributes as float64."""
+    with H5File(path) as f:
+        for g in f.keys("/"):
+            if g in skip or f.kind(g) != "group":
+                continue
+            writer.group(g)
+            for a in f.attr_names(g):
+                try:
+                    v = f.attr_num(g, a)
+                except (ValueError, OSError, KeyError):
+                    writer.attr(g, a, f.attr_str(g, a)[0])
+                    continue
+                v = v.astype(np.int64 if a in _INT_ATTRS else np.float64)
+                writer.attr(g, a, v[0] if v.size == 1 else v)
+            for d in f.keys(g):
+                if f.kind(f"{g}/{d}") == "dataset":
+                    writer.dataset(f"{g}/{d}", f.read(f"{g}/{d}"))
+
+
+def generate_simulation_file(path, reynolds_numbers: Iterable[int] = range(100, 801, 100), mesh_sizes: Sequence[int] = (10, 50, 400),
+                             bc=LDC_DOUBLE_LID, bc_type: str = "double_lid(u_top=1,u_bottom=1)",
+                             case_name: str = "double lid driven cavity", dt: float = 0.001, scheme: str = "QUICK",
+                             convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
+                             max_batch: int = 8, device: int = 0, solve: Optional[Callable] = None) -> List[Tuple[int, int, int, int]]:
+    """The data-creation notebook's sweep (sr-simulation-data-creation.ipynb cell 2): every Reynolds number on every n x n mesh
+    from zero fields, one `Re{Re}_mesh{n}x{n}` group each in `path`, which `load_paired_reynolds_multi` reads.  Per mesh size
+    the Reynolds numbers are solved `max_batch` at a time by `fine.run_normal_simulations` (or by `solve`, a callable of that
+    signature), and the file is saved after every batch.  Groups already in the file are kept (the notebook appends); a group
+    of the same name is replaced.  A diverged case is reported and not written; one that only reached `max_iterations` is
+    written, like the notebook's.  -> [(Re, n, iterations, status)] with fine.FineSolverBatch's status codes."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    if solve is None:
+        from .fine import run_normal_simulations as solve
+    reynolds_numbers = list(reynolds_numbers)
+    done: Dict[str, tuple] = {}           # group -> (Re, n, fields) of this call, in the order the file gets them
+    record = []
+    for n in mesh_sizes:
+        for a in range(0, len(reynolds_numbers), max_batch):
+            res = reynolds_numbers[a:a + max_batch]
+            results = solve(res, n, n, dt=dt, scheme=scheme, convergence_criteria=convergence_criteria, max_iterations=max_iterations,
+                            bc=bc, max_batch=max_batch, device=device)
+            for Re, (fields, iterations, status) in zip(res, results):
+                record.append((Re, n, int(iterations), int(status)))
+                if status != 2:
+                    done[f"Re{Re}_mesh{n}x{n}"] = (Re, n, fields)
+            # whole-file rewrite: the groups the file had before this call, then this call's
+            w = H5Writer()
+            if os.path.exists(path):
+                _copy_groups(path, w, skip=done)
+            for Re, n_, fields in done.values():
+                append_solution(w, Re, n_, fields, bc_type, case_name, lx=1.0, ly=1.0)
+            w.save(path)
+    return record

@@ -7,13 +7,17 @@ coarse.run_bfs_coarse_simulation), on libsrcfd's float64 device solver (csrc/fin
 reference's MeshParameters fields, so the reference's `extract_centerlines(solver, nx, ny)` works on it unchanged.  The loop is
 srcfd_coarse_solve's; its inner sweeps are Jacobi (momentum) and red-black (pressure) -- tests/fine_solver_spec.py is the
 specification.  No plots; `output_name` writes the HDF5 field file in coarse.save_coarse_fields' layout.
+
+`FineSolverBatch` runs B cases of one mesh in one set of launches (csrc/fine_batch.hip, `srcfd_fine_batch_*`), each with the bits
+of a `FineSolver` of its own; `run_normal_simulations` / `run_bfs_normal_simulations` are `run_normal_simulation` /
+`run_bfs_normal_simulation` for a list of Reynolds numbers on it (the sweeps of sr-simulation-data-creation.ipynb cell 2).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import time
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -167,6 +171,92 @@ class FineSolver:
         save_coarse_fields(path, self.fields(), Re, self.mesh.lx, self.mesh.ly, bfs_step_height=bfs_step_height)
 
 
+class FineSolverBatch:
+    """B cases of one mesh, scheme and case type in one set of launches (srcfd_fine_batch_*): each case computes what a
+    `FineSolver` of its own computes, bit for bit.  `status[i]` is 0 while case i runs (or only the iteration budget ended),
+    1 converged, 2 diverged (non-finite residuals; the other cases go on, nothing is raised)."""
+
+    def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0):
+        self.problems = list(problems)
+        self.n_cases = len(self.problems)
+        self.max_iterations = int(max_iterations)
+        arr = (L.CoarseProblem * max(self.n_cases, 1))(*self.problems)
+        self._h = C.c_void_p()
+        L.check(L.lib.srcfd_fine_batch_create(arr, self.n_cases, int(device), C.byref(self._h)))
+        pb = self.problems[0]
+        self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
+        self.init()
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            L.lib.srcfd_fine_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def shape(self):
+        return (self.n_cases, 3, self.mesh.nx + 2, self.mesh.ny + 2)
+
+    def init(self, Var: Optional[np.ndarray] = None) -> None:
+        """Var None: zero fields; otherwise the interiors of (B, 3, nx+2, ny+2).  Every case runs again from iteration 0."""
+        if Var is None:
+            L.check(L.lib.srcfd_fine_batch_init(self._h, None))
+        else:
+            Var = np.ascontiguousarray(Var, dtype=np.float64)
+            if Var.shape != self.shape:
+                raise ValueError(f"Var must have shape {self.shape}, not {Var.shape}")
+            L.check(L.lib.srcfd_fine_batch_init(self._h, Var.ctypes.data_as(C.c_void_p)))
+        self.residual_history: List[Dict[str, List[float]]] = [{"u": [], "v": [], "p": []} for _ in range(self.n_cases)]
+        self.iterations = np.zeros(self.n_cases, dtype=np.int64)
+        self.status = np.zeros(self.n_cases, dtype=np.int64)
+        self.rms = np.zeros((self.n_cases, 3))
+
+    def run(self, n: int) -> np.ndarray:
+        """Up to n more outer iterations of every running case; returns the per-case iteration counts."""
+        B, rows = self.n_cases, int(n) // 100 + 1
+        it, st = (C.c_int * B)(), (C.c_int * B)()
+        rms, hist = np.zeros((B, 3)), np.zeros((B, rows, 3))
+        before = self.iterations
+        L.check(L.lib.srcfd_fine_batch_run(self._h, int(n), it, st, rms.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p), rows))
+        self.iterations = np.array(list(it), dtype=np.int64)
+        self.status = np.array(list(st), dtype=np.int64)
+        self.rms = rms
+        for i in range(B):
+            for r in hist[i, :self.iterations[i] // 100 - before[i] // 100]:
+                for k, c in enumerate(COMPONENTS):
+                    self.residual_history[i][c].append(float(r[k]))
+        return self.iterations
+
+    def solve(self, max_iterations: Optional[int] = None) -> np.ndarray:
+        """Runs until no case is running or the running ones have done `max_iterations` outer iterations in all."""
+        cap = self.max_iterations if max_iterations is None else int(max_iterations)
+        return self.run(max(0, cap - int(self.iterations.max(initial=0))))
+
+    @property
+    def Var(self) -> np.ndarray:
+        out = np.empty(self.shape)
+        L.check(L.lib.srcfd_fine_batch_get_state(self._h, -1, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def case_var(self, i: int) -> np.ndarray:
+        out = np.empty(self.shape[1:])
+        L.check(L.lib.srcfd_fine_batch_get_state(self._h, int(i), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def fields(self, i: int) -> Dict[str, np.ndarray]:
+        V = self.case_var(i)
+        return {c: V[k, 1:-1, 1:-1].T.copy() for k, c in enumerate(COMPONENTS)}
+
+    def counters(self) -> Dict[str, object]:
+        c = (C.c_int64 * 4)()
+        s = (C.c_int * (3 * self.n_cases))()
+        L.check(L.lib.srcfd_fine_batch_counters(self._h, c, s))
+        return {"momentum_sweeps": c[0], "pressure_sweeps": c[1], "launches": c[2], "host_syncs": c[3],
+                "last_sweeps": [list(s[3 * i:3 * i + 3]) for i in range(self.n_cases)]}
+
+
 def _finish(solver: FineSolver, Re, output_name, suffix, bfs_step_height=None):
     t0 = time.time()
     it = solver.solve()
@@ -196,6 +286,41 @@ def run_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.001, scheme
     """PyCFD_ML_accelerated.py:1126-1184: the same solve from zero fields."""
     s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations)
     return _finish(s, Re, output_name, "_normal")
+
+
+def _per_case(bc, n):
+    """One BC set for every case, or a list with one per case."""
+    if isinstance(bc, (list, tuple)):
+        if len(bc) != n:
+            raise ValueError(f"bc must be one boundary-condition set or a list of {n}, one per Reynolds number")
+        return list(bc)
+    return [bc] * n
+
+
+def _solve_in_batches(problems, max_iterations, max_batch, device):
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    out = []
+    for a in range(0, len(problems), max_batch):
+        b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device)
+        try:
+            b.solve()
+            out += [(b.fields(i), int(b.iterations[i]), int(b.status[i])) for i in range(b.n_cases)]
+        finally:
+            b.close()
+    return out
+
+
+def run_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: float = 0.001, scheme: str = "QUICK",
+                           convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
+                           max_batch: int = 8, device: int = 0) -> list:
+    """`run_normal_simulation` for a list of Reynolds numbers, `max_batch` cases at a time on the batched device solver:
+    a list of (fields, iterations, status) in input order; fields are the (ny, nx) u, v, p, status as FineSolverBatch's.
+    `bc`: one boundary-condition set or a list with one per Reynolds number."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs)]
+    return _solve_in_batches(pbs, max_iterations, max_batch, device)
 
 
 def _model_files(stats_file, encoder_file, decoder_file):
@@ -250,6 +375,18 @@ def run_bfs_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.002, sc
     s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
                    max_iterations)
     return _finish(s, Re, output_name, "_normal", bfs_step_height=step_height)
+
+
+def run_bfs_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: float = 0.002, scheme: str = "UPWIND",
+                               convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
+                               step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                               relaxation_factors: Optional[Dict[str, float]] = None, max_batch: int = 8, device: int = 0) -> list:
+    """`run_bfs_normal_simulation` for a list of Reynolds numbers, batched as `run_normal_simulations`."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
+           for Re, b in zip(reynolds, bcs)]
+    return _solve_in_batches(pbs, max_iterations, max_batch, device)
 
 
 def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re: float, nx: int, ny: int, lr_dim: int = 10,

@@ -1,0 +1,374 @@
+"""The batched fine-mesh solver (csrc/fine_batch.hip, fine.FineSolverBatch) on an MI355X: every case of a batch has the bits of
+its numpy specification (tests/fine_solver_spec.py) and of a single-case FineSolver, whatever the batch size, its position in
+the batch and what its neighbours do -- stop their inner solves at other sweeps, converge earlier, diverge.  Then the
+training-set generator on top of it, end to end."""
+import importlib
+import signal
+
+import numpy as np
+import pytest
+
+from conftest import require_gpu
+import fine_solver_spec as spec
+
+pytestmark = pytest.mark.gpu
+
+RUNNING, CONVERGED, DIVERGED = 0, 1, 2
+CAP = spec.CAP
+_BFS = {"step_height": 1.0, "h": 2.0, "Ub": 1.0}
+_LOOSE = {"u": 1e-2, "v": 1e-2, "p": 1e-2}
+
+
+@pytest.fixture(autouse=True)
+def _time_limit(request):
+    """Every test here runs under its own time limit (each takes a few seconds)."""
+    def _alarm(*_):
+        raise TimeoutError(f"{request.node.name} exceeded its time limit")
+    old = signal.signal(signal.SIGALRM, _alarm)
+    signal.alarm(120)
+    yield
+    signal.alarm(0)
+    signal.signal(signal.SIGALRM, old)
+
+
+@pytest.fixture(scope="module")
+def fine(srcfd):
+    require_gpu(srcfd)
+    return importlib.import_module("sr-for-cfd_amd.fine")
+
+
+@pytest.fixture(scope="module")
+def coarse():
+    return importlib.import_module("sr-for-cfd_amd.coarse")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def _same(a, b):
+    np.testing.assert_array_equal(_bits(a), _bits(b))
+
+
+def _smooth_state(nx, ny, seed):
+    """A seeded, smooth, non-zero state; u changes sign along the right boundary (backflow at a BFS outlet)."""
+    rng = np.random.default_rng(seed)
+    x = (np.arange(1, nx + 1) - 0.5) / nx
+    y = (np.arange(1, ny + 1) - 0.5) / ny
+    X, Y = np.meshgrid(x, y, indexing="ij")
+    var = np.zeros((3, nx + 2, ny + 2))
+    for k in range(3):
+        a, b, c = rng.uniform(0.5, 1.5, 3)
+        ph = rng.uniform(0, np.pi, 2)
+        var[k, 1:-1, 1:-1] = 0.3 * a * np.sin(np.pi * (b * X) + ph[0]) * np.cos(np.pi * (c * Y) + ph[1]) + 0.05 * k
+    return var
+
+
+# ---------------------------------------------------------------------------------------------- 1: staggered stopping
+def _staggered_problems(fine, coarse):
+    """12x10, QUICK, dt 0.01, tolerances 1e-2, from zero: alone, the spec converges at 211, 326, 315 and 822."""
+    return [fine.problem(Re, 12, 10, 1.0, 1.0, 0.01, "QUICK", _LOOSE, bc) for Re, bc in
+            ((50.0, coarse.LDC_SINGLE_LID), (100.0, coarse.LDC_DOUBLE_LID), (100.0, coarse.LDC_SINGLE_LID), (400.0, coarse.LDC_DOUBLE_LID))]
+
+
+@pytest.fixture(scope="module")
+def staggered(fine, coarse):
+    """Per case: the spec run to convergence, with Var and rms kept at the iterations the tests look at."""
+    out = []
+    for pb in _staggered_problems(fine, coarse):
+        sp = spec.from_problem(pb)
+        sp.init()
+        snap = {}
+        for stop in (30, 400, 100000):
+            sp.run(stop - sp.count)
+            snap[sp.count] = (sp.Var.copy(), sp.rms.copy(), len(sp.history))
+        assert sp.converged
+        out.append((sp, snap))
+    return out
+
+
+def test_staggered_cases_equal_the_specification_bit_for_bit(fine, coarse, staggered):
+    assert [sp.count for sp, _ in staggered] == [211, 326, 315, 822]
+    # the cases stop every inner solve at different sweeps, and cases 0 and 1 end the u solve on different parities
+    assert [sp.sweeps[49] for sp, _ in staggered] == [[5, 4, 61], [4, 4, 69], [4, 4, 59], [3, 3, 47]]
+    for which in range(3):
+        assert len({sp.sweeps[49][which] for sp, _ in staggered}) >= 2
+    assert staggered[0][0].sweeps[49][0] % 2 != staggered[1][0].sweeps[49][0] % 2
+    b = fine.FineSolverBatch(_staggered_problems(fine, coarse))
+    assert b.Var.shape == (4, 3, 14, 12)
+    assert b.run(400).tolist() == [211, 326, 315, 400]
+    assert b.status.tolist() == [CONVERGED, CONVERGED, CONVERGED, RUNNING]
+    assert b.iterations.tolist() == [211, 326, 315, 400]
+
+    def check(i, at):
+        sp, snap = staggered[i]
+        var, rms, n_hist = snap[at]
+        _same(b.Var[i], var)
+        _same(b.case_var(i), var)
+        _same(b.rms[i], rms)
+        assert b.counters()["last_sweeps"][i] == sp.sweeps[at - 1]
+        hist = np.array([b.residual_history[i][c] for c in "uvp"]).T.reshape(-1, 3)
+        _same(hist, np.array(sp.history[:n_hist]).reshape(-1, 3))
+        assert n_hist == at // 100
+        np.testing.assert_array_equal(b.fields(i)["v"], var[1, 1:-1, 1:-1].T)
+
+    for i, at in enumerate((211, 326, 315, 400)):
+        check(i, at)
+    # the second run finishes case 3 and leaves the converged cases and their counters' entries untouched
+    assert b.run(1000).tolist() == [211, 326, 315, 822]
+    assert b.status.tolist() == [CONVERGED] * 4
+    for i, at in enumerate((211, 326, 315, 822)):
+        check(i, at)
+    # nothing is running: a further run does nothing
+    cnt = b.counters()
+    assert b.run(10).tolist() == [211, 326, 315, 822] and b.counters() == cnt
+    b.close()
+
+
+def test_each_case_stops_its_inner_solves_at_its_own_sweep(fine, coarse, staggered):
+    b = fine.FineSolverBatch(_staggered_problems(fine, coarse))
+    for n in range(1, 61):
+        assert b.run(1).tolist() == [n] * 4
+        assert b.counters()["last_sweeps"] == [sp.sweeps[n - 1] for sp, _ in staggered], n
+    b.close()
+
+
+# ---------------------------------------------------------------------------------------------- 2: divergence
+def test_a_diverging_case_is_frozen_and_the_others_do_not_notice(fine, coarse):
+    """40x30 UPWIND Re 100 double lid from zero at dt 0.001, 0.1, 0.01: alone, dt 0.1 is finite at iteration 1 and not at 2."""
+    pbs = [fine.problem(100.0, 40, 30, 1.0, 1.0, dt, "UPWIND", None, coarse.LDC_DOUBLE_LID) for dt in (0.001, 0.1, 0.01)]
+    sps = [spec.from_problem(pb) for pb in pbs]
+    for i, sp in enumerate(sps):
+        sp.init()
+        if i == 1:
+            sp.run(1)
+            with pytest.raises(ValueError, match="NaN/Inf"), np.errstate(over="ignore", invalid="ignore"):
+                sp.run(1)
+        else:
+            sp.run(4)
+    assert sps[0].sweeps == [[4, 1, 257], [4, 2, 322], [4, 2, 361], [4, 2, 388]]
+    assert sps[1].sweeps == [[33, 1, 280], [CAP] * 3]
+    assert sps[2].sweeps == [[8, 1, 260], [8, 4, 325], [8, 5, 382], [7, 5, 443]]
+    b = fine.FineSolverBatch(pbs)
+    sweeps = []
+    for n in range(1, 5):
+        b.run(1)                             # raises nothing
+        sweeps.append(b.counters()["last_sweeps"])
+    assert b.status.tolist() == [RUNNING, DIVERGED, RUNNING] and b.iterations.tolist() == [4, 2, 4]
+    for i in (0, 2):
+        assert [s[i] for s in sweeps] == sps[i].sweeps
+        _same(b.Var[i], sps[i].Var)
+        _same(b.rms[i], sps[i].rms)
+    assert [s[1] for s in sweeps] == [[33, 1, 280]] + [[CAP] * 3] * 3
+    assert not np.isfinite(b.rms[1]).all()
+    # one call over the same four iterations gives the same
+    c = fine.FineSolverBatch(pbs)
+    assert c.run(4).tolist() == [4, 2, 4] and c.status.tolist() == [RUNNING, DIVERGED, RUNNING]
+    _same(c.Var[[0, 2]], b.Var[[0, 2]])
+    c.close()
+    # init clears the diverged state
+    b.init()
+    assert b.status.tolist() == [RUNNING] * 3 and b.run(1).tolist() == [1, 1, 1]
+    assert b.counters()["last_sweeps"] == [sp.sweeps[0] for sp in sps]
+    assert b.status.tolist() == [RUNNING] * 3
+    b.close()
+
+
+# ---------------------------------------------------------------------------------------------- 3: kernel edges against FineSolver
+EDGES = {
+    # a thread takes cells j, j + 256 of a row; sum_partials adds partials q, q + 256 (pressure: also q + 512); two BC workgroups
+    "ldc400_quick": (lambda f, c: [f.problem(Re, 400, 400, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID) for Re in (400.0, 1000.0)], 2),
+    # ny > 512: a thread takes 2 cells of one colour in a row; odd nx, even ny
+    "tall_131x530": (lambda f, c: [f.problem(Re, 131, 530, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_SINGLE_LID) for Re in (1000.0, 300.0)], 2),
+    # nx > 256 with ny < 256: multi-pass sum_partials and convergence_check; the second BC workgroup along i only
+    "wide_301x61": (lambda f, c: [f.problem(400.0, 301, 61, 1.0, 1.0, dt, "UPWIND", None, c.LDC_DOUBLE_LID) for dt in (0.001, 0.002)], 2),
+    # the BFS inlet, under-relaxation with per-case factors
+    "bfs_upwind": (lambda f, c: [f.problem(Re, 37, 29, 10.0, 3.0, 0.002, "UPWIND", None, None, bfs=_BFS, relaxation_factors=rf)
+                                 for Re, rf in ((200.0, {"u": 0.5, "v": 0.5, "p": 0.2}), (400.0, {"u": 0.7, "v": 0.6, "p": 0.3}))], 3),
+    "one_case": (lambda f, c: [f.problem(1000.0, 37, 29, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID)], 3),
+}
+
+
+def _solo_trace(fine, pb, var0, iterations):
+    s = fine.FineSolver(pb)
+    s.init(var0)
+    trace = []
+    for _ in range(iterations):
+        s.run(1)
+        trace.append((_bits(s.rms).tolist(), s.counters()["last_sweeps"]))
+    var = s.Var
+    s.close()
+    return trace, var
+
+
+@pytest.mark.parametrize("case", list(EDGES))
+def test_each_case_equals_a_single_case_solver(fine, coarse, case):
+    make, iterations = EDGES[case]
+    pbs = make(fine, coarse)
+    starts = np.stack([_smooth_state(pb.nx, pb.ny, seed=7 + i) for i, pb in enumerate(pbs)])
+    b = fine.FineSolverBatch(pbs)
+    b.init(starts)
+    got = [[] for _ in pbs]
+    for n in range(iterations):
+        b.run(1)
+        sw = b.counters()["last_sweeps"]
+        for i in range(len(pbs)):
+            got[i].append((_bits(b.rms[i]).tolist(), sw[i]))
+    assert b.status.tolist() == [RUNNING] * len(pbs)
+    var = b.Var
+    b.close()
+    for i, pb in enumerate(pbs):
+        trace, solo_var = _solo_trace(fine, pb, starts[i], iterations)
+        assert got[i] == trace, (case, i)
+        _same(var[i], solo_var)
+    if len(pbs) > 1:
+        assert got[0] != got[1]
+
+
+# ---------------------------------------------------------------------------------------------- 4: independence of B and position
+def test_bits_do_not_depend_on_batch_size_or_position(fine, coarse, staggered):
+    pbs = _staggered_problems(fine, coarse)
+    want = staggered[1][1][30]
+    other = fine.problem(1000.0, 12, 10, 1.0, 1.0, 0.002, "QUICK", _LOOSE, coarse.LDC_SINGLE_LID)
+    for problems, at in (([pbs[1]], 0), ([pbs[1], pbs[3]], 0), ([pbs[0], other, pbs[2], pbs[1], pbs[3]], 3)):
+        b = fine.FineSolverBatch(problems)
+        b.run(30)
+        _same(b.case_var(at), want[0])
+        _same(b.rms[at], want[1])
+        assert b.counters()["last_sweeps"][at] == staggered[1][0].sweeps[29]
+        b.close()
+
+
+def test_live_batches_and_a_live_solver_do_not_share_state(fine, coarse):
+    """Alternating outer iterations of two batches and a FineSolver equal each one's run on its own."""
+    pbs = _staggered_problems(fine, coarse)
+    big = [fine.problem(Re, 40, 30, 1.0, 1.0, 0.05, "QUICK", None, coarse.LDC_DOUBLE_LID) for Re in (100.0, 200.0)]
+    start = _smooth_state(40, 30, seed=7)
+    make = {"a": lambda: fine.FineSolverBatch(pbs[:2]), "b": lambda: fine.FineSolverBatch(big), "s": lambda: fine.FineSolver(big[0])}
+    alone = {}
+    for name, mk in make.items():
+        s = mk()
+        if name == "s":
+            s.init(start)
+        s.run(4)
+        alone[name] = (s.Var, np.array(s.rms))
+        s.close()
+    live = {name: mk() for name, mk in make.items()}
+    live["s"].init(start)
+    for _ in range(4):
+        for s in live.values():
+            s.run(1)
+    for name, s in live.items():
+        _same(s.Var, alone[name][0])
+        _same(np.array(s.rms), alone[name][1])
+        s.close()
+
+
+# ---------------------------------------------------------------------------------------------- 5: host synchronisations
+def _expected_syncs(sweeps):
+    """Host synchronisations of the outer iterations with these [u, v, p] sweep counts: one per chunk of an inner solve and one
+    at the end of the iteration.  The first chunk is the previous solve's count n + n/8 + 2 (16, 16, cap at first), later ones
+    double; the exit rule of a solve of n sweeps fires in launch n, so the solve ends with the chunk that contains it."""
+    predict, syncs = [16, 16, CAP], 0
+    for per_iter in sweeps:
+        for which, n in enumerate(per_iter):
+            done, chunk = 0, predict[which]
+            while True:
+                chunk = min(chunk, CAP - done)
+                done += chunk
+                syncs += 1
+                if done > n or done >= CAP:
+                    break
+                chunk = 8 if chunk < 8 else 2 * chunk
+            predict[which] = min(CAP, n + 2 + n // 8)
+        syncs += 1
+    return syncs
+
+
+def test_host_synchronisations_do_not_grow_with_the_batch(fine, coarse):
+    pb = EDGES["bfs_upwind"][0](fine, coarse)[0]
+    start = _smooth_state(pb.nx, pb.ny, seed=7)
+    cnt = {}
+    for B in (1, 4):
+        b = fine.FineSolverBatch([pb] * B)
+        b.init(np.stack([start] * B))
+        base = b.counters()
+        sweeps = []
+        for _ in range(5):
+            b.run(1)
+            sweeps.append(b.counters()["last_sweeps"])
+        c = b.counters()
+        cnt[B] = ({k: c[k] - base[k] for k in ("momentum_sweeps", "pressure_sweeps", "launches", "host_syncs")}, sweeps)
+        b.close()
+    # identical cases replicated: the same sweeps per case and iteration, so the same launches and the same synchronisations
+    assert all(per_iter == [per_iter[0]] * 4 for per_iter in cnt[4][1])
+    assert [s[0] for s in cnt[4][1]] == [s[0] for s in cnt[1][1]]
+    assert cnt[4][0] == cnt[1][0], cnt
+    assert cnt[4][0]["host_syncs"] == _expected_syncs([s[0] for s in cnt[4][1]]), cnt
+
+
+# ---------------------------------------------------------------------------------------------- 6: refusals
+def test_refusals(fine, coarse):
+    ok = lambda **kw: fine.problem(kw.get("Re", 100.0), kw.get("nx", 12), kw.get("ny", 10), 1.0, 1.0, 0.01, kw.get("scheme", "QUICK"),
+                                   None, None, bfs=kw.get("bfs"))
+    for pbs, text in (([ok(), ok(), ok(nx=13)], r"case 2: nx differs"),
+                      ([ok(), ok(ny=11)], r"case 1: ny differs"),
+                      ([ok(), ok(), ok(), ok(scheme="UPWIND")], r"case 3: scheme differs"),
+                      ([ok(), ok(bfs=_BFS)], r"case 1: case_type differs"),
+                      ([ok(), ok(Re=-1.0)], r"case 1: bad problem"),
+                      ([], r"n_cases 0 "),
+                      ([ok()] * 65, r"n_cases 65 ")):
+        with pytest.raises(ValueError, match="srcfd_fine_batch_create: " + text):
+            fine.FineSolverBatch(pbs)
+    b = fine.FineSolverBatch([ok(), ok(Re=200.0)])
+    for shape in ((3, 14, 12), (1, 3, 14, 12), (2, 3, 12, 14), (3, 3, 14, 12)):
+        with pytest.raises(ValueError, match=r"shape \(2, 3, 14, 12\)"):
+            b.init(np.zeros(shape))
+    assert b.run(2).tolist() == [2, 2]       # still usable
+    b.close()
+    with pytest.raises(ValueError, match="one per Reynolds number"):
+        fine.run_normal_simulations([100, 200], 12, 10, bc=[coarse.LDC_DOUBLE_LID])
+
+
+# ---------------------------------------------------------------------------------------------- 7: the generator, end to end
+def test_generator_end_to_end(fine, coarse, tmp_path):
+    datasets = importlib.import_module("sr-for-cfd_amd.datasets")
+    h5 = importlib.import_module("sr-for-cfd_amd.h5")
+    path = str(tmp_path / "simulation_result_double_lid.h5")
+    rec = datasets.generate_simulation_file(path, reynolds_numbers=[50, 100], mesh_sizes=(6, 12), dt=0.01, convergence_criteria=_LOOSE,
+                                            max_batch=2)
+    assert rec == [(50, 6, 220, CONVERGED), (100, 6, 356, CONVERGED), (50, 12, 200, CONVERGED), (100, 12, 328, CONVERGED)]
+    x_lr, x_hr, res, comps, bcs = datasets.load_paired_reynolds_multi([path], 6, 12)
+    assert x_lr.shape == (6, 6, 6, 1) and x_hr.shape == (6, 12, 12, 1)
+    assert res.tolist() == [50] * 3 + [100] * 3 and comps.tolist() == list("uvp") * 2 and set(bcs) == {"double_lid(u_top=1,u_bottom=1)"}
+    n = 0
+    for Re in (50, 100):
+        solo = {}
+        for m in (6, 12):
+            s = fine.FineSolver(fine.problem(Re, m, m, 1.0, 1.0, 0.01, "QUICK", _LOOSE, coarse.LDC_DOUBLE_LID))
+            s.solve()
+            solo[m] = s.fields()
+            s.close()
+        for c in "uvp":
+            np.testing.assert_array_equal(x_lr[n, ..., 0], solo[6][c].astype(np.float32))
+            np.testing.assert_array_equal(x_hr[n, ..., 0], solo[12][c].astype(np.float32))
+            n += 1
+    with h5.H5File(path) as f:
+        first = {g: {d: f.read(f"{g}/{d}") for d in f.keys(g)} for g in f.keys("/")}
+    assert len(first) == 4
+    # a second call keeps the first four groups (max_batch 1: one case per batch; the spec converges at 467 and 442)
+    rec = datasets.generate_simulation_file(path, reynolds_numbers=[150], mesh_sizes=(6, 12), dt=0.01, convergence_criteria=_LOOSE, max_batch=1)
+    assert rec == [(150, 6, 467, CONVERGED), (150, 12, 442, CONVERGED)]
+    with h5.H5File(path) as f:
+        assert sorted(f.keys("/")) == sorted(list(first) + ["Re150_mesh6x6", "Re150_mesh12x12"])
+        for g, data in first.items():
+            for d, v in data.items():
+                np.testing.assert_array_equal(f.read(f"{g}/{d}"), v)
+    assert datasets.load_paired_reynolds_multi([path], 6, 12)[0].shape[0] == 9
+    # the drop-in returns the same fields, in input order, however the list is cut
+    a = fine.run_normal_simulations([100, 50, 150], 6, 6, dt=0.01, convergence_criteria=_LOOSE, bc=coarse.LDC_DOUBLE_LID, max_batch=2)
+    assert [(it, st) for _, it, st in a] == [(356, CONVERGED), (220, CONVERGED), (rec[0][2], CONVERGED)]
+    with h5.H5File(path) as f:
+        np.testing.assert_array_equal(a[1][0]["u"].flatten(), f.read("Re50_mesh6x6/u"))
+    r = fine.run_bfs_normal_simulations([200, 400], 40, 20, max_iterations=2)
+    assert [(it, st) for _, it, st in r] == [(2, RUNNING)] * 2 and r[0][0]["u"].shape == (20, 40)

@@ -5,6 +5,13 @@ us per sweep launch against the 1.45 us dependent-launch floor, and srcfd_coarse
 2 outer iterations as the host comparison.
 
     python tools/fine_solver_bench.py [--iters N] [--warmup W] [--n 400]
+
+With --batch 1,2,4,8,16 it times the batched solver (srcfd_fine_batch_*) instead: per batch size B, B cavities (QUICK, double
+lid, Re spread evenly over 100..800, from zero) as one batch, and in the same process the same cases one after the other on the
+unchanged single-case solver; --repeats times each, on fresh handles.  One JSON line: per B and repeat the ms per outer
+iteration of the batch and of the B sequential solves, and from the batch's counters the us per sweep launch and host_syncs.
+
+    python tools/fine_solver_bench.py --batch 1,2,4,8,16 --iters 10 --warmup 2 [--repeats 3]
 """
 import argparse
 import importlib
@@ -18,15 +25,64 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _timed(solver, warmup, iters):
+    solver.run(warmup)
+    c0 = solver.counters()
+    t0 = time.perf_counter()
+    solver.run(iters)
+    dt_s = time.perf_counter() - t0
+    c1 = solver.counters()
+    return dt_s, {k: c1[k] - c0[k] for k in ("momentum_sweeps", "pressure_sweeps", "launches", "host_syncs")}
+
+
+def batch_bench(a, fine, coarse):
+    n = a.n
+    out = {"mesh": f"{n}x{n}", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "floor_us_per_launch": 1.45, "batch": {}}
+    for B in [int(b) for b in a.batch.split(",")]:
+        res = [float(r) for r in np.linspace(100.0, 800.0, B)]
+        pbs = [fine.problem(Re, n, n, 1.0, 1.0, 0.001, "QUICK", None, coarse.LDC_DOUBLE_LID) for Re in res]
+        rows = []
+        for _ in range(a.repeats):
+            b = fine.FineSolverBatch(pbs)
+            dt_s, c = _timed(b, a.warmup, a.iters)
+            b.close()
+            seq_s, seq_launches = 0.0, 0
+            for pb in pbs:
+                s = fine.FineSolver(pb)
+                one_s, c1 = _timed(s, a.warmup, a.iters)
+                s.close()
+                seq_s += one_s
+                seq_launches += c1["momentum_sweeps"] + 2 * c1["pressure_sweeps"]
+            sweep_launches = c["momentum_sweeps"] + 2 * c["pressure_sweeps"]
+            rows.append({
+                "batch_ms_per_outer_iteration": round(1e3 * dt_s / a.iters, 3),
+                "batch_ms_per_outer_iteration_per_case": round(1e3 * dt_s / a.iters / B, 3),
+                "sequential_ms_per_outer_iteration": round(1e3 * seq_s / a.iters, 3),
+                "batch_over_sequential": round(dt_s / seq_s, 4),
+                "sweep_launches_executed": sweep_launches,
+                "sequential_sweep_launches_executed": seq_launches,
+                "us_per_sweep_launch": round(1e6 * dt_s / max(1, sweep_launches), 3),
+                "sequential_us_per_sweep_launch": round(1e6 * seq_s / max(1, seq_launches), 3),
+                "launches_issued": c["launches"],
+                "host_syncs": c["host_syncs"],
+            })
+        out["batch"][str(B)] = {"reynolds": res, "repeats": rows}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=400)
     ap.add_argument("--host-iters", type=int, default=2)
+    ap.add_argument("--batch", default=None, help="comma-separated batch sizes: time the batched solver against sequential solves")
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
     fine = importlib.import_module("sr-for-cfd_amd.fine")
     coarse = importlib.import_module("sr-for-cfd_amd.coarse")
+    if a.batch:
+        return batch_bench(a, fine, coarse)
     n = a.n
     configs = {
         "ldc_quick_re1000_double_lid": dict(Re=1000.0, lx=1.0, ly=1.0, dt=0.001, scheme="QUICK", bc=coarse.LDC_DOUBLE_LID, bfs=None),
