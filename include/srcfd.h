@@ -330,8 +330,9 @@ int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], 
 /* ---- batches of fine-mesh cases (the sweeps that make training data) ---------------------------------
  * Replaces the loop over Reynolds numbers of sr-simulation-data-creation.ipynb cell 2: n_cases problems with one nx, ny, scheme
  * and case_type (everything else may differ per case) advance together, the case index as the second grid dimension of every
- * launch (csrc/fine_batch.hip).  Each case computes what a srcfd_fine_solver of its own computes, bit for bit, whatever the
- * batch size and its position in it.  A case that converges, or whose residuals stop being finite, is frozen; the others go on. */
+ * launch (csrc/fine_solver.hip; a srcfd_fine_solver is a batch of one).  Each case computes what a srcfd_fine_solver of its own
+ * computes, bit for bit, whatever the batch size and its position in it.  A case that converges, or whose residuals stop being
+ * finite, is frozen; the others go on. */
 typedef struct srcfd_fine_batch srcfd_fine_batch;
 #define SRCFD_CASE_RUNNING 0   /* also: stopped only because run()'s iteration budget ended; resumable */
 #define SRCFD_CASE_CONVERGED 1

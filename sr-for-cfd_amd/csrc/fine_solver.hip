@@ -1,4 +1,6 @@
-// Fine-mesh incompressible solver on the device (float64): the solve the SR warm start is for.
+// Fine-mesh incompressible solver on the device (float64): the solve the SR warm start is for, for one case
+// (C ABI srcfd_fine_solver_*) or for B cases of one mesh, scheme and case type in one set of launches (srcfd_fine_batch_*).
+// There is one solver: a single case is a batch of one.
 //
 // The same outer loop as srcfd_coarse_solve (coarse_solver.cpp; PyCFD_ML_accelerated.py:433-505, bfs_ml_accelerated.py:626-707)
 // with the same expressions in the same operation order, so that with -ffp-contract=off every cell update rounds as the host's
@@ -13,7 +15,20 @@
 //
 // Loop control: one launch per sweep (pressure: per colour).  Each sweep launch first reduces the previous sweep's partials and
 // returns at once when the inner solve has stopped, so the host enqueues sweeps in chunks sized from the previous solve's count and
-// reads one small status block per chunk -- never per sweep.  See DESIGN.md, "Fine-mesh solve on the device".
+// reads the status blocks once per chunk -- never per sweep.  See DESIGN.md, "Fine-mesh solve on the device".
+//
+// Batches.  A Reynolds sweep of single cases leaves the device almost empty: one workgroup per mesh row and about 2 000 dependent
+// launches per outer iteration, whose cost is the launch boundary and not the cell arithmetic.  The cases of a sweep share the
+// mesh and the launch sequence, so they share the launches: blockIdx.y is the case, and within a case the thread-to-cell mapping,
+// the expressions and the reductions do not know about the batch.  A case's bits therefore depend neither on B nor on its
+// neighbours.
+//
+// Per-case control.  Every sweep launch covers all cases with the same sweep index m.  A case's workgroups return at once when
+// that case's own stop flag is set, or when the case is frozen (converged or diverged: Status::state != 0), so each case ends
+// each inner solve at its own sweep and momentum_finish picks Jb or Var by the case's own count.  The host enqueues chunks
+// predicted from the largest count among the live cases, reads all B status blocks in one copy per chunk, and ends the solve
+// when every live case has stopped: host synchronisations per outer iteration do not grow with B.  The live cases wait for the
+// slowest inner solve of the batch -- the lock-step cost, DESIGN.md section 2c.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,7 +38,6 @@
 #include <vector>
 
 #include "engine.h"
-#include "fine_device.h"
 
 namespace srcfd {
 
@@ -33,8 +47,114 @@ int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const fl
 
 namespace {
 
+constexpr int NT = 256;            // threads per workgroup; one workgroup per mesh row i
+constexpr int SWEEP_CAP = 1000;    // inner sweeps per solve (PyCFD_ML_accelerated.py:251, 299)
+constexpr double INNER_TOL = 1e-6;
+constexpr int MAX_CASES = 64;      // keeps the per-chunk status read small
+
+struct Status {      // one per case; written by the kernels with plain stores, read by the host once per chunk
+  int m_sweeps, m_stop;    // current momentum solve: sweeps executed, exit rule fired
+  int p_sweeps, p_stop;    // current pressure solve
+  int state;               // SRCFD_CASE_*, a case that is not RUNNING is frozen
+  int pad;
+  double rms[3];
+};
+
+struct Bc {
+  int type[4];
+  double value[4];
+  int bfs;
+  double step_h, h, Ub;
+};
+
+struct CaseP {       // what may differ between the cases of a batch
+  double dx, dy, volp, dt, rho, nu;
+  double tol[3], relax[3];
+  Bc bc[3];
+};
+
+struct BDev {        // the kernels' argument: the batch
+  int nx, ny, sx, sy;
+  size_t stride;     // doubles per case: Var, Old, Jb (3 planes each), Ff (4), rhs (1), partials (9 nx)
+  double* base;
+  const CaseP* cp;
+  Status* st;
+};
+constexpr size_t case_doubles(int nx, int ny) { return (size_t)14 * (nx + 2) * (ny + 2) + (size_t)9 * nx; }
+
+struct Dev {         // one case's view of it (case_dev)
+  int nx, ny, sx, sy;
+  double dx, dy, volp, dt, rho, nu;
+  double *Var, *Old, *Ff, *Jb, *rhs, *part;
+  Status* st;
+};
+
+__device__ __forceinline__ Dev case_dev(const BDev& b, int c) {
+  const CaseP& p = b.cp[c];
+  Dev g;
+  g.nx = b.nx; g.ny = b.ny; g.sx = b.sx; g.sy = b.sy;
+  g.dx = p.dx; g.dy = p.dy; g.volp = p.volp; g.dt = p.dt; g.rho = p.rho; g.nu = p.nu;
+  double* f = b.base + (size_t)c * b.stride;
+  const size_t sx = (size_t)b.sx;
+  g.Var = f;
+  g.Old = f + 3 * sx;
+  g.Jb = f + 6 * sx;
+  g.Ff = f + 9 * sx;
+  g.rhs = f + 13 * sx;
+  g.part = f + 14 * sx;
+  g.st = b.st + c;
+  return g;
+}
+__device__ __forceinline__ bool frozen(const BDev& b) { return b.st[blockIdx.y].state != SRCFD_CASE_RUNNING; }
+
+// partials: [0, 2nx) momentum, by sweep parity; [2nx, 6nx) pressure, [parity][colour][row]; [6nx, 9nx) outer residuals [k][row]
+__device__ __forceinline__ double* mom_part(const Dev& g, int parity) { return g.part + (size_t)parity * g.nx; }
+__device__ __forceinline__ double* p_part(const Dev& g, int parity) { return g.part + (size_t)(2 + 2 * parity) * g.nx; }
+__device__ __forceinline__ double* res_part(const Dev& g) { return g.part + (size_t)6 * g.nx; }
+
+// Fixed-order workgroup sum: thread t's own sequential sum v, then a halving tree lds[t] += lds[t + s], s = 128 .. 1.
+__device__ double block_sum(double v, double* lds) {
+  const int t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (t < s) lds[t] = lds[t] + lds[t + s];
+    __syncthreads();
+  }
+  const double r = lds[0];
+  __syncthreads();
+  return r;
+}
+// Sum of n partials: thread t adds p[t], p[t + 256], ... in order, then block_sum.
+__device__ double sum_partials(const double* p, int n, double* lds) {
+  double a = 0.0;
+  for (int q = threadIdx.x; q < n; q += NT) a = a + p[q];
+  return block_sum(a, lds);
+}
+__device__ __forceinline__ int uniform_flag(const int* f, int* lds_flag) {
+  if (threadIdx.x == 0) *lds_flag = *(const volatile int*)f;
+  __syncthreads();
+  const int v = *lds_flag;
+  __syncthreads();
+  return v;
+}
+
+__device__ __forceinline__ double at(const Dev& g, const double* A, int k, int i, int j) { return A[(size_t)k * g.sx + (size_t)i * g.sy + j]; }
+// Grid::vw: negative indices wrap per axis, indices past the end run on in the flat (3, nx+2, ny+2) array, clamped at its end
+__device__ __forceinline__ double atw(const Dev& g, const double* A, int k, int i, int j) {
+  if (i < 0) i += g.nx + 2;
+  if (j < 0) j += g.ny + 2;
+  size_t idx = (size_t)k * g.sx + (size_t)i * g.sy + j;
+  const size_t n = (size_t)3 * g.sx;
+  if (idx >= n) idx = n - 1;
+  return A[idx];
+}
+
 // ---------------------------------------------------------------- boundary conditions, apply_bc + apply_bfs_inlet of plane k
-__global__ void __launch_bounds__(NT) bc_kernel(Dev g, int k, Bc b) {
+__global__ void __launch_bounds__(NT) bc_kernel(BDev bd, int k) {
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
+  const Bc& b = bd.cp[blockIdx.y].bc[k];
   const int t = blockIdx.x * NT + threadIdx.x + 1;
   double* V = g.Var + (size_t)k * g.sx;
   if (t <= g.ny) {
@@ -66,7 +186,7 @@ __global__ void __launch_bounds__(NT) bc_kernel(Dev g, int k, Bc b) {
 }
 
 // ---------------------------------------------------------------- element-wise passes over the interior (one thread per cell)
-__device__ __forceinline__ bool interior(const Dev& g, int& i, int& j) {
+__device__ __forceinline__ bool interior(const BDev& g, int& i, int& j) {
   const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
   if (c >= (int64_t)g.nx * g.ny) return false;
   i = (int)(c / g.ny) + 1;
@@ -74,9 +194,10 @@ __device__ __forceinline__ bool interior(const Dev& g, int& i, int& j) {
   return true;
 }
 
-__global__ void __launch_bounds__(NT) linear_interpolation(Dev g) {   // PyCFD_ML_accelerated.py:148-155
+__global__ void __launch_bounds__(NT) linear_interpolation(BDev bd) {   // PyCFD_ML_accelerated.py:148-155
   int i, j;
-  if (!interior(g, i, j)) return;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   const double* V = g.Var;
   double* F = g.Ff;
   const size_t c = (size_t)i * g.sy + j;
@@ -86,37 +207,44 @@ __global__ void __launch_bounds__(NT) linear_interpolation(Dev g) {   // PyCFD_M
   F[3 * (size_t)g.sx + c] = -(at(g, V, 1, i, j) + at(g, V, 1, i, j - 1)) * g.dx * 0.5;
 }
 
-// Ends a momentum solve: the result sits in Jb when the sweep count is odd; BFS under-relaxes against Old (bfs...:371-375).
-__global__ void __launch_bounds__(NT) momentum_finish(Dev g, int k, int relax, double alpha) {
+// Ends a momentum solve: the result sits in Jb when the case's own sweep count is odd; BFS under-relaxes against Old
+// (bfs...:371-375).
+__global__ void __launch_bounds__(NT) momentum_finish(BDev bd, int k, int relax) {
   int i, j;
-  if (!interior(g, i, j)) return;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   const size_t c = (size_t)k * g.sx + (size_t)i * g.sy + j;
   double v = (g.st->m_sweeps & 1) ? g.Jb[c] : g.Var[c];
   if (relax) {
+    const double alpha = bd.cp[blockIdx.y].relax[k];
     const double o = g.Old[c];
     v = o + alpha * (v - o);
   }
   g.Var[c] = v;
 }
 
-__global__ void __launch_bounds__(NT) under_relax(Dev g, int k, double alpha) {
+__global__ void __launch_bounds__(NT) under_relax(BDev bd, int k) {
   int i, j;
-  if (!interior(g, i, j)) return;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
+  const double alpha = bd.cp[blockIdx.y].relax[k];
   const size_t c = (size_t)k * g.sx + (size_t)i * g.sy + j;
   const double o = g.Old[c];
   g.Var[c] = o + alpha * (g.Var[c] - o);
 }
 
-__global__ void __launch_bounds__(NT) pressure_rhs(Dev g) {   // the RHS of solve_pressure: Ff is constant inside the solve
+__global__ void __launch_bounds__(NT) pressure_rhs(BDev bd) {   // the RHS of solve_pressure: Ff is constant inside the solve
   int i, j;
-  if (!interior(g, i, j)) return;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   const size_t c = (size_t)i * g.sy + j;
   g.rhs[c] = g.rho / g.dt * (g.Ff[c] + g.Ff[g.sx + c] + g.Ff[2 * (size_t)g.sx + c] + g.Ff[3 * (size_t)g.sx + c]);
 }
 
-__global__ void __launch_bounds__(NT) update_flux(Dev g) {   // PyCFD_ML_accelerated.py:242-249
+__global__ void __launch_bounds__(NT) update_flux(BDev bd) {   // PyCFD_ML_accelerated.py:242-249
   int i, j;
-  if (!interior(g, i, j)) return;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   const double* P = g.Var + 2 * (size_t)g.sx;
   double* F = g.Ff;
   const size_t c = (size_t)i * g.sy + j;
@@ -127,25 +255,31 @@ __global__ void __launch_bounds__(NT) update_flux(Dev g) {   // PyCFD_ML_acceler
   F[3 * (size_t)g.sx + c] += -g.dt / g.rho * (P[c - 1] - p) * g.dx / g.dy;
 }
 
-__global__ void __launch_bounds__(NT) copy_f64(double* __restrict__ dst, const double* __restrict__ src, int64_t n, const int* skip_if) {
-  if (skip_if && *skip_if) return;
+// The three planes at `dst` = those at `src` (offsets in a case's block) for every case that is not frozen: the Jb copy before a
+// momentum solve, and Old = Var, which a case that has just converged or diverged skips.
+__global__ void __launch_bounds__(NT) copy_planes_kernel(BDev bd, size_t dst, size_t src) {
+  if (frozen(bd)) return;
   const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
-  if (c < n) dst[c] = src[c];
+  double* f = bd.base + (size_t)blockIdx.y * bd.stride;
+  if (c < 3 * (int64_t)bd.sx) f[dst + c] = f[src + c];
 }
 
-// Var = 0 except the interior, which comes from `src` (same layout); corners and ghosts are left 0 for the BC pass.
-__global__ void __launch_bounds__(NT) take_interior(Dev g, const double* __restrict__ src) {
+// Var = 0 except the interior, which comes from Jb (where init staged the host array); ghosts and corners are left 0 for the BCs.
+__global__ void __launch_bounds__(NT) take_interior(BDev bd) {
   const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
-  if (c >= 3 * (int64_t)g.sx) return;
-  const int r = (int)(c % g.sx), i = r / g.sy, j = r - i * g.sy;
-  g.Var[c] = (i >= 1 && i <= g.nx && j >= 1 && j <= g.ny) ? src[c] : 0.0;
+  if (c >= 3 * (int64_t)bd.sx) return;
+  double* f = bd.base + (size_t)blockIdx.y * bd.stride;
+  const int r = (int)(c % bd.sx), i = r / bd.sy, j = r - i * bd.sy;
+  f[c] = (i >= 1 && i <= bd.nx && j >= 1 && j <= bd.ny) ? f[6 * (size_t)bd.sx + c] : 0.0;
 }
 
-// ---------------------------------------------------------------- momentum: one Jacobi sweep m of plane k (row i = blockIdx.x + 1)
+// ---------------------------------------------------------------- momentum: Jacobi sweep m of plane k, row blockIdx.x + 1 of case blockIdx.y
 template <bool QUICK>
-__global__ void __launch_bounds__(NT) momentum_sweep(Dev g, int k, int m) {
+__global__ void __launch_bounds__(NT) momentum_sweep(BDev bd, int k, int m) {
   __shared__ double lds[NT];
   __shared__ int flag;
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   if (m > 0) {
     if (uniform_flag(&g.st->m_stop, &flag)) return;
     const double s = sum_partials(mom_part(g, (m - 1) & 1), g.nx, lds);
@@ -199,9 +333,11 @@ __global__ void __launch_bounds__(NT) momentum_sweep(Dev g, int k, int m) {
 }
 
 // ---------------------------------------------------------------- pressure: colour `colour` of red-black sweep m, in place
-__global__ void __launch_bounds__(NT) pressure_half_sweep(Dev g, int colour, int m) {
+__global__ void __launch_bounds__(NT) pressure_half_sweep(BDev bd, int colour, int m) {
   __shared__ double lds[NT];
   __shared__ int flag;
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   if (colour == 1 || m > 0) {
     if (uniform_flag(&g.st->p_stop, &flag)) return;
   }
@@ -236,8 +372,10 @@ __global__ void __launch_bounds__(NT) pressure_half_sweep(Dev g, int colour, int
 }
 
 // ---------------------------------------------------------------- correct_velocity with the residual partials (row per workgroup)
-__global__ void __launch_bounds__(NT) correct_velocity(Dev g) {   // PyCFD_ML_accelerated.py:323-335
+__global__ void __launch_bounds__(NT) correct_velocity(BDev bd) {   // PyCFD_ML_accelerated.py:323-335
   __shared__ double lds[NT];
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   const int i = blockIdx.x + 1;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0;
   const double* P = g.Var + 2 * (size_t)g.sx;
@@ -261,55 +399,127 @@ __global__ void __launch_bounds__(NT) correct_velocity(Dev g) {   // PyCFD_ML_ac
   }
 }
 
-// _convergence_check (PyCFD_ML_accelerated.py:472-505): one workgroup
-__global__ void __launch_bounds__(NT) convergence_check(Dev g, double tol0, double tol1, double tol2) {
+// _convergence_check (PyCFD_ML_accelerated.py:472-505), one workgroup per case.  Non-finite residuals are tested first:
+// `r > tol` is false for NaN, so the converged test alone would take a NaN for convergence.
+__global__ void __launch_bounds__(NT) convergence_check(BDev bd) {
   __shared__ double lds[NT];
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
   double res[3];
   for (int k = 0; k < 3; ++k) res[k] = sum_partials(res_part(g) + (size_t)k * g.nx, g.nx, lds);
   if (threadIdx.x != 0) return;
-  const double tol[3] = {tol0, tol1, tol2};
+  const CaseP& p = bd.cp[blockIdx.y];
   int conv = 1, bad = 0;
   for (int k = 0; k < 3; ++k) {
     const double r = std::sqrt(res[k] / (g.nx * g.ny)) / g.dt;
     g.st->rms[k] = r;
     if (!std::isfinite(r)) bad = 1;
-    if (r > tol[k]) conv = 0;
+    if (r > p.tol[k]) conv = 0;
   }
-  g.st->converged = conv;
-  g.st->nonfinite = bad;
+  g.st->state = bad ? SRCFD_CASE_DIVERGED : conv ? SRCFD_CASE_CONVERGED : SRCFD_CASE_RUNNING;
+}
+
+// srcfd_coarse_solve's validation rules (coarse_solver.cpp)
+bool fine_problem_ok(const srcfd_coarse_problem* pb) {
+  return !(pb->nx < 3 || pb->ny < 3 || pb->nx > 4096 || pb->ny > 4096 || !(pb->lx > 0) || !(pb->ly > 0) || !(pb->reynolds > 0) ||
+           !(pb->rho > 0) || !(pb->dt > 0) || pb->max_iterations < 0 || (pb->scheme != SRCFD_SCHEME_QUICK && pb->scheme != SRCFD_SCHEME_UPWIND) ||
+           (pb->case_type != SRCFD_CASE_LDC && pb->case_type != SRCFD_CASE_BFS) || (pb->case_type == SRCFD_CASE_BFS && !(pb->channel_height > 0)));
 }
 
 }  // namespace
 
-#define HIPCHECK_FS(expr)                                   \
+#define HIPCHECK_F(expr)                                    \
   do {                                                      \
     hipError_t _e = (expr);                                 \
     if (_e != hipSuccess) return hip_fail(#expr, _e);       \
   } while (0)
 
-struct FineSolver {
-  srcfd_coarse_problem pb{};
-  int device = 0;
-  Dev g{};
+// The handle behind both C ABIs: srcfd_fine_batch is a FineBatch, srcfd_fine_solver a FineBatch of one case.
+struct FineBatch {
+  std::vector<srcfd_coarse_problem> pb;
+  int n = 0, device = 0;
+  BDev g{};
   hipStream_t stream = nullptr;
-  Status* host_st = nullptr;   // page-locked
-  double* d_mem = nullptr;
-  int count = 0;               // outer iterations since the last init
-  bool converged = false;
+  Status* host_st = nullptr;   // page-locked, n blocks
+  char* d_mem = nullptr;
+  size_t state_bytes = 0;      // fields and status blocks: what init clears
+  int count = 0;               // outer iterations of the live cases since the last init
   bool primed = false;
-  int predict[3] = {16, 16, SWEEP_CAP};   // chunk sizes: the previous solve's count + margin
-  int last_sweeps[3] = {0, 0, 0};
+  std::vector<int> state, iters, last_sweeps;   // per case; last_sweeps [n][3]
+  std::vector<double> rms;                      // [n][3]
+  int predict[3] = {16, 16, SWEEP_CAP};         // chunk sizes: the largest count of the previous solve + margin
   int64_t n_mom = 0, n_p = 0, n_launch = 0, n_sync = 0;
 
-  ~FineSolver() {
+  ~FineBatch() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamDestroy(stream);
     if (d_mem) (void)hipFree(d_mem);
     if (host_st) (void)hipHostFree(host_st);
   }
-  bool bfs() const { return pb.case_type == SRCFD_CASE_BFS; }
-  unsigned cells_blocks() const { return (unsigned)(((int64_t)g.nx * g.ny + NT - 1) / NT); }
-  unsigned var_blocks() const { return (unsigned)((3 * (int64_t)g.sx + NT - 1) / NT); }
+  bool bfs() const { return pb[0].case_type == SRCFD_CASE_BFS; }
+  bool live(int c) const { return state[c] == SRCFD_CASE_RUNNING; }
+  bool any_live() const {
+    for (int c = 0; c < n; ++c) if (live(c)) return true;
+    return false;
+  }
+  size_t planes() const { return 3 * (size_t)g.sx; }   // doubles in Var (or Old, or Jb) of one case
+  dim3 cells_grid() const { return dim3((unsigned)(((int64_t)g.nx * g.ny + NT - 1) / NT), (unsigned)n); }
+  dim3 var_grid() const { return dim3((unsigned)((3 * (int64_t)g.sx + NT - 1) / NT), (unsigned)n); }
+  dim3 rows_grid() const { return dim3((unsigned)g.nx, (unsigned)n); }
+
+  static int hip_fail(const char* what, hipError_t e) {
+    set_error(std::string("fine solver: ") + what + " failed: " + hipGetErrorString(e));
+    return SRCFD_EHIP;
+  }
+
+  // The problems have been validated by the caller.  One allocation: the cases' field blocks, then the status blocks, then the
+  // parameter blocks.
+  static int create(const std::string& who, const srcfd_coarse_problem* problems, int n_cases, int device, FineBatch** out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error(who + "no HIP device"); return SRCFD_ENODEV; }
+    if (device < 0 || device >= ndev) { set_error(who + "bad device index"); return SRCFD_EINVAL; }
+    std::unique_ptr<FineBatch> s(new FineBatch());
+    s->pb.assign(problems, problems + n_cases);
+    s->n = n_cases;
+    s->device = device;
+    s->state.assign(n_cases, SRCFD_CASE_RUNNING);
+    s->iters.assign(n_cases, 0);
+    s->last_sweeps.assign((size_t)3 * n_cases, 0);
+    s->rms.assign((size_t)3 * n_cases, 0.0);
+    HIPCHECK_F(hipSetDevice(device));
+    BDev& g = s->g;
+    g.nx = problems[0].nx; g.ny = problems[0].ny; g.sy = g.ny + 2; g.sx = (g.nx + 2) * (g.ny + 2);
+    g.stride = case_doubles(g.nx, g.ny);
+    std::vector<CaseP> cp((size_t)n_cases);
+    for (int c = 0; c < n_cases; ++c) {
+      const srcfd_coarse_problem& p = problems[c];
+      CaseP& q = cp[c];
+      std::memset(&q, 0, sizeof(q));
+      q.dx = p.lx / g.nx; q.dy = p.ly / g.ny; q.volp = q.dx * q.dy;
+      q.dt = p.dt; q.rho = p.rho; q.nu = 1.0 / p.reynolds;
+      for (int k = 0; k < 3; ++k) {
+        q.tol[k] = p.tolerance[k];
+        q.relax[k] = p.relax[k];
+        for (int side = 0; side < 4; ++side) { q.bc[k].type[side] = p.bc_type[k][side]; q.bc[k].value[side] = p.bc_value[k][side]; }
+        q.bc[k].bfs = p.case_type == SRCFD_CASE_BFS;
+        q.bc[k].step_h = p.step_height; q.bc[k].h = p.channel_height; q.bc[k].Ub = p.bulk_velocity;
+      }
+    }
+    const size_t field_bytes = (size_t)n_cases * g.stride * sizeof(double);
+    s->state_bytes = field_bytes + (size_t)n_cases * sizeof(Status);
+    const size_t total = s->state_bytes + (size_t)n_cases * sizeof(CaseP);
+    HIPCHECK_F(hipMalloc(&s->d_mem, total));
+    g.base = reinterpret_cast<double*>(s->d_mem);
+    g.st = reinterpret_cast<Status*>(s->d_mem + field_bytes);
+    g.cp = reinterpret_cast<const CaseP*>(s->d_mem + s->state_bytes);
+    HIPCHECK_F(hipMemset(s->d_mem, 0, s->state_bytes));
+    HIPCHECK_F(hipMemcpy(s->d_mem + s->state_bytes, cp.data(), cp.size() * sizeof(CaseP), hipMemcpyHostToDevice));
+    HIPCHECK_F(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    HIPCHECK_F(hipHostMalloc(reinterpret_cast<void**>(&s->host_st), (size_t)n_cases * sizeof(Status), hipHostMallocDefault));
+    std::memset(s->host_st, 0, (size_t)n_cases * sizeof(Status));
+    *out = s.release();
+    return SRCFD_OK;
+  }
 
   int launched() {
     ++n_launch;
@@ -317,190 +527,217 @@ struct FineSolver {
     if (e != hipSuccess) { set_error(std::string("fine solver: kernel launch failed: ") + hipGetErrorString(e)); return SRCFD_EHIP; }
     return SRCFD_OK;
   }
-  int sync_status() {
+  int sync_status() {   // all n status blocks in one copy
     ++n_sync;
-    HIPCHECK_FS(hipMemcpyAsync(host_st, g.st, sizeof(Status), hipMemcpyDeviceToHost, stream));
-    HIPCHECK_FS(hipStreamSynchronize(stream));
+    HIPCHECK_F(hipMemcpyAsync(host_st, g.st, (size_t)n * sizeof(Status), hipMemcpyDeviceToHost, stream));
+    HIPCHECK_F(hipStreamSynchronize(stream));
     return SRCFD_OK;
-  }
-  static int hip_fail(const char* what, hipError_t e) {
-    set_error(std::string("fine solver: ") + what + " failed: " + hipGetErrorString(e));
-    return SRCFD_EHIP;
   }
 
   int bc(int k) {
-    Bc b{};
-    for (int s = 0; s < 4; ++s) { b.type[s] = pb.bc_type[k][s]; b.value[s] = pb.bc_value[k][s]; }
-    b.bfs = bfs();
-    b.step_h = pb.step_height; b.h = pb.channel_height; b.Ub = pb.bulk_velocity;
-    const int n = g.nx > g.ny ? g.nx : g.ny;
-    hipLaunchKernelGGL(bc_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, stream, g, k, b);
+    const int m = g.nx > g.ny ? g.nx : g.ny;
+    hipLaunchKernelGGL(bc_kernel, dim3((m + NT - 1) / NT, n), dim3(NT), 0, stream, g, k);
     return launched();
+  }
+  int copy_planes(size_t dst, size_t src) {
+    hipLaunchKernelGGL(copy_planes_kernel, var_grid(), dim3(NT), 0, stream, g, dst, src);
+    return launched();
+  }
+
+  // Clears every case's fields, fluxes, partials and status block, so that all cases are live again -- with keep_var, all of it
+  // but Var, which the caller has filled on the device.  prime() follows.
+  int reset(bool keep_var) {
+    primed = false;
+    if (!keep_var) {
+      HIPCHECK_F(hipMemsetAsync(d_mem, 0, state_bytes, stream));
+      ++n_launch;
+      return SRCFD_OK;
+    }
+    for (int c = 0; c < n; ++c) {
+      HIPCHECK_F(hipMemsetAsync(g.base + (size_t)c * g.stride + planes(), 0, (g.stride - planes()) * sizeof(double), stream));
+      ++n_launch;
+    }
+    HIPCHECK_F(hipMemsetAsync(g.st, 0, (size_t)n * sizeof(Status), stream));
+    ++n_launch;
+    return SRCFD_OK;
   }
   int prime() {   // BCs (with the BFS inlet), Old = Var, linear_interpolation: _initialize_fields / PyCFD_ML_accelerated.py:940-953
     int rc;
     for (int k = 0; k < 3; ++k) if ((rc = bc(k))) return rc;
-    hipLaunchKernelGGL(copy_f64, dim3(var_blocks()), dim3(NT), 0, stream, g.Old, g.Var, 3 * (int64_t)g.sx, (const int*)nullptr);
-    if ((rc = launched())) return rc;
-    hipLaunchKernelGGL(linear_interpolation, dim3(cells_blocks()), dim3(NT), 0, stream, g);
+    if ((rc = copy_planes(planes(), 0))) return rc;
+    hipLaunchKernelGGL(linear_interpolation, cells_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
     if ((rc = sync_status())) return rc;
     count = 0;
-    converged = false;
+    for (int c = 0; c < n; ++c) {
+      state[c] = SRCFD_CASE_RUNNING;
+      iters[c] = 0;
+      for (int k = 0; k < 3; ++k) rms[3 * c + k] = 0.0;
+    }
     primed = true;
     return SRCFD_OK;
   }
+  // var NULL: zero fields; otherwise the interiors of (n, 3, nx+2, ny+2), staged through each case's Jb, which every momentum
+  // solve overwrites
+  int init(const double* var) {
+    HIPCHECK_F(hipSetDevice(device));
+    int rc = reset(false);
+    if (rc) return rc;
+    if (var) {
+      for (int c = 0; c < n; ++c)
+        HIPCHECK_F(hipMemcpyAsync(g.base + (size_t)c * g.stride + 2 * planes(), var + (size_t)c * planes(), planes() * sizeof(double),
+                                  hipMemcpyHostToDevice, stream));
+      hipLaunchKernelGGL(take_interior, var_grid(), dim3(NT), 0, stream, g);
+      if ((rc = launched())) return rc;
+    }
+    return prime();
+  }
 
-  // One inner solve: chunks of sweep launches until the exit rule has fired or the cap is reached.  Returns the sweep count.
-  int inner(int which, int k, int* sweeps) {
+  // One inner solve of every live case: chunks of sweep launches until each has stopped or the cap is reached.
+  int inner(int which, int k, int64_t* executed) {
     int done = 0, chunk = predict[which], rc;
     for (;;) {
       if (chunk > SWEEP_CAP - done) chunk = SWEEP_CAP - done;
       for (int m = done; m < done + chunk; ++m) {
         if (which < 2) {
-          if (pb.scheme == SRCFD_SCHEME_QUICK) hipLaunchKernelGGL(momentum_sweep<true>, dim3(g.nx), dim3(NT), 0, stream, g, k, m);
-          else hipLaunchKernelGGL(momentum_sweep<false>, dim3(g.nx), dim3(NT), 0, stream, g, k, m);
+          if (pb[0].scheme == SRCFD_SCHEME_QUICK) hipLaunchKernelGGL(momentum_sweep<true>, rows_grid(), dim3(NT), 0, stream, g, k, m);
+          else hipLaunchKernelGGL(momentum_sweep<false>, rows_grid(), dim3(NT), 0, stream, g, k, m);
           if ((rc = launched())) return rc;
         } else {
           for (int colour = 0; colour < 2; ++colour) {
-            hipLaunchKernelGGL(pressure_half_sweep, dim3(g.nx), dim3(NT), 0, stream, g, colour, m);
+            hipLaunchKernelGGL(pressure_half_sweep, rows_grid(), dim3(NT), 0, stream, g, colour, m);
             if ((rc = launched())) return rc;
           }
         }
       }
       done += chunk;
       if ((rc = sync_status())) return rc;
-      const int stop = which < 2 ? host_st->m_stop : host_st->p_stop;
-      if (stop || done >= SWEEP_CAP) break;
+      bool all_stopped = true;
+      for (int c = 0; c < n; ++c)
+        if (live(c) && !(which < 2 ? host_st[c].m_stop : host_st[c].p_stop)) all_stopped = false;
+      if (all_stopped || done >= SWEEP_CAP) break;
       chunk = chunk < 8 ? 8 : 2 * chunk;
     }
-    const int n = which < 2 ? host_st->m_sweeps : host_st->p_sweeps;
-    *sweeps = n;
-    const int next = n + 2 + n / 8;
+    int most = 0;
+    for (int c = 0; c < n; ++c) {
+      if (!live(c)) continue;
+      const int s = which < 2 ? host_st[c].m_sweeps : host_st[c].p_sweeps;
+      last_sweeps[3 * c + which] = s;
+      if (s > most) most = s;
+    }
+    *executed += most;
+    const int next = most + 2 + most / 8;
     predict[which] = next > SWEEP_CAP ? SWEEP_CAP : next;
     return SRCFD_OK;
   }
 
-  // One outer iteration: _implicit_solve + _convergence_check (the order of srcfd_coarse_solve)
+  // One outer iteration of every live case: _implicit_solve + _convergence_check (the order of srcfd_coarse_solve)
   int outer() {
-    int rc, sw = 0;
-    const bool relax = bfs();
+    int rc;
+    const int relax = bfs() ? 1 : 0;
     for (int k = 0; k < 2; ++k) {
-      hipLaunchKernelGGL(copy_f64, dim3(var_blocks()), dim3(NT), 0, stream, g.Jb, g.Var, 3 * (int64_t)g.sx, (const int*)nullptr);
-      if ((rc = launched())) return rc;
-      if ((rc = inner(k, k, &sw))) return rc;
-      last_sweeps[k] = sw;
-      n_mom += sw;
-      hipLaunchKernelGGL(momentum_finish, dim3(cells_blocks()), dim3(NT), 0, stream, g, k, relax ? 1 : 0, pb.relax[k]);
+      if ((rc = copy_planes(2 * planes(), 0))) return rc;
+      if ((rc = inner(k, k, &n_mom))) return rc;
+      hipLaunchKernelGGL(momentum_finish, cells_grid(), dim3(NT), 0, stream, g, k, relax);
       if ((rc = launched())) return rc;
       if ((rc = bc(k))) return rc;
     }
-    hipLaunchKernelGGL(linear_interpolation, dim3(cells_blocks()), dim3(NT), 0, stream, g);
+    hipLaunchKernelGGL(linear_interpolation, cells_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
-    hipLaunchKernelGGL(pressure_rhs, dim3(cells_blocks()), dim3(NT), 0, stream, g);
+    hipLaunchKernelGGL(pressure_rhs, cells_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
-    if ((rc = inner(2, 2, &sw))) return rc;
-    last_sweeps[2] = sw;
-    n_p += sw;
+    if ((rc = inner(2, 2, &n_p))) return rc;
     if (relax) {
-      hipLaunchKernelGGL(under_relax, dim3(cells_blocks()), dim3(NT), 0, stream, g, 2, pb.relax[2]);
+      hipLaunchKernelGGL(under_relax, cells_grid(), dim3(NT), 0, stream, g, 2);
       if ((rc = launched())) return rc;
     }
     if ((rc = bc(2))) return rc;
-    hipLaunchKernelGGL(correct_velocity, dim3(g.nx), dim3(NT), 0, stream, g);
+    hipLaunchKernelGGL(correct_velocity, rows_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
     if ((rc = bc(0))) return rc;
     if ((rc = bc(1))) return rc;
-    hipLaunchKernelGGL(update_flux, dim3(cells_blocks()), dim3(NT), 0, stream, g);
+    hipLaunchKernelGGL(update_flux, cells_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
-    hipLaunchKernelGGL(convergence_check, dim3(1), dim3(NT), 0, stream, g, pb.tolerance[0], pb.tolerance[1], pb.tolerance[2]);
+    hipLaunchKernelGGL(convergence_check, dim3(1, n), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
-    hipLaunchKernelGGL(copy_f64, dim3(var_blocks()), dim3(NT), 0, stream, g.Old, g.Var, 3 * (int64_t)g.sx, (const int*)&g.st->converged);
-    if ((rc = launched())) return rc;
+    if ((rc = copy_planes(planes(), 0))) return rc;   // Old = Var of the cases that go on
     return sync_status();
   }
-#undef HIPCHECK_FS
-};
 
-bool fine_problem_ok(const srcfd_coarse_problem* pb);
+  // Up to max_iterations outer iterations of the live cases; history [n][history_len][3], the other outputs per case.
+  int run(int max_iterations, int* iterations, int* status, double* rms_out, double* history, int history_len) {
+    HIPCHECK_F(hipSetDevice(device));
+    std::vector<int> n_hist((size_t)n, 0);
+    for (int it = 0; it < max_iterations && any_live(); ++it) {
+      ++count;
+      int rc = outer();
+      if (rc) { primed = false; return rc; }
+      for (int c = 0; c < n; ++c) {
+        if (!live(c)) continue;
+        const Status& st = host_st[c];
+        iters[c] = count;
+        state[c] = st.state;   // a diverged case is frozen on the device already; the others go on
+        for (int k = 0; k < 3; ++k) rms[3 * c + k] = st.rms[k];
+        if (count % 100 == 0 && n_hist[c] < history_len) {   // residual_history (PyCFD_ML_accelerated.py:418-421), at the case's own iterations 100, 200, ...
+          for (int k = 0; k < 3; ++k) history[((size_t)c * history_len + n_hist[c]) * 3 + k] = st.rms[k];
+          ++n_hist[c];
+        }
+      }
+    }
+    for (int c = 0; c < n; ++c) {
+      if (iterations) iterations[c] = iters[c];
+      if (status) status[c] = state[c];
+      if (rms_out) for (int k = 0; k < 3; ++k) rms_out[3 * c + k] = rms[3 * c + k];
+    }
+    return SRCFD_OK;
+  }
+
+  int get_state(int first, int last, double* var) {   // Var of cases [first, last)
+    HIPCHECK_F(hipSetDevice(device));
+    for (int c = first; c < last; ++c)
+      HIPCHECK_F(hipMemcpyAsync(var + (size_t)(c - first) * planes(), g.base + (size_t)c * g.stride, planes() * sizeof(double),
+                                hipMemcpyDeviceToHost, stream));
+    HIPCHECK_F(hipStreamSynchronize(stream));
+    return SRCFD_OK;
+  }
+  void counters(int64_t out[4], int* sweeps) const {
+    if (out) {
+      out[0] = n_mom;
+      out[1] = n_p;
+      out[2] = n_launch;
+      out[3] = n_sync;
+    }
+    if (sweeps) for (int q = 0; q < 3 * n; ++q) sweeps[q] = last_sweeps[q];
+  }
+};
+#undef HIPCHECK_F
 
 }  // namespace srcfd
 
-using srcfd::FineSolver;
+using srcfd::FineBatch;
 using srcfd::set_error;
 
-namespace srcfd {
-// srcfd_coarse_solve's validation rules (coarse_solver.cpp)
-bool fine_problem_ok(const srcfd_coarse_problem* pb) {
-  return !(pb->nx < 3 || pb->ny < 3 || pb->nx > 4096 || pb->ny > 4096 || !(pb->lx > 0) || !(pb->ly > 0) || !(pb->reynolds > 0) ||
-           !(pb->rho > 0) || !(pb->dt > 0) || pb->max_iterations < 0 || (pb->scheme != SRCFD_SCHEME_QUICK && pb->scheme != SRCFD_SCHEME_UPWIND) ||
-           (pb->case_type != SRCFD_CASE_LDC && pb->case_type != SRCFD_CASE_BFS) || (pb->case_type == SRCFD_CASE_BFS && !(pb->channel_height > 0)));
-}
-}  // namespace srcfd
+static FineBatch* batch_of(srcfd_fine_solver* s) { return reinterpret_cast<FineBatch*>(s); }
+static FineBatch* batch_of(srcfd_fine_batch* b) { return reinterpret_cast<FineBatch*>(b); }
 
 extern "C" {
 
+// ---------------------------------------------------------------- one case: a batch of one
 int srcfd_fine_solver_create(const srcfd_coarse_problem* problem, int device, srcfd_fine_solver** out) {
   return srcfd::abi_guard("srcfd_fine_solver_create", [&]() -> int {
     if (!problem || !out) { set_error("srcfd_fine_solver_create: bad arguments"); return SRCFD_EINVAL; }
     *out = nullptr;
     if (!srcfd::fine_problem_ok(problem)) { set_error("srcfd_fine_solver_create: bad problem description"); return SRCFD_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("srcfd_fine_solver_create: no HIP device"); return SRCFD_ENODEV; }
-    if (device < 0 || device >= ndev) { set_error("srcfd_fine_solver_create: bad device index"); return SRCFD_EINVAL; }
-    std::unique_ptr<FineSolver> s(new FineSolver());
-    s->pb = *problem;
-    s->device = device;
-    HIPCHECK(hipSetDevice(device));
-    srcfd::Dev& g = s->g;
-    g.nx = problem->nx; g.ny = problem->ny; g.sy = g.ny + 2; g.sx = (g.nx + 2) * (g.ny + 2);
-    g.dx = problem->lx / g.nx; g.dy = problem->ly / g.ny; g.volp = g.dx * g.dy;
-    g.dt = problem->dt; g.rho = problem->rho; g.nu = 1.0 / problem->reynolds;
-    const size_t sx = (size_t)g.sx;
-    // Var, Old, Jb (3 planes each), Ff (4), rhs (1), partials (9 nx), status
-    const size_t n_f64 = 3 * sx + 3 * sx + 3 * sx + 4 * sx + sx + 9 * (size_t)g.nx;
-    const size_t st_off = (n_f64 * sizeof(double) + 255) / 256 * 256;
-    char* base = nullptr;
-    HIPCHECK(hipMalloc(&base, st_off + sizeof(srcfd::Status)));
-    s->d_mem = reinterpret_cast<double*>(base);
-    double* p = s->d_mem;
-    g.Var = p; p += 3 * sx;
-    g.Old = p; p += 3 * sx;
-    g.Jb = p; p += 3 * sx;
-    g.Ff = p; p += 4 * sx;
-    g.rhs = p; p += sx;
-    g.part = p;
-    g.st = reinterpret_cast<srcfd::Status*>(base + st_off);
-    HIPCHECK(hipMemset(base, 0, st_off + sizeof(srcfd::Status)));
-    HIPCHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&s->host_st), sizeof(srcfd::Status), hipHostMallocDefault));
-    std::memset(s->host_st, 0, sizeof(srcfd::Status));
-    *out = reinterpret_cast<srcfd_fine_solver*>(s.release());
-    return SRCFD_OK;
+    return FineBatch::create("srcfd_fine_solver_create: ", problem, 1, device, reinterpret_cast<FineBatch**>(out));
   });
 }
 
-void srcfd_fine_solver_destroy(srcfd_fine_solver* s) { delete reinterpret_cast<FineSolver*>(s); }
+void srcfd_fine_solver_destroy(srcfd_fine_solver* s) { delete batch_of(s); }
 
 int srcfd_fine_solver_init(srcfd_fine_solver* s, const double* var) {
   return srcfd::abi_guard("srcfd_fine_solver_init", [&]() -> int {
     if (!s) { set_error("srcfd_fine_solver_init: bad arguments"); return SRCFD_EINVAL; }
-    FineSolver* f = reinterpret_cast<FineSolver*>(s);
-    srcfd::Dev& g = f->g;
-    HIPCHECK(hipSetDevice(f->device));
-    const size_t bytes = 3 * (size_t)g.sx * sizeof(double);
-    HIPCHECK(hipMemsetAsync(g.Ff, 0, 4 * (size_t)g.sx * sizeof(double), f->stream));
-    ++f->n_launch;
-    if (var) {   // staged through Jb, which every momentum solve overwrites
-      HIPCHECK(hipMemcpyAsync(g.Jb, var, bytes, hipMemcpyHostToDevice, f->stream));
-      hipLaunchKernelGGL(srcfd::take_interior, dim3(f->var_blocks()), dim3(srcfd::NT), 0, f->stream, g, (const double*)g.Jb);
-      int rc = f->launched();
-      if (rc) return rc;
-    } else {
-      HIPCHECK(hipMemsetAsync(g.Var, 0, bytes, f->stream));
-      ++f->n_launch;
-    }
-    return f->prime();
+    return batch_of(s)->init(var);
   });
 }
 
@@ -508,35 +745,35 @@ int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m,
                                            const float* out_affine, int flags, int64_t* n_nonfinite) {
   return srcfd::abi_guard("srcfd_fine_solver_init_from_prediction", [&]() -> int {
     if (!s || !m || !x) { set_error("srcfd_fine_solver_init_from_prediction: bad arguments"); return SRCFD_EINVAL; }
-    FineSolver* f = reinterpret_cast<FineSolver*>(s);
+    FineBatch* f = batch_of(s);
     srcfd::Model* mm = reinterpret_cast<srcfd::Model*>(m);
     if (mm->device != f->device) { set_error("srcfd_fine_solver_init_from_prediction: model and solver are on different devices"); return SRCFD_EINVAL; }
-    const srcfd::Dev& g = f->g;
+    const srcfd_coarse_problem& pb = f->pb[0];
+    const int nx = pb.nx, ny = pb.ny;
     // the solver's own boundary conditions; BFS: the inlet / wall rows of u and v as left-boundary profiles (pipeline.bfs_inlet_profiles)
     srcfd_solver_bc bc[3];
-    std::vector<double> prof((size_t)2 * g.ny, 0.0);
+    std::vector<double> prof((size_t)2 * ny, 0.0);
     for (int k = 0; k < 3; ++k) {
-      for (int q = 0; q < 4; ++q) { bc[k].type[q] = f->pb.bc_type[k][q]; bc[k].value[q] = f->pb.bc_value[k][q]; }
+      for (int q = 0; q < 4; ++q) { bc[k].type[q] = pb.bc_type[k][q]; bc[k].value[q] = pb.bc_value[k][q]; }
       bc[k].left_profile = nullptr;
     }
     if (f->bfs()) {
-      const double sh = f->pb.step_height, h = f->pb.channel_height, Ub = f->pb.bulk_velocity;
-      for (int j = 1; j <= g.ny; ++j) {
-        const double y = (j - 0.5) * g.dy;
+      const double sh = pb.step_height, h = pb.channel_height, Ub = pb.bulk_velocity, dy = pb.ly / ny;
+      for (int j = 1; j <= ny; ++j) {
+        const double y = (j - 0.5) * dy;
         double yp = y - sh;
         if (yp < 0.0) yp = 0.0;
         if (yp > h) yp = h;
         prof[j - 1] = y < sh ? 0.0 : 6.0 * Ub * (yp / h) * (1.0 - (yp / h));
       }
       bc[0].left_profile = prof.data();
-      bc[1].left_profile = prof.data() + g.ny;
+      bc[1].left_profile = prof.data() + ny;
     }
     HIPCHECK(hipSetDevice(f->device));
     HIPCHECK(hipStreamSynchronize(f->stream));   // the hand-off runs on the default stream
-    int rc = srcfd::predict_solver_state(mm, r, x, in_affine, out_affine, bc, g.nx, g.ny, g.Var, nullptr, flags, n_nonfinite);
+    int rc = srcfd::predict_solver_state(mm, r, x, in_affine, out_affine, bc, nx, ny, f->g.base, nullptr, flags, n_nonfinite);   // Var of case 0
     if (rc) return rc;
-    HIPCHECK(hipMemsetAsync(g.Ff, 0, 4 * (size_t)g.sx * sizeof(double), f->stream));
-    ++f->n_launch;
+    if ((rc = f->reset(true))) return rc;
     return f->prime();
   });
 }
@@ -547,28 +784,19 @@ int srcfd_fine_solver_run(srcfd_fine_solver* s, int max_iterations, int* iterati
       set_error("srcfd_fine_solver_run: bad arguments");
       return SRCFD_EINVAL;
     }
-    FineSolver* f = reinterpret_cast<FineSolver*>(s);
+    FineBatch* f = batch_of(s);
     if (!f->primed) { set_error("srcfd_fine_solver_run: call srcfd_fine_solver_init first"); return SRCFD_EINVAL; }
-    HIPCHECK(hipSetDevice(f->device));
-    int n_hist = 0;
-    for (int n = 0; n < max_iterations && !f->converged; ++n) {
-      ++f->count;
-      int rc = f->outer();
-      if (rc) return rc;
-      const srcfd::Status& st = *f->host_st;
-      if (st.nonfinite) {
-        f->primed = false;
-        set_error("srcfd_fine_solver_run: NaN or Inf in the residuals (solver instability)");   // the reference raises ValueError here
-        return SRCFD_EINVAL;
-      }
-      f->converged = st.converged != 0;
-      if (f->count % 100 == 0 && n_hist < history_len) {   // residual_history (PyCFD_ML_accelerated.py:418-421)
-        for (int k = 0; k < 3; ++k) history[3 * n_hist + k] = st.rms[k];
-        ++n_hist;
-      }
+    int it = 0, status = SRCFD_CASE_RUNNING;
+    double r[3];
+    int rc = f->run(max_iterations, &it, &status, r, history, history_len);
+    if (rc) return rc;
+    if (status == SRCFD_CASE_DIVERGED) {
+      f->primed = false;
+      set_error("srcfd_fine_solver_run: NaN or Inf in the residuals (solver instability)");   // the reference raises ValueError here
+      return SRCFD_EINVAL;
     }
-    if (iterations) *iterations = f->count;
-    if (rms) for (int k = 0; k < 3; ++k) rms[k] = f->host_st->rms[k];
+    if (iterations) *iterations = it;
+    if (rms) for (int k = 0; k < 3; ++k) rms[k] = r[k];
     return SRCFD_OK;
   });
 }
@@ -576,25 +804,87 @@ int srcfd_fine_solver_run(srcfd_fine_solver* s, int max_iterations, int* iterati
 int srcfd_fine_solver_get_state(srcfd_fine_solver* s, double* var) {
   return srcfd::abi_guard("srcfd_fine_solver_get_state", [&]() -> int {
     if (!s || !var) { set_error("srcfd_fine_solver_get_state: bad arguments"); return SRCFD_EINVAL; }
-    FineSolver* f = reinterpret_cast<FineSolver*>(s);
-    HIPCHECK(hipSetDevice(f->device));
-    HIPCHECK(hipMemcpyAsync(var, f->g.Var, 3 * (size_t)f->g.sx * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    HIPCHECK(hipStreamSynchronize(f->stream));
-    return SRCFD_OK;
+    return batch_of(s)->get_state(0, 1, var);
   });
 }
 
 int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], int last_sweeps[3]) {
   return srcfd::abi_guard("srcfd_fine_solver_counters", [&]() -> int {
     if (!s) { set_error("srcfd_fine_solver_counters: bad arguments"); return SRCFD_EINVAL; }
-    const FineSolver* f = reinterpret_cast<const FineSolver*>(s);
-    if (counters) {
-      counters[0] = f->n_mom;
-      counters[1] = f->n_p;
-      counters[2] = f->n_launch;
-      counters[3] = f->n_sync;
+    reinterpret_cast<const FineBatch*>(s)->counters(counters, last_sweeps);
+    return SRCFD_OK;
+  });
+}
+
+// ---------------------------------------------------------------- batches
+int srcfd_fine_batch_footprint(int nx, int ny, int n_cases, int64_t* device_bytes) {
+  return srcfd::abi_guard("srcfd_fine_batch_footprint", [&]() -> int {
+    if (!device_bytes || nx < 3 || ny < 3 || nx > 4096 || ny > 4096 || n_cases < 1 || n_cases > srcfd::MAX_CASES) {
+      set_error("srcfd_fine_batch_footprint: bad arguments");
+      return SRCFD_EINVAL;
     }
-    if (last_sweeps) for (int k = 0; k < 3; ++k) last_sweeps[k] = f->last_sweeps[k];
+    *device_bytes = (int64_t)n_cases * (int64_t)(srcfd::case_doubles(nx, ny) * sizeof(double) + sizeof(srcfd::Status) + sizeof(srcfd::CaseP));
+    return SRCFD_OK;
+  });
+}
+
+int srcfd_fine_batch_create(const srcfd_coarse_problem* problems, int n_cases, int device, srcfd_fine_batch** out) {
+  return srcfd::abi_guard("srcfd_fine_batch_create", [&]() -> int {
+    const std::string who = "srcfd_fine_batch_create: ";
+    if (!out) { set_error(who + "bad arguments"); return SRCFD_EINVAL; }
+    *out = nullptr;
+    if (n_cases < 1 || n_cases > srcfd::MAX_CASES) {
+      set_error(who + "n_cases " + std::to_string(n_cases) + " is outside 1.." + std::to_string(srcfd::MAX_CASES));
+      return SRCFD_EINVAL;
+    }
+    if (!problems) { set_error(who + "bad arguments"); return SRCFD_EINVAL; }
+    for (int c = 0; c < n_cases; ++c) {
+      const srcfd_coarse_problem& p = problems[c];
+      if (!srcfd::fine_problem_ok(&p)) { set_error(who + "case " + std::to_string(c) + ": bad problem description"); return SRCFD_EINVAL; }
+      const char* field = p.nx != problems[0].nx ? "nx" : p.ny != problems[0].ny ? "ny" : p.scheme != problems[0].scheme ? "scheme" :
+                          p.case_type != problems[0].case_type ? "case_type" : nullptr;
+      if (field) {
+        set_error(who + "case " + std::to_string(c) + ": " + field + " differs from case 0 (one batch has one mesh, scheme and case type)");
+        return SRCFD_EINVAL;
+      }
+    }
+    return FineBatch::create(who, problems, n_cases, device, reinterpret_cast<FineBatch**>(out));
+  });
+}
+
+void srcfd_fine_batch_destroy(srcfd_fine_batch* b) { delete batch_of(b); }
+
+int srcfd_fine_batch_init(srcfd_fine_batch* b, const double* var) {
+  return srcfd::abi_guard("srcfd_fine_batch_init", [&]() -> int {
+    if (!b) { set_error("srcfd_fine_batch_init: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(b)->init(var);
+  });
+}
+
+int srcfd_fine_batch_run(srcfd_fine_batch* b, int max_iterations, int* iterations, int* status, double* rms, double* history,
+                         int history_len) {
+  return srcfd::abi_guard("srcfd_fine_batch_run", [&]() -> int {
+    if (!b || max_iterations < 0 || history_len < 0 || (history_len > 0 && !history)) {
+      set_error("srcfd_fine_batch_run: bad arguments");
+      return SRCFD_EINVAL;
+    }
+    if (!batch_of(b)->primed) { set_error("srcfd_fine_batch_run: call srcfd_fine_batch_init first"); return SRCFD_EINVAL; }
+    return batch_of(b)->run(max_iterations, iterations, status, rms, history, history_len);
+  });
+}
+
+int srcfd_fine_batch_get_state(srcfd_fine_batch* b, int case_index, double* var) {
+  return srcfd::abi_guard("srcfd_fine_batch_get_state", [&]() -> int {
+    FineBatch* f = batch_of(b);
+    if (!b || !var || case_index < -1 || case_index >= f->n) { set_error("srcfd_fine_batch_get_state: bad arguments"); return SRCFD_EINVAL; }
+    return case_index < 0 ? f->get_state(0, f->n, var) : f->get_state(case_index, case_index + 1, var);
+  });
+}
+
+int srcfd_fine_batch_counters(const srcfd_fine_batch* b, int64_t counters[4], int* last_sweeps) {
+  return srcfd::abi_guard("srcfd_fine_batch_counters", [&]() -> int {
+    if (!b) { set_error("srcfd_fine_batch_counters: bad arguments"); return SRCFD_EINVAL; }
+    reinterpret_cast<const FineBatch*>(b)->counters(counters, last_sweeps);
     return SRCFD_OK;
   });
 }

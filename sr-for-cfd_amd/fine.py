@@ -8,8 +8,8 @@ reference's MeshParameters fields, so the reference's `extract_centerlines(solve
 srcfd_coarse_solve's; its inner sweeps are Jacobi (momentum) and red-black (pressure) -- tests/fine_solver_spec.py is the
 specification.  No plots; `output_name` writes the HDF5 field file in coarse.save_coarse_fields' layout.
 
-`FineSolverBatch` runs B cases of one mesh in one set of launches (csrc/fine_batch.hip, `srcfd_fine_batch_*`), each with the bits
-of a `FineSolver` of its own; `run_normal_simulations` / `run_bfs_normal_simulations` are `run_normal_simulation` /
+`FineSolverBatch` runs B cases of one mesh in one set of launches (`srcfd_fine_batch_*`; the same solver, of which a `FineSolver`
+is a batch of one), each with the bits of a `FineSolver` of its own; `run_normal_simulations` / `run_bfs_normal_simulations` are `run_normal_simulation` /
 `run_bfs_normal_simulation` for a list of Reynolds numbers on it (the sweeps of sr-simulation-data-creation.ipynb cell 2).
 """
 from __future__ import annotations

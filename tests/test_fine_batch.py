@@ -160,7 +160,7 @@ def test_batch_footprint_needs_no_device(srcfd):
         return B * (14 * (nx + 2) * (ny + 2) + 9 * nx) * 8
 
     per_case = footprint(3, 3, 1) - fields(3, 3, 1)
-    assert 56 <= per_case <= 1024          # the status block alone is 8 ints and 3 doubles
+    assert 56 <= per_case <= 1024          # the status block (6 ints and 3 doubles) and the parameter block
     for nx, ny, B in ((3, 3, 1), (12, 10, 4), (131, 530, 2), (400, 400, 8), (400, 400, 64), (4096, 4096, 64)):
         assert footprint(nx, ny, B) == fields(nx, ny, B) + B * per_case, (nx, ny, B)
     for nx, ny, B in ((2, 10, 1), (10, 4097, 1), (10, 10, 0), (10, 10, 65)):

@@ -1,5 +1,5 @@
-"""The batched fine-mesh solver (csrc/fine_batch.hip, fine.FineSolverBatch) on an MI355X: every case of a batch has the bits of
-its numpy specification (tests/fine_solver_spec.py) and of a single-case FineSolver, whatever the batch size, its position in
+"""Batches of cases on the fine-mesh solver (csrc/fine_solver.hip, fine.FineSolverBatch) on an MI355X: every case of a batch has the
+bits of its numpy specification (tests/fine_solver_spec.py) and of a single-case FineSolver, whatever the batch size, its position in
 the batch and what its neighbours do -- stop their inner solves at other sweeps, converge earlier, diverge.  Then the
 training-set generator on top of it, end to end."""
 import importlib
@@ -174,7 +174,7 @@ def test_a_diverging_case_is_frozen_and_the_others_do_not_notice(fine, coarse):
     b.close()
 
 
-# ---------------------------------------------------------------------------------------------- 3: kernel edges against FineSolver
+# ---------------------------------------------------------------------------------------------- 3: kernel edges against the spec and FineSolver
 EDGES = {
     # a thread takes cells j, j + 256 of a row; sum_partials adds partials q, q + 256 (pressure: also q + 512); two BC workgroups
     "ldc400_quick": (lambda f, c: [f.problem(Re, 400, 400, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID) for Re in (400.0, 1000.0)], 2),
@@ -187,6 +187,16 @@ EDGES = {
                                  for Re, rf in ((200.0, {"u": 0.5, "v": 0.5, "p": 0.2}), (400.0, {"u": 0.7, "v": 0.6, "p": 0.3}))], 3),
     "one_case": (lambda f, c: [f.problem(1000.0, 37, 29, 1.0, 1.0, 0.001, "QUICK", None, c.LDC_DOUBLE_LID)], 3),
 }
+
+
+def _spec_trace(pb, var0, iterations):
+    sp = spec.from_problem(pb)
+    sp.init(var0)
+    trace = []
+    for _ in range(iterations):
+        sp.run(1)
+        trace.append((_bits(sp.rms).tolist(), sp.sweeps[-1]))
+    return trace, sp.Var
 
 
 def _solo_trace(fine, pb, var0, iterations):
@@ -203,6 +213,8 @@ def _solo_trace(fine, pb, var0, iterations):
 
 @pytest.mark.parametrize("case", list(EDGES))
 def test_each_case_equals_a_single_case_solver(fine, coarse, case):
+    """A FineSolver is a batch of one on the same kernels: the solo comparison shows that a case's bits depend neither on the batch
+    size nor on its place, the specification that they are the right ones."""
     make, iterations = EDGES[case]
     pbs = make(fine, coarse)
     starts = np.stack([_smooth_state(pb.nx, pb.ny, seed=7 + i) for i, pb in enumerate(pbs)])
@@ -218,6 +230,9 @@ def test_each_case_equals_a_single_case_solver(fine, coarse, case):
     var = b.Var
     b.close()
     for i, pb in enumerate(pbs):
+        trace, spec_var = _spec_trace(pb, starts[i], iterations)
+        assert got[i] == trace, (case, i)
+        _same(var[i], spec_var)
         trace, solo_var = _solo_trace(fine, pb, starts[i], iterations)
         assert got[i] == trace, (case, i)
         _same(var[i], solo_var)

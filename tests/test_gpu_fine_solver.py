@@ -287,8 +287,10 @@ def _same_two_iterations(s, t):
     """The solver primed by init_from_prediction runs as the one primed by init(host): the same Var, Old and fluxes.  The
     synthetic decoder's BFS field (|u| up to 16 at dx 0.025, dt 0.002) overflows, in the specification too: its second
     iteration is the NaN/Inf error, after 1 000 sweeps of each inner solve, in both."""
-    assert _trace(s, 2) == _trace(t, 2)
+    trace = _trace(s, 2)
+    assert trace == _trace(t, 2)
     np.testing.assert_array_equal(_bits(s.Var), _bits(t.Var))
+    return trace
 
 
 def test_hand_off_into_the_device_state_ldc(srcfd, fine, coarse, model):
@@ -326,7 +328,14 @@ def test_hand_off_into_the_device_state_bfs(srcfd, fine, model):
     t = fine.FineSolver(pb)
     t.init(host)
     np.testing.assert_array_equal(_bits(t.Var), _bits(dev))
-    _same_two_iterations(s, t)
+    trace = _same_two_iterations(s, t)
+    # the second iteration was the NaN/Inf error: the hand-off re-arms the diverged handle, keeping the Var it has just written
+    # and nothing else
+    assert isinstance(trace[1][0], str) and "NaN/Inf" in trace[1][0]
+    s.init_from_prediction(model, x, ain, aout, back)
+    np.testing.assert_array_equal(s.Var, host)
+    assert s.iterations == 0
+    assert _trace(s, 1) == trace[:1]
 
 
 def test_resume_and_determinism_at_400(fine, coarse):

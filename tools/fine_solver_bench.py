@@ -7,8 +7,8 @@ us per sweep launch against the 1.45 us dependent-launch floor, and srcfd_coarse
     python tools/fine_solver_bench.py [--iters N] [--warmup W] [--n 400]
 
 With --batch 1,2,4,8,16 it times the batched solver (srcfd_fine_batch_*) instead: per batch size B, B cavities (QUICK, double
-lid, Re spread evenly over 100..800, from zero) as one batch, and in the same process the same cases one after the other on the
-unchanged single-case solver; --repeats times each, on fresh handles.  One JSON line: per B and repeat the ms per outer
+lid, Re spread evenly over 100..800, from zero) as one batch, and in the same process the same cases one after the other, each in
+a single-case handle of its own (a batch of one: B cases in one handle against B handles); --repeats times each, on fresh handles.  One JSON line: per B and repeat the ms per outer
 iteration of the batch and of the B sequential solves, and from the batch's counters the us per sweep launch and host_syncs.
 
     python tools/fine_solver_bench.py --batch 1,2,4,8,16 --iters 10 --warmup 2 [--repeats 3]
