@@ -311,8 +311,9 @@ void srcfd_fine_solver_destroy(srcfd_fine_solver* s);
  * taken (ghosts and corners start at 0).  Then the injection sequence of :940-953: BCs (BFS: with the inlet), Old = Var,
  * linear_interpolation.  Resets the iteration count. */
 int srcfd_fine_solver_init(srcfd_fine_solver* s, const double* var);
-/* The srcfd_predict_into_solver_state hand-off (with the solver's own BCs; BFS: its inlet rows as left profiles) written
- * straight into the solver's device Var, then the priming of srcfd_fine_solver_init.  No field crosses to the host. */
+/* SR of the u, v, p samples of one coarse field (x: (3, lr, lr, 1) float32) written straight into the solver's device Var, then
+ * the priming of srcfd_fine_solver_init with the solver's own BCs (BFS: with the inlet).  No field crosses to the host.  This is
+ * srcfd_fine_batch_init_from_prediction on a batch of one. */
 int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m, srcfd_resampler* r, const float* x,
                                            const float* in_affine, const float* out_affine, int flags, int64_t* n_nonfinite);
 /* Up to max_iterations more outer iterations (none once converged).  *iterations = outer iterations since init; rms = the
@@ -344,6 +345,18 @@ void srcfd_fine_batch_destroy(srcfd_fine_batch* b);
 /* var NULL: zero fields; otherwise (n_cases, 3, nx+2, ny+2) host float64, each case as srcfd_fine_solver_init takes its own.
  * Every case is RUNNING again, at iteration 0. */
 int srcfd_fine_batch_init(srcfd_fine_batch* b, const double* var);
+/* SR of n_warm coarse fields (x: (3*n_warm, lr, lr, 1) float32, u, v, p of each; affines (3*n_warm, 2) or NULL) written into
+ * the device Var of the cases cases[0..n_warm) (NULL: n_warm == n_cases, case i takes field i); every other case starts from
+ * zero fields, as srcfd_fine_batch_init(b, NULL) starts it.  Then the priming of srcfd_fine_batch_init: every case is live
+ * again.  r: NULL, or the resampler from the model's output to the batch's mesh.  No field crosses to the host.
+ * SRCFD_EINVAL: n_warm outside 1..n_cases, a case index out of range or listed twice, model and batch on different devices, a
+ * prediction mesh that is not the batch's, a multi-channel model, a resampler that does not match the model.  n_nonfinite: the
+ * NaN guard's count over all warm samples.  The network chooses its kernels by the sample count, so a warm case's initial
+ * field has the bits of a 3*n_warm-sample prediction: they depend on n_warm (to f32 rounding), unlike everything the solver
+ * computes from a given Var. */
+int srcfd_fine_batch_init_from_prediction(srcfd_fine_batch* b, srcfd_model* m, srcfd_resampler* r, const float* x, int n_warm,
+                                          const int* cases, const float* in_affine, const float* out_affine, int flags,
+                                          int64_t* n_nonfinite);
 /* Up to max_iterations more outer iterations of every case that is RUNNING; returns when none is, or when the budget is
  * spent.  Per case: iterations[n] (a frozen case keeps the count at which it froze), status[n] (SRCFD_CASE_*), rms[n][3] of
  * its last convergence check, history[n][history_len][3] = its rms at its iteration counts divisible by 100 that this call

@@ -136,6 +136,7 @@ _protos = {
     "srcfd_fine_batch_create": (C.c_int, [C.POINTER(CoarseProblem), C.c_int, C.c_int, C.POINTER(_p)]),
     "srcfd_fine_batch_destroy": (None, [_p]),
     "srcfd_fine_batch_init": (C.c_int, [_p, _p]),
+    "srcfd_fine_batch_init_from_prediction": (C.c_int, [_p, _p, _p, _p, C.c_int, C.POINTER(C.c_int), _p, _p, C.c_int, C.POINTER(C.c_int64)]),
     "srcfd_fine_batch_run": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _p, _p, C.c_int]),
     "srcfd_fine_batch_get_state": (C.c_int, [_p, C.c_int, _p]),
     "srcfd_fine_batch_counters": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

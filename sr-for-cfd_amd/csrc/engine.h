@@ -149,7 +149,9 @@ struct Model {
                       unsigned long long* nonfinite, hipStream_t s);
   int predict_device(const void* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
                      unsigned long long* nonfinite, hipStream_t s);
-  // sink (optional): consumes each chunk's device result [first, first+count) on the default stream instead of the copy into y
+  // sink (optional): consumes each chunk's device result [first, first+count) on the default stream instead of the copy into y;
+  // a chunk is up to STAGE_SAMPLES samples then, as for a pageable y
+  static constexpr int STAGE_SAMPLES = 256;
   int predict_host(const float* x, int n, const float* aff_in, const float* aff_out, float* y, int flags, int64_t* n_nonfinite,
                    const std::function<int(const float* y_dev, int first, int count)>& sink = nullptr);
 };
@@ -161,5 +163,12 @@ int fused_debug_read(Model& m, int index, void* dst, size_t bytes);
 int fused_reserve(Model& m, int n);
 int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
                   int flags, unsigned long long* nonfinite, hipStream_t s);
+
+// The prediction behind the hand-offs into a solver state (resample.hip): `write` takes the n_samples predicted [and
+// resampled] planes (ny, nx) on the device, float or double, on the default stream.
+using SolverFieldSink = std::function<int(const void* fields, bool f64, int ny, int nx)>;
+int predict_solver_fields(Model* mm, srcfd_resampler* r, const float* x, int n_samples, const float* in_affine, const float* out_affine,
+                          const std::string& who, const char* owner, int want_nx, int want_ny, int flags, int64_t* n_nonfinite,
+                          const SolverFieldSink& write);
 
 }  // namespace srcfd

@@ -521,7 +521,7 @@ int Model::predict_host(const float* x, int n, const float* aff_in, const float*
     bool armed; hipStream_t* cs;
     ~Drain() { if (armed) { if (*cs) (void)hipStreamSynchronize(*cs); (void)hipStreamSynchronize(nullptr); } }
   } drain{pinned, &copy_stream};
-  int chunk = std::min(n, pinned ? 128 : 256);
+  int chunk = std::min(n, pinned ? 128 : STAGE_SAMPLES);
   if (chunk > stage_chunk || (pinned && !d_y_stage2)) {
     chunk = std::max(chunk, stage_chunk);
     for (void* p : {(void*)d_x_stage, (void*)d_y_stage, (void*)d_y_stage2, (void*)d_aff}) if (p) HIPCHECK(hipFree(p));
@@ -853,7 +853,7 @@ int srcfd_model_footprint(const srcfd_model* m, int n, int precision, size_t byt
       bytes[0] = 2 * (size_t)chunk * mm.max_act_elems() * sizeof(float);
       bytes[1] = params * sizeof(float) * 2 + mm.pack_x3.size() * sizeof(uint16_t);   // packed weights + the per-layer operand orders of the fused f32 kernels (upper bound) + the split-bf16 planes
     }
-    const size_t stage = (size_t)std::min(n, 256);
+    const size_t stage = (size_t)std::min(n, Model::STAGE_SAMPLES);
     bytes[2] = stage * (in_elems + 2 * out_elems + 4) * sizeof(float);   // predict_host: input, two result buffers, affine pairs
     bytes[3] = (size_t)n * out_elems * sizeof(float);                    // what ONE host result of the call takes (pool buffer or caller's array)
     return SRCFD_OK;

@@ -29,6 +29,9 @@
 // predicted from the largest count among the live cases, reads all B status blocks in one copy per chunk, and ends the solve
 // when every live case has stopped: host synchronisations per outer iteration do not grow with B.  The live cases wait for the
 // slowest inner solve of the batch -- the lock-step cost, DESIGN.md section 2c.
+//
+// Warm starts.  srcfd_fine_batch_init_from_prediction super-resolves the coarse fields of any subset of the cases in one prediction
+// and handoff_kernel writes the result into those cases' Var; the other cases start from zero ("Warm starts").
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,16 +44,16 @@
 
 namespace srcfd {
 
-int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const float* in_affine, const float* out_affine,
-                         const srcfd_solver_bc bc[3], int want_nx, int want_ny, double* d_var, double* host_var, int flags,
-                         int64_t* n_nonfinite);   // resample.hip
-
 namespace {
 
 constexpr int NT = 256;            // threads per workgroup; one workgroup per mesh row i
 constexpr int SWEEP_CAP = 1000;    // inner sweeps per solve (PyCFD_ML_accelerated.py:251, 299)
 constexpr double INNER_TOL = 1e-6;
 constexpr int MAX_CASES = 64;      // keeps the per-chunk status read small
+// A warm start predicts u, v, p of up to MAX_CASES fields in one call, which must be one staged chunk of the prediction
+// (predict_solver_fields refuses anything else at run time).
+static_assert(3 * MAX_CASES <= Model::STAGE_SAMPLES, "the samples of a full batch must fit one staged chunk of Model::predict_host");
+static_assert(MAX_CASES <= 256, "WarmMap holds case indices in bytes");
 
 struct Status {      // one per case; written by the kernels with plain stores, read by the host once per chunk
   int m_sweeps, m_stop;    // current momentum solve: sweeps executed, exit rule fired
@@ -271,6 +274,36 @@ __global__ void __launch_bounds__(NT) take_interior(BDev bd) {
   double* f = bd.base + (size_t)blockIdx.y * bd.stride;
   const int r = (int)(c % bd.sx), i = r / bd.sy, j = r - i * bd.sy;
   f[c] = (i >= 1 && i <= bd.nx && j >= 1 && j <= bd.ny) ? f[6 * (size_t)bd.sx + c] : 0.0;
+}
+
+// ---------------------------------------------------------------- the SR hand-off: predicted fields into Var
+// Sample s of the prediction is component s % 3 of the case map.case_of[s / 3]:  Var[k, 1+i, 1+j] = field_k[j, i]  (the reference's
+// transposed injection, PyCFD_ML_accelerated.py:936-938), float64, from the network's float or the resampler's double.  One
+// workgroup per 32 x 32 tile of the (nx+2) x (ny+2) plane, through LDS, so that the read runs along nx and the write along ny + 2.
+// The ghost ring and the corners are written as zeros: prime() follows and sets the ring of all three planes from the interior
+// and the case's own CaseP, as after take_interior.
+constexpr int HT = 32;
+struct WarmMap { unsigned char case_of[MAX_CASES]; };
+
+template <typename T>
+__global__ void __launch_bounds__(NT) handoff_kernel(BDev bd, const T* __restrict__ fields, WarmMap map) {
+  __shared__ double tile[HT][HT + 1];   // the padding column keeps the transposed read off one bank
+  const int s = blockIdx.z, k = s % 3;
+  const T* f = fields + (size_t)s * bd.nx * bd.ny;
+  double* V = bd.base + (size_t)map.case_of[s / 3] * bd.stride + (size_t)k * bd.sx;
+  const int i0 = blockIdx.x * HT, j0 = blockIdx.y * HT;
+  const int tx = threadIdx.x % HT, ty = threadIdx.x / HT;
+  for (int r = ty; r < HT; r += NT / HT) {
+    const int i = i0 + tx, j = j0 + r;
+    if (i >= 1 && i <= bd.nx && j >= 1 && j <= bd.ny) tile[r][tx] = (double)f[(size_t)(j - 1) * bd.nx + (i - 1)];
+  }
+  __syncthreads();
+  for (int r = ty; r < HT; r += NT / HT) {
+    const int i = i0 + r, j = j0 + tx;
+    if (i > bd.nx + 1 || j > bd.ny + 1) continue;
+    const bool inside = i >= 1 && i <= bd.nx && j >= 1 && j <= bd.ny;
+    V[(size_t)i * bd.sy + j] = inside ? tile[tx][r] : 0.0;
+  }
 }
 
 // ---------------------------------------------------------------- momentum: Jacobi sweep m of plane k, row blockIdx.x + 1 of case blockIdx.y
@@ -545,8 +578,8 @@ struct FineBatch {
   }
 
   // Clears every case's fields, fluxes, partials and status block, so that all cases are live again -- with keep_var, all of it
-  // but Var, which the caller has filled on the device.  prime() follows.
-  int reset(bool keep_var) {
+  // but the Var of the cases it marks, which the caller has filled on the device.  prime() follows.
+  int reset(const char* keep_var) {
     primed = false;
     if (!keep_var) {
       HIPCHECK_F(hipMemsetAsync(d_mem, 0, state_bytes, stream));
@@ -554,7 +587,8 @@ struct FineBatch {
       return SRCFD_OK;
     }
     for (int c = 0; c < n; ++c) {
-      HIPCHECK_F(hipMemsetAsync(g.base + (size_t)c * g.stride + planes(), 0, (g.stride - planes()) * sizeof(double), stream));
+      const size_t kept = keep_var[c] ? planes() : 0;
+      HIPCHECK_F(hipMemsetAsync(g.base + (size_t)c * g.stride + kept, 0, (g.stride - kept) * sizeof(double), stream));
       ++n_launch;
     }
     HIPCHECK_F(hipMemsetAsync(g.st, 0, (size_t)n * sizeof(Status), stream));
@@ -581,7 +615,7 @@ struct FineBatch {
   // solve overwrites
   int init(const double* var) {
     HIPCHECK_F(hipSetDevice(device));
-    int rc = reset(false);
+    int rc = reset(nullptr);
     if (rc) return rc;
     if (var) {
       for (int c = 0; c < n; ++c)
@@ -590,6 +624,40 @@ struct FineBatch {
       hipLaunchKernelGGL(take_interior, var_grid(), dim3(NT), 0, stream, g);
       if ((rc = launched())) return rc;
     }
+    return prime();
+  }
+
+  // SR of n_warm coarse fields into the Var of the cases cases[0..n_warm) (nullptr: every case, in order), zero fields for the
+  // others, then prime().  The prediction runs on the default stream, so this handle's stream is drained first and the
+  // prediction drains its own before the memsets and prime() follow here.
+  int init_from_prediction(const std::string& who, const char* owner, Model* mm, srcfd_resampler* r, const float* x, int n_warm,
+                           const int* cases, const float* in_affine, const float* out_affine, int flags, int64_t* n_nonfinite) {
+    if (n_warm < 1 || n_warm > n || (!cases && n_warm != n)) {
+      set_error(who + ": n_warm " + std::to_string(n_warm) + (cases ? " is outside 1.." : " without a case list is not the batch's ") + std::to_string(n));
+      return SRCFD_EINVAL;
+    }
+    WarmMap map{};
+    std::vector<char> warm((size_t)n, 0);
+    for (int w = 0; w < n_warm; ++w) {
+      const int c = cases ? cases[w] : w;
+      if (c < 0 || c >= n) { set_error(who + ": cases[" + std::to_string(w) + "] = " + std::to_string(c) + " is outside 0.." + std::to_string(n - 1)); return SRCFD_EINVAL; }
+      if (warm[c]) { set_error(who + ": case " + std::to_string(c) + " is listed twice"); return SRCFD_EINVAL; }
+      warm[c] = 1;
+      map.case_of[w] = (unsigned char)c;
+    }
+    if (mm->device != device) { set_error(who + ": model and " + owner + " are on different devices"); return SRCFD_EINVAL; }
+    HIPCHECK_F(hipSetDevice(device));
+    HIPCHECK_F(hipStreamSynchronize(stream));
+    int rc = predict_solver_fields(mm, r, x, 3 * n_warm, in_affine, out_affine, who, owner, g.nx, g.ny, flags, n_nonfinite,
+                                   [&](const void* fields, bool f64, int, int) -> int {
+      const dim3 grid((unsigned)((g.nx + 2 + HT - 1) / HT), (unsigned)((g.ny + 2 + HT - 1) / HT), (unsigned)(3 * n_warm));
+      if (f64) hipLaunchKernelGGL(handoff_kernel<double>, grid, dim3(NT), 0, nullptr, g, static_cast<const double*>(fields), map);
+      else hipLaunchKernelGGL(handoff_kernel<float>, grid, dim3(NT), 0, nullptr, g, static_cast<const float*>(fields), map);
+      HIPCHECK_F(hipGetLastError());
+      return SRCFD_OK;
+    });
+    if (rc) return rc;
+    if ((rc = reset(warm.data()))) return rc;
     return prime();
   }
 
@@ -745,36 +813,8 @@ int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m,
                                            const float* out_affine, int flags, int64_t* n_nonfinite) {
   return srcfd::abi_guard("srcfd_fine_solver_init_from_prediction", [&]() -> int {
     if (!s || !m || !x) { set_error("srcfd_fine_solver_init_from_prediction: bad arguments"); return SRCFD_EINVAL; }
-    FineBatch* f = batch_of(s);
-    srcfd::Model* mm = reinterpret_cast<srcfd::Model*>(m);
-    if (mm->device != f->device) { set_error("srcfd_fine_solver_init_from_prediction: model and solver are on different devices"); return SRCFD_EINVAL; }
-    const srcfd_coarse_problem& pb = f->pb[0];
-    const int nx = pb.nx, ny = pb.ny;
-    // the solver's own boundary conditions; BFS: the inlet / wall rows of u and v as left-boundary profiles (pipeline.bfs_inlet_profiles)
-    srcfd_solver_bc bc[3];
-    std::vector<double> prof((size_t)2 * ny, 0.0);
-    for (int k = 0; k < 3; ++k) {
-      for (int q = 0; q < 4; ++q) { bc[k].type[q] = pb.bc_type[k][q]; bc[k].value[q] = pb.bc_value[k][q]; }
-      bc[k].left_profile = nullptr;
-    }
-    if (f->bfs()) {
-      const double sh = pb.step_height, h = pb.channel_height, Ub = pb.bulk_velocity, dy = pb.ly / ny;
-      for (int j = 1; j <= ny; ++j) {
-        const double y = (j - 0.5) * dy;
-        double yp = y - sh;
-        if (yp < 0.0) yp = 0.0;
-        if (yp > h) yp = h;
-        prof[j - 1] = y < sh ? 0.0 : 6.0 * Ub * (yp / h) * (1.0 - (yp / h));
-      }
-      bc[0].left_profile = prof.data();
-      bc[1].left_profile = prof.data() + ny;
-    }
-    HIPCHECK(hipSetDevice(f->device));
-    HIPCHECK(hipStreamSynchronize(f->stream));   // the hand-off runs on the default stream
-    int rc = srcfd::predict_solver_state(mm, r, x, in_affine, out_affine, bc, nx, ny, f->g.base, nullptr, flags, n_nonfinite);   // Var of case 0
-    if (rc) return rc;
-    if ((rc = f->reset(true))) return rc;
-    return f->prime();
+    return batch_of(s)->init_from_prediction("srcfd_fine_solver_init_from_prediction", "solver", reinterpret_cast<srcfd::Model*>(m), r, x, 1,
+                                             nullptr, in_affine, out_affine, flags, n_nonfinite);
   });
 }
 
@@ -858,6 +898,16 @@ int srcfd_fine_batch_init(srcfd_fine_batch* b, const double* var) {
   return srcfd::abi_guard("srcfd_fine_batch_init", [&]() -> int {
     if (!b) { set_error("srcfd_fine_batch_init: bad arguments"); return SRCFD_EINVAL; }
     return batch_of(b)->init(var);
+  });
+}
+
+int srcfd_fine_batch_init_from_prediction(srcfd_fine_batch* b, srcfd_model* m, srcfd_resampler* r, const float* x, int n_warm,
+                                          const int* cases, const float* in_affine, const float* out_affine, int flags,
+                                          int64_t* n_nonfinite) {
+  return srcfd::abi_guard("srcfd_fine_batch_init_from_prediction", [&]() -> int {
+    if (!b || !m || !x) { set_error("srcfd_fine_batch_init_from_prediction: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(b)->init_from_prediction("srcfd_fine_batch_init_from_prediction", "batch", reinterpret_cast<srcfd::Model*>(m), r, x, n_warm,
+                                             cases, in_affine, out_affine, flags, n_nonfinite);
   });
 }
 

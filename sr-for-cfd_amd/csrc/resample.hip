@@ -207,61 +207,70 @@ __global__ void __launch_bounds__(256) solver_state_f64(const T* __restrict__ fi
   Var[idx] = v;
 }
 
-// The hand-off behind srcfd_predict_into_solver_state and srcfd_fine_solver_init_from_prediction: predict the u, v, p samples
-// of one field, [resample,] and write the solver state Var into d_var (nullptr: the model's own scratch); host_var, when not
-// nullptr, receives a copy.  want_nx / want_ny >= 0: the mesh the caller expects (mismatch -> SRCFD_EINVAL).  Default stream;
-// returns after the stream has drained.
-int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const float* in_affine, const float* out_affine,
-                         const srcfd_solver_bc bc[3], int want_nx, int want_ny, double* d_var, double* host_var, int flags,
-                         int64_t* n_nonfinite) {
+// What every hand-off into a solver state shares: the checks of model and resampler against the mesh the caller expects
+// (want_nx / want_ny >= 0; `owner` names whose mesh that is), the prediction of n_samples samples -- u, v, p of n_samples / 3
+// fields -- and the resampler, all on the default stream.  `write` then receives the fields on the device, n_samples planes
+// of (ny, nx): float from the network, double after the resampler.  Returns after the stream has drained.
+// predict_host stages up to Model::STAGE_SAMPLES samples per chunk when it has no host destination; a hand-off writes one
+// chunk (its callers bound n_samples at compile time), and anything else is refused here rather than half-written.
+int predict_solver_fields(Model* mm, srcfd_resampler* r, const float* x, int n_samples, const float* in_affine, const float* out_affine,
+                          const std::string& who, const char* owner, int want_nx, int want_ny, int flags, int64_t* n_nonfinite,
+                          const SolverFieldSink& write) {
   Resampler* rr = reinterpret_cast<Resampler*>(r);
   const int* os = mm->desc.out_shape();
-  if (os[2] != 1) { set_error("srcfd_predict_into_solver_state: single-channel models only"); return SRCFD_EINVAL; }
+  if (os[2] != 1) { set_error(who + ": single-channel models only"); return SRCFD_EINVAL; }
   if (rr && (os[0] != rr->H || os[1] != rr->W || mm->device != rr->device)) {
-    set_error("srcfd_predict_into_solver_state: resampler does not match the model");
+    set_error(who + ": resampler does not match the model");
     return SRCFD_EINVAL;
   }
   const int ny = rr ? rr->OH : os[0], nx = rr ? rr->OW : os[1];
   if ((want_nx >= 0 && want_nx != nx) || (want_ny >= 0 && want_ny != ny)) {
-    set_error("srcfd_fine_solver_init_from_prediction: the prediction's mesh (" + std::to_string(nx) + " x " + std::to_string(ny) +
-              ") is not the solver's (" + std::to_string(want_nx) + " x " + std::to_string(want_ny) + ")");
+    set_error(who + ": the prediction's mesh (" + std::to_string(nx) + " x " + std::to_string(ny) + ") is not the " + owner + "'s (" +
+              std::to_string(want_nx) + " x " + std::to_string(want_ny) + ")");
     return SRCFD_EINVAL;
   }
-  BcDev b{};
-  std::vector<double> prof((size_t)3 * ny, 0.0);
-  bool any_profile = false;
-  for (int k = 0; k < 3; ++k) {
-    for (int s = 0; s < 4; ++s) { b.type[k][s] = bc[k].type[s]; b.value[k][s] = bc[k].value[s]; }
-    b.has_profile[k] = bc[k].left_profile != nullptr;
-    if (bc[k].left_profile) { std::memcpy(&prof[(size_t)k * ny], bc[k].left_profile, sizeof(double) * ny); any_profile = true; }
-  }
-  const size_t var_elems = (size_t)3 * (nx + 2) * (ny + 2);
-  return mm->predict_host(x, 3, in_affine, out_affine, nullptr, flags, n_nonfinite, [&](const float* y_dev, int first, int count) -> int {
-    if (first != 0 || count != 3) { set_error("srcfd_predict_into_solver_state: internal chunking error"); return SRCFD_EINVAL; }
-    const size_t need = (d_var ? 0 : var_elems) + prof.size();
+  return mm->predict_host(x, n_samples, in_affine, out_affine, nullptr, flags, n_nonfinite, [&](const float* y_dev, int first, int count) -> int {
+    if (first != 0 || count != n_samples) { set_error(who + ": internal chunking error"); return SRCFD_EINVAL; }
+    if (!rr) return write(y_dev, false, ny, nx);
+    int rc = rr->reserve(count);
+    if (rc) return rc;
+    rc = rr->run(y_dev, count, rr->d_out, nullptr);
+    if (rc) return rc;
+    return write(rr->d_out, true, ny, nx);
+  });
+}
+
+// srcfd_predict_into_solver_state: one field, the caller's boundary conditions by value, Var (3, nx+2, ny+2) to the host.
+int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const float* in_affine, const float* out_affine,
+                         const srcfd_solver_bc bc[3], double* host_var, int flags, int64_t* n_nonfinite) {
+  static_assert(3 <= Model::STAGE_SAMPLES, "one field's samples are one staged chunk");
+  return predict_solver_fields(mm, r, x, 3, in_affine, out_affine, "srcfd_predict_into_solver_state", "caller", -1, -1, flags, n_nonfinite,
+                               [&](const void* fields, bool f64, int ny, int nx) -> int {
+    BcDev b{};
+    std::vector<double> prof((size_t)3 * ny, 0.0);
+    bool any_profile = false;
+    for (int k = 0; k < 3; ++k) {
+      for (int s = 0; s < 4; ++s) { b.type[k][s] = bc[k].type[s]; b.value[k][s] = bc[k].value[s]; }
+      b.has_profile[k] = bc[k].left_profile != nullptr;
+      if (bc[k].left_profile) { std::memcpy(&prof[(size_t)k * ny], bc[k].left_profile, sizeof(double) * ny); any_profile = true; }
+    }
+    const size_t var_elems = (size_t)3 * (nx + 2) * (ny + 2);
+    const size_t need = var_elems + prof.size();
     if (need > mm->solver_state_elems) {
       if (mm->d_solver_state) { HIPCHECK(hipFree(mm->d_solver_state)); mm->d_solver_state = nullptr; mm->solver_state_elems = 0; }
       HIPCHECK(hipMalloc(&mm->d_solver_state, need * sizeof(double)));
       mm->solver_state_elems = need;
     }
-    double* d_out = d_var ? d_var : mm->d_solver_state;
-    double* d_prof = any_profile ? mm->d_solver_state + (d_var ? 0 : var_elems) : nullptr;
+    double* d_out = mm->d_solver_state;
+    double* d_prof = any_profile ? mm->d_solver_state + var_elems : nullptr;
     if (any_profile) HIPCHECK(hipMemcpyAsync(d_prof, prof.data(), prof.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
     const unsigned blocks = (unsigned)((var_elems + 255) / 256);
-    int rc = SRCFD_OK;
-    if (rr) {
-      rc = rr->reserve(3);
-      if (rc) return rc;
-      rc = rr->run(y_dev, 3, rr->d_out, nullptr);
-      if (rc) return rc;
-      hipLaunchKernelGGL((solver_state_f64<double>), dim3(blocks), dim3(256), 0, nullptr, rr->d_out, ny, nx, b, d_prof, d_out);
-    } else {
-      hipLaunchKernelGGL((solver_state_f64<float>), dim3(blocks), dim3(256), 0, nullptr, y_dev, ny, nx, b, d_prof, d_out);
-    }
+    if (f64) hipLaunchKernelGGL((solver_state_f64<double>), dim3(blocks), dim3(256), 0, nullptr, static_cast<const double*>(fields), ny, nx, b, d_prof, d_out);
+    else hipLaunchKernelGGL((solver_state_f64<float>), dim3(blocks), dim3(256), 0, nullptr, static_cast<const float*>(fields), ny, nx, b, d_prof, d_out);
     HIPCHECK(hipGetLastError());
-    if (host_var) HIPCHECK(hipMemcpyAsync(host_var, d_out, var_elems * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIPCHECK(hipMemcpyAsync(host_var, d_out, var_elems * sizeof(double), hipMemcpyDeviceToHost, nullptr));
     HIPCHECK(hipStreamSynchronize(nullptr));
-    return rc;
+    return SRCFD_OK;
   });
 }
 
@@ -441,8 +450,7 @@ int srcfd_predict_into_solver_state(srcfd_model* m, srcfd_resampler* r, const fl
                                     const srcfd_solver_bc bc[3], double* Var, int flags, int64_t* n_nonfinite) {
   return srcfd::abi_guard("srcfd_predict_into_solver_state", [&]() -> int {
     if (!m || !x || !bc || !Var) { set_error("srcfd_predict_into_solver_state: bad arguments"); return SRCFD_EINVAL; }
-    return srcfd::predict_solver_state(reinterpret_cast<srcfd::Model*>(m), r, x, in_affine, out_affine, bc, -1, -1, nullptr, Var, flags,
-                                       n_nonfinite);
+    return srcfd::predict_solver_state(reinterpret_cast<srcfd::Model*>(m), r, x, in_affine, out_affine, bc, Var, flags, n_nonfinite);
   });
 }
 

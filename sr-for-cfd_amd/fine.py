@@ -11,6 +11,9 @@ specification.  No plots; `output_name` writes the HDF5 field file in coarse.sav
 `FineSolverBatch` runs B cases of one mesh in one set of launches (`srcfd_fine_batch_*`; the same solver, of which a `FineSolver`
 is a batch of one), each with the bits of a `FineSolver` of its own; `run_normal_simulations` / `run_bfs_normal_simulations` are `run_normal_simulation` /
 `run_bfs_normal_simulation` for a list of Reynolds numbers on it (the sweeps of sr-simulation-data-creation.ipynb cell 2).
+`FineSolverBatch.init_from_prediction` warm-starts any subset of a batch from one SR call (srcfd_fine_batch_init_from_prediction);
+`run_ml_accelerated_fine_simulations` / `run_bfs_ml_accelerated_fine_simulations` are the warm-started drop-ins for a sweep, and
+`compare_ml_and_normal_simulations` / `compare_bfs_ml_and_normal_simulations` run each Reynolds number warm and cold in one batch.
 """
 from __future__ import annotations
 
@@ -208,6 +211,41 @@ class FineSolverBatch:
             if Var.shape != self.shape:
                 raise ValueError(f"Var must have shape {self.shape}, not {Var.shape}")
             L.check(L.lib.srcfd_fine_batch_init(self._h, Var.ctypes.data_as(C.c_void_p)))
+        self._reset()
+
+    def init_from_prediction(self, model, x, in_affine=None, out_affine=None, resampler=None, nan_guard: bool = True,
+                             cases: Optional[Sequence[int]] = None) -> int:
+        """SR of n_warm coarse fields -- `x` (3 * n_warm, lr, lr, 1), u, v, p of each, affines (3 * n_warm, 2) -- straight into
+        the device state of the cases `cases` (None: every case, field i into case i); the other cases start from zero fields.
+        Every case runs again from iteration 0 (srcfd_fine_batch_init_from_prediction).  Returns the number of NaN / Inf values
+        the guard replaced in the warm fields.  The network picks its kernels by the sample count, so a warm case's initial
+        bits are those of a 3 * n_warm-sample prediction and depend on n_warm; what the solver makes of a given Var does not."""
+        case_list = None if cases is None else [int(c) for c in cases]
+        n_warm = self.n_cases if case_list is None else len(case_list)
+        if not 1 <= n_warm <= self.n_cases:
+            raise ValueError(f"cases must name between 1 and {self.n_cases} cases, not {n_warm}")
+        if case_list is not None and len(set(case_list)) != n_warm:
+            raise ValueError(f"cases must not repeat a case: {case_list}")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 4 or x.shape[0] != 3 * n_warm or tuple(x.shape[1:]) != tuple(model.input_shape) or x.shape[3] != 1:
+            raise ValueError(f"x must have shape ({3 * n_warm}, lr, lr, 1) for {n_warm} warm cases and the model's input, not {x.shape}")
+        aff = []
+        for name, a in (("in_affine", in_affine), ("out_affine", out_affine)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != (3 * n_warm, 2):
+                    raise ValueError(f"{name} must have shape ({3 * n_warm}, 2), not {a.shape}")
+            aff.append(a)
+        bad = C.c_int64(0)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        idx = None if case_list is None else (C.c_int * n_warm)(*case_list)
+        L.check(L.lib.srcfd_fine_batch_init_from_prediction(self._h, model._h, resampler._h if resampler is not None else None, p(x),
+                                                            n_warm, idx, p(aff[0]), p(aff[1]), L.FLAG_NAN_GUARD if nan_guard else 0,
+                                                            C.byref(bad)))
+        self._reset()
+        return int(bad.value)
+
+    def _reset(self) -> None:
         self.residual_history: List[Dict[str, List[float]]] = [{"u": [], "v": [], "p": []} for _ in range(self.n_cases)]
         self.iterations = np.zeros(self.n_cases, dtype=np.int64)
         self.status = np.zeros(self.n_cases, dtype=np.int64)
@@ -297,13 +335,16 @@ def _per_case(bc, n):
     return [bc] * n
 
 
-def _solve_in_batches(problems, max_iterations, max_batch, device):
+def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=None):
+    """warm_start(batch, a): starts the batch of problems[a : a + batch.n_cases] (default: from zero fields, as created)."""
     if max_batch < 1:
         raise ValueError("max_batch must be at least 1")
     out = []
     for a in range(0, len(problems), max_batch):
         b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device)
         try:
+            if warm_start is not None:
+                warm_start(b, a)
             b.solve()
             out += [(b.fields(i), int(b.iterations[i]), int(b.status[i])) for i in range(b.n_cases)]
         finally:
@@ -347,6 +388,95 @@ def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re:
     s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations_fine, model.device)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated")
+
+
+def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch, output_name, suffix_of, bfs_step_height=None,
+                every=1):
+    """The batched warm-started solve behind the sweep drop-ins.  `problems` holds `every` consecutive cases per coarse field,
+    of which the first is warm-started from it and the others start from zero; prepare(fields) is pipeline._prepare_batch for
+    a list of coarse fields.  The prediction of a batch holds the fields of that batch's warm cases only."""
+    from . import pipeline
+    if max_batch < every:
+        raise ValueError(f"max_batch must be at least {every}")
+    model = prepare([])[0]   # the handle is cached: this picks the device before any solver exists
+
+    def warm_start(b, a):
+        first, n_warm = a // every, b.n_cases // every
+        _, x, ain, aout, back = prepare(coarse_fields_list[first:first + n_warm])
+        cases = None if every == 1 else [every * i for i in range(n_warm)]
+        pipeline._warn_nonfinite(b.init_from_prediction(model, x, ain, aout, back, cases=cases))
+
+    out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start)
+    if output_name is not None:
+        for i, (fields, _, _) in enumerate(out):
+            name = f"{output_name}_Re{problems[i].reynolds:g}{suffix_of(i)}"
+            d = os.path.dirname(name)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            save_coarse_fields(f"{name}.h5", fields, problems[i].reynolds, problems[i].lx, problems[i].ly, bfs_step_height=bfs_step_height)
+    return out
+
+
+def _paired(out, reynolds):
+    """(warm, cold) result pairs of `_warm_sweep(..., every=2)` as the reference's end-of-script comparison
+    (PyCFD_ML_accelerated.py:1488-1499, bfs_ml_accelerated.py main), one dict per Reynolds number."""
+    res = []
+    for i, Re in enumerate(reynolds):
+        (f_ml, it_ml, st_ml), (f_n, it_n, st_n) = out[2 * i], out[2 * i + 1]
+        res.append({"Re": Re, "ml_iterations": it_ml, "normal_iterations": it_n, "ml_status": st_ml, "normal_status": st_n,
+                    "iterations_saved": it_n - it_ml, "ratio": it_n / it_ml if it_ml else float("nan"),
+                    "ml_fields": f_ml, "normal_fields": f_n})
+    return res
+
+
+def _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
+               encoder_file, decoder_file, bc, precision, max_batch, device, every):
+    from . import pipeline
+    reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
+    if len(coarse_fields_list) != len(reynolds):
+        raise ValueError(f"coarse_fields_list must hold one set of coarse fields per Reynolds number ({len(reynolds)}), not {len(coarse_fields_list)}")
+    bcs = _per_case(bc, len(reynolds))
+    stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}.txt"
+    encoder_file = encoder_file or f"vanilla_encoder{lr_dim}_to_{nx}.h5"
+    decoder_file = decoder_file or f"vanilla_decoder{nx}_from_{lr_dim}.h5"
+    _model_files(stats_file, encoder_file, decoder_file)
+    pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs) for _ in range(every)]
+    prepare = lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0, False, 0.3,
+                                                     precision, device)
+    return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
+                       lambda i: "_accelerated" if i % every == 0 else "_normal", every=every)
+
+
+def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                        lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
+                                        convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                        output_name: Optional[str] = None, stats_file: Optional[str] = None,
+                                        encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
+                                        precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+    """`run_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, `max_batch` cases at a time:
+    one SR call per batch straight into the batched device solver, then the batched solve.  Returns a list of (fields,
+    iterations, status) in input order, as `run_normal_simulations`.  `bc`: one boundary-condition set or one per case.
+    `output_name`: None writes nothing; otherwise each case's fields go to `{output_name}_Re{Re}_accelerated.h5`.  `device`:
+    None lets the model loader choose.  A case's initial field has the bits of its batch's prediction (see
+    FineSolverBatch.init_from_prediction); with max_batch=1 every case equals the single-case function bit for bit."""
+    return _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
+                      stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 1)
+
+
+def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                      lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
+                                      convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                      output_name: Optional[str] = None, stats_file: Optional[str] = None,
+                                      encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
+                                      precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+    """The reference's headline experiment (PyCFD_ML_accelerated.py:1431-1499) for a sweep: every Reynolds number goes into the
+    batch twice, case 2i warm-started from its coarse field and case 2i + 1 from zero fields, under the same iteration cap.
+    Returns one dict per Reynolds number: Re, ml_iterations, normal_iterations, ml_status, normal_status, iterations_saved
+    (normal - ml), ratio (normal / ml) and both results' fields.  Whether iterations are saved depends on the decoder's
+    weights; the function only reports the counts."""
+    out = _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
+                     stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 2)
+    return _paired(out, list(reynolds))
 
 
 # ---------------------------------------------------------------------------------------------- backward-facing step
@@ -412,3 +542,55 @@ def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray],
                    max_iterations_fine, model.device)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
+
+
+def _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
+               encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
+               use_adaptive_normalization, blend_factor, precision, max_batch, device, every):
+    from . import pipeline
+    reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
+    if len(coarse_fields_list) != len(reynolds):
+        raise ValueError(f"coarse_fields_list must hold one set of coarse fields per Reynolds number ({len(reynolds)}), not {len(coarse_fields_list)}")
+    bcs = _per_case(bc, len(reynolds))
+    stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}_swish_trained_upto_700_multiBC.txt"
+    encoder_file = encoder_file or f"vanilla_encoder{lr_dim}_to_{nx}_swish_trained_upto_700_multiBC.h5"
+    decoder_file = decoder_file or f"vanilla_decoder{nx}_from_{lr_dim}_swish_trained_upto_700_multiBC.h5"
+    _model_files(stats_file, encoder_file, decoder_file)
+    pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
+           for Re, b in zip(reynolds, bcs) for _ in range(every)]
+    prepare = lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction,
+                                                     lx, ly, use_adaptive_normalization, blend_factor, precision, device)
+    return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
+                       lambda i: "_accelerated" if i % every == 0 else "_normal", bfs_step_height=step_height, every=every)
+
+
+def run_bfs_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                            lr_dim: int = 10, dt: float = 0.002, scheme: str = "UPWIND",
+                                            convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                            output_name: Optional[str] = None, stats_file: Optional[str] = None,
+                                            encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
+                                            step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                                            relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
+                                            use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
+                                            precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+    """`run_bfs_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, batched as
+    `run_ml_accelerated_fine_simulations`."""
+    return _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
+                      stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
+                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 1)
+
+
+def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                          lr_dim: int = 10, dt: float = 0.002, scheme: str = "UPWIND",
+                                          convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                          output_name: Optional[str] = None, stats_file: Optional[str] = None,
+                                          encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
+                                          step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                                          relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
+                                          use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
+                                          precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+    """`compare_ml_and_normal_simulations` for the backward-facing step (bfs_ml_accelerated.py main)."""
+    out = _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
+                     stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
+                     use_adaptive_normalization, blend_factor, precision, max_batch, device, 2)
+    return _paired(out, list(reynolds))

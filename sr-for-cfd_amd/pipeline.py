@@ -64,10 +64,10 @@ def reshape_square_to_rectangular(fields, nx_rect, ny_rect, lx, ly):
     return out
 
 
-def _prepare(coarse_fields, lr_dim, hr_dim, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction, lx, ly,
-             use_adaptive_normalization, blend_factor, precision, say):
-    """Everything before `predict` (PyCFD...:787-857 / bfs...:1025-1108): model handle, the (3,lr,lr,1) float32
-    batch, the per-component (mean,std) pairs in and out, and the resampler for the way back (or None)."""
+def _case_inputs(coarse_fields, lr_dim, stats_lr, stats_hr, use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor,
+                 say):
+    """The part of `_prepare` that depends on the coarse field (PyCFD...:787-857 / bfs...:1025-1108): the (3,lr,lr,1) float32
+    batch, the per-component (mean,std) pairs in and out, and the fields the batch was cast from."""
     fields = coarse_fields
     if use_aspect_ratio_correction and lx != ly:
         # reshape_rectangular_to_square (bfs_ml_accelerated.py:59-101) as two cached 1-D spline matrices: the same
@@ -76,11 +76,6 @@ def _prepare(coarse_fields, lr_dim, hr_dim, stats_file, encoder_file, decoder_fi
         from . import resample as rs
         Ry, Rx = rs.rect_to_square_matrices(lr_dim, lr_dim, float(lx), float(ly))
         fields = {c: Ry @ np.asarray(coarse_fields[c], np.float64) @ Rx.T for c in COMPONENTS}
-    stats_lr, stats_hr = load_stats(stats_file, lr_dim, hr_dim)  # FileNotFoundError / KeyError like :819-825
-    for f in (encoder_file, decoder_file):  # the callers pre-check this (:1080-1087); load_model would raise too
-        if not os.path.exists(f):
-            raise FileNotFoundError(f"model file '{f}' not found")
-    model = kc._device_handle((os.fspath(encoder_file), os.fspath(decoder_file)), precision or kc._DEFAULT_PRECISION)
     x = np.empty((3, lr_dim, lr_dim, 1), np.float32)
     ain = np.empty((3, 2), np.float32)
     aout = np.empty((3, 2), np.float32)
@@ -101,11 +96,47 @@ def _prepare(coarse_fields, lr_dim, hr_dim, stats_file, encoder_file, decoder_fi
                 say(f"  {c.upper()}: adaptive norm (blend={blend_factor:.2f}) mean={float(mean_lr):.6f} std={float(std_lr):.6f}")
         ain[i] = (mean_lr, std_lr)
         aout[i] = stats_hr[c]
+    return x, ain, aout, fields
+
+
+def _prepare_list(coarse_fields_list, lr_dim, hr_dim, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction, lx, ly,
+                  use_adaptive_normalization, blend_factor, precision, say, device=None):
+    """Everything before `predict` for a list of coarse fields: the model handle, the resampler for the way back (or None),
+    and per field what `_case_inputs` returns."""
+    stats_lr, stats_hr = load_stats(stats_file, lr_dim, hr_dim)  # FileNotFoundError / KeyError like :819-825
+    for f in (encoder_file, decoder_file):  # the callers pre-check this (:1080-1087); load_model would raise too
+        if not os.path.exists(f):
+            raise FileNotFoundError(f"model file '{f}' not found")
+    model = kc._device_handle((os.fspath(encoder_file), os.fspath(decoder_file)), precision or kc._DEFAULT_PRECISION, device)
+    per_case = [_case_inputs(cf, lr_dim, stats_lr, stats_hr, use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor,
+                             say) for cf in coarse_fields_list]
     back = None
     if use_aspect_ratio_correction and lx != ly:
         from . import resample as rs
         back = rs.square_to_rect_resampler(hr_dim, hr_dim, hr_dim, float(lx), float(ly), model.device)
+    return model, back, per_case
+
+
+def _prepare(coarse_fields, lr_dim, hr_dim, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction, lx, ly,
+             use_adaptive_normalization, blend_factor, precision, say):
+    """Everything before `predict` (PyCFD...:787-857 / bfs...:1025-1108): model handle, the (3,lr,lr,1) float32
+    batch, the per-component (mean,std) pairs in and out, and the resampler for the way back (or None)."""
+    model, back, ((x, ain, aout, fields),) = _prepare_list([coarse_fields], lr_dim, hr_dim, stats_file, encoder_file, decoder_file,
+                                                           use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor,
+                                                           precision, say)
     return model, x, ain, aout, back, fields
+
+
+def _prepare_batch(coarse_fields_list, lr_dim, hr_dim, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction, lx, ly,
+                   use_adaptive_normalization, blend_factor, precision, device=None):
+    """`_prepare` for a list of coarse fields, stacked: x (3n,lr,lr,1), the affine pairs (3n,2), u, v, p of each field in order."""
+    model, back, per_case = _prepare_list(coarse_fields_list, lr_dim, hr_dim, stats_file, encoder_file, decoder_file,
+                                          use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor, precision, _quiet,
+                                          device)
+    if not per_case:
+        return model, np.empty((0, lr_dim, lr_dim, 1), np.float32), np.empty((0, 2), np.float32), np.empty((0, 2), np.float32), back
+    x, ain, aout = (np.concatenate([pc[q] for pc in per_case]) for q in range(3))
+    return model, x, ain, aout, back
 
 
 def _quiet(*a, **k):

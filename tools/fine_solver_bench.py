@@ -12,6 +12,17 @@ a single-case handle of its own (a batch of one: B cases in one handle against B
 iteration of the batch and of the B sequential solves, and from the batch's counters the us per sweep launch and host_syncs.
 
     python tools/fine_solver_bench.py --batch 1,2,4,8,16 --iters 10 --warmup 2 [--repeats 3]
+
+With --handoff 1,8,16 it times the SR hand-off into the device state at n x n instead (real encoder, synthetic decoder; LDC, and
+BFS through the back-resampler): per batch size B the wall time of one FineSolverBatch.init_from_prediction call that warm-starts
+all B cases (network, [resampler,] hand-off kernel, priming, the host synchronisation at its end), and of B single-case
+FineSolver.init_from_prediction calls one after the other on B handles; --repeats times each after --warmup untimed calls, handles
+created outside the timed region.  --single-only times only the single-case calls, which is all a tree without the batched entry
+has: run it there for the comparison.  One JSON line with every repeat in us.  On a shared machine give every invocation a time
+limit of its own and chain them, e.g.
+
+    timeout -k 10 120 python tools/fine_solver_bench.py --handoff 1,8,16 --repeats 7 > handoff.json &&
+    timeout -k 10 120 python tools/fine_solver_bench.py --handoff 1,8,16 --repeats 7 --single-only > handoff_single.json
 """
 import argparse
 import importlib
@@ -70,6 +81,65 @@ def batch_bench(a, fine, coarse):
     print(json.dumps(out))
 
 
+def handoff_bench(a, fine, coarse):
+    srcfd = importlib.import_module("sr-for-cfd_amd")
+    synth = importlib.import_module("sr-for-cfd_amd.synth")
+    rs = importlib.import_module("sr-for-cfd_amd.resample")
+    n = a.n
+    stem = "swish_trained_upto_700_multiBC"
+    enc_w = srcfd.SRModel.load_h5(os.path.join(a.golden, f"vanilla_encoder10_to_400_{stem}.h5"), None, device=-1).weights()
+    model = srcfd.SRModel.from_weights(enc_w, synth.synthetic_decoder_weights(1), device=0)
+    lr, hr = srcfd.load_stats(os.path.join(a.golden, f"standardization_stats_10to400_{stem}.txt"), 10, 400)
+    ain1, aout1 = (np.array([st[c] for c in "uvp"], np.float32) for st in (lr, hr))
+    if model.output_shape[:2] != (n, n):
+        raise SystemExit(f"--handoff needs --n {model.output_shape[0]}: the mesh of the decoder's output")
+
+    def inputs(name):
+        cf = srcfd.read_coarse_fields(os.path.join(a.golden, name))
+        return np.stack([cf[c].astype(np.float32) for c in "uvp"])[..., None]
+
+    configs = {
+        "ldc_quick_double_lid": (inputs("coarse_ldc_Re800_double_lid.h5"), None,
+                                 lambda Re: fine.problem(Re, n, n, 1.0, 1.0, 0.001, "QUICK", None, coarse.LDC_DOUBLE_LID)),
+        "bfs_upwind_resampled": (inputs("coarse_bfs_Re400.h5"), rs.square_to_rect_resampler(n, n, n, 10.0, 3.0, model.device),
+                                 lambda Re: fine.problem(Re, n, n, 10.0, 3.0, 0.002, "UPWIND", None, None,
+                                                         bfs={"step_height": 1.0, "h": 2.0, "Ub": 1.0})),
+    }
+    us = lambda t: round(1e6 * t, 1)
+    out = {"mesh": f"{n}x{n}", "warmup": a.warmup, "repeats": a.repeats, "single_only": bool(a.single_only), "handoff": {}}
+    for name, (x1, back, make) in configs.items():
+        out["handoff"][name] = {}
+        for B in [int(b) for b in a.handoff.split(",")]:
+            pbs = [make(float(Re)) for Re in np.linspace(100.0, 800.0, B)]
+            row = {}
+            if not a.single_only:
+                x, ain, aout = np.concatenate([x1] * B), np.concatenate([ain1] * B), np.concatenate([aout1] * B)
+                b = fine.FineSolverBatch(pbs)
+                times = []
+                for r in range(a.warmup + a.repeats):
+                    t0 = time.perf_counter()
+                    b.init_from_prediction(model, x, ain, aout, resampler=back)
+                    times.append(time.perf_counter() - t0)
+                b.close()
+                row["batched_us"] = [us(t) for t in times[a.warmup:]]
+                row["batched_us_per_case_median"] = us(float(np.median(times[a.warmup:])) / B)
+            solvers = [fine.FineSolver(pb) for pb in pbs]
+            times = []
+            for r in range(a.warmup + a.repeats):
+                t0 = time.perf_counter()
+                for s in solvers:
+                    s.init_from_prediction(model, x1, ain1, aout1, resampler=back)
+                times.append(time.perf_counter() - t0)
+            for s in solvers:
+                s.close()
+            row["sequential_single_case_us"] = [us(t) for t in times[a.warmup:]]
+            row["sequential_single_case_us_per_case_median"] = us(float(np.median(times[a.warmup:])) / B)
+            if not a.single_only:
+                row["batched_over_sequential_median"] = round(float(np.median(row["batched_us"]) / np.median(row["sequential_single_case_us"])), 4)
+            out["handoff"][name][str(B)] = row
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -78,11 +148,17 @@ def main():
     ap.add_argument("--host-iters", type=int, default=2)
     ap.add_argument("--batch", default=None, help="comma-separated batch sizes: time the batched solver against sequential solves")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--handoff", default=None, help="comma-separated batch sizes: time the SR hand-off, batched against single-case calls")
+    ap.add_argument("--single-only", action="store_true", help="with --handoff: only the single-case calls")
+    ap.add_argument("--golden", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"),
+                    help="directory of the encoder, statistics and coarse-field files --handoff reads")
     a = ap.parse_args()
     fine = importlib.import_module("sr-for-cfd_amd.fine")
     coarse = importlib.import_module("sr-for-cfd_amd.coarse")
     if a.batch:
         return batch_bench(a, fine, coarse)
+    if a.handoff:
+        return handoff_bench(a, fine, coarse)
     n = a.n
     configs = {
         "ldc_quick_re1000_double_lid": dict(Re=1000.0, lx=1.0, ly=1.0, dt=0.001, scheme="QUICK", bc=coarse.LDC_DOUBLE_LID, bfs=None),
