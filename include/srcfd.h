@@ -148,7 +148,13 @@ void srcfd_host_free(void* p);
  * affines float32 device arrays or NULL, y_dev of dtype out_dtype (SRCFD_F32,
  * SRCFD_BF16 or SRCFD_F16), nonfinite_dev an optional device int64 counter
  * that is ADDED to.  Enqueues on hip_stream (a hipStream_t, NULL = default
- * stream) and returns without synchronising. */
+ * stream) and returns without synchronising.
+ * One handle, one stream at a time: the activation workspace, the split-K slabs
+ * and the captured hipGraph belong to the handle, so two calls on the SAME handle
+ * are ordered only when they are enqueued on the same stream.  A caller that moves
+ * a handle to another stream orders the two calls itself (an event, or a
+ * synchronisation in between); nothing in the handle does.  Distinct handles may be
+ * in flight on distinct streams at once (tests/test_gpu_stream_order.py). */
 int srcfd_predict_device(srcfd_model* m, const void* x_dev, int n, const float* in_affine_dev,
                          const float* out_affine_dev, void* y_dev, int out_dtype, int flags,
                          int64_t* nonfinite_dev, void* hip_stream);
@@ -393,7 +399,11 @@ int srcfd_trainer_get_plan(const srcfd_trainer* t, int* fused_tail, int* fused_e
  * squared errors to *sse_dev (device double, may be NULL).  Enqueues on hip_stream, no synchronisation: part of the weight
  * gradients runs on a stream of the trainer's own that forks from and joins hip_stream inside the call.  From the second
  * call with the same params_dev / grads_dev / sse_dev / n / loss_scale the step is replayed as one hipGraph (x_dev and
- * y_dev are first copied to staging buffers, so they need not stay at one address). */
+ * y_dev are first copied to staging buffers, so they need not stay at one address).
+ * One trainer, one stream at a time: the activations, gradient slabs, staging buffers and step graphs belong to the trainer, so
+ * calls on the SAME trainer (this entry, the _ex one below) are ordered only when they are enqueued on the same stream; a caller
+ * that changes streams between two calls orders them itself.  srcfd_adam_step keeps no state of its own: it is ordered by the
+ * stream it is given, like any kernel on the caller's arrays. */
 int srcfd_trainer_forward_backward(srcfd_trainer* t, const float* params_dev, const float* x_dev, const float* y_dev, int n,
                                    float loss_scale, float* grads_dev, double* sse_dev, void* hip_stream);
 /* The same with flags.  SRCFD_TRAIN_OVERWRITE: grads_dev and *sse_dev are WRITTEN, not added into (every parameter's gradient is
