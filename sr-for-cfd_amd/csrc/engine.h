@@ -27,8 +27,12 @@ void set_error(const std::string& m);
     }                                                                                \
   } while (0)
 
+}  // namespace srcfd
+#include "device_mem.h"
+namespace srcfd {
+
 struct ProfEvent {
-  hipEvent_t a, b;
+  Event a, b;
   std::string name;
 };
 
@@ -90,29 +94,27 @@ struct Model {
   size_t enc32_w2 = 0;     // conv2d_1 A fragments in `pack`
   Tail32Pack t32;
   int num_cus = 256;
-  float* d_pack = nullptr;
+  DevBuf<float> d_pack;
   // SRCFD_PREC_FP32X3: ops the split-bf16 GEMM takes (kernels_x3.hip): x3_off[i] = offset of op i's three weight planes in pack_x3
   // (elements), or -1.  Built at create, uploaded with the f32 pack.
   std::vector<int64_t> x3_off;
   int64_t t32_w1x = -1, t32_w2x = -1;   // the streaming tail's first- and second-layer fragments in pack_x3 (kernels.h, Tail32Params::w1x / w2x), or -1
   std::vector<uint16_t> pack_x3;
-  uint16_t* d_pack_x3 = nullptr;
+  DevBuf<uint16_t> d_pack_x3;
 
-  float* buf[2] = {nullptr, nullptr};
+  DevBuf<float> buf[2];
   int ws_chunk = 0;
   size_t ws_per_sample = 0;   // elements per sample the two buffers were sized for (depends on the precision)
-  float* d_splitk = nullptr;  // split-K slabs of the skinny f32 GEMMs
-  double* d_solver_state = nullptr;  // (3, nx+2, ny+2) + row profiles of the solver hand-off
-  size_t solver_state_elems = 0;
-  size_t splitk_floats = 0;
-  float* d_x_stage = nullptr;
-  float* d_y_stage = nullptr;    // host-buffer entry: result of the chunk being computed ...
-  float* d_y_stage2 = nullptr;   // ... and of the chunk being copied out (page-locked destinations: copy and compute overlap)
-  float* d_aff = nullptr;
+  DevBuf<float> d_splitk;  // split-K slabs of the skinny f32 GEMMs
+  DevBuf<double> d_solver_state;  // (3, nx+2, ny+2) + row profiles of the solver hand-off
+  DevBuf<float> d_x_stage;
+  DevBuf<float> d_y_stage;    // host-buffer entry: result of the chunk being computed ...
+  DevBuf<float> d_y_stage2;   // ... and of the chunk being copied out (page-locked destinations: copy and compute overlap)
+  DevBuf<float> d_aff;
   int stage_chunk = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_computed[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-  unsigned long long* d_nonfinite = nullptr;
+  Event ev_computed[2], ev_copied[2];
+  Stream copy_stream;
+  DevBuf<unsigned long long> d_nonfinite;
 
   bool profiling = false;
   std::vector<ProfEvent> prof_events;
@@ -134,13 +136,12 @@ struct Model {
   GraphKey graph_key, last_key;
   Switches sw;            // of the call in progress
   Plan plan, graph_plan;  // of the last forward / of the captured graph
-  hipGraphExec_t graph_exec = nullptr;
-  hipStream_t graph_stream = nullptr;
+  Stream graph_stream;
+  GraphExec graph_exec;
   void drop_graph();
 
   ~Model();
   int init_device();
-  void free_workspace();
   size_t max_act_elems() const;
   int chunk_cap() const;
   int ensure_workspace(int n);

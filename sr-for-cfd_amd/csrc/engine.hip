@@ -113,14 +113,8 @@ static void plan_enc32(Model& m) {
 // ---------------------------------------------------------------------------
 Model::~Model() {
   if (device >= 0) {
-    (void)hipSetDevice(device);
-    free_workspace();
-    if (d_pack) (void)hipFree(d_pack);
-    if (d_pack_x3) (void)hipFree(d_pack_x3);
+    (void)hipSetDevice(device);   // for the members' destructors (device_mem.h)
     fused_free(*this);
-    drop_graph();
-    if (graph_stream) (void)hipStreamDestroy(graph_stream);
-    for (auto& e : prof_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   }
 }
 
@@ -143,22 +137,8 @@ Switches Switches::from_env() {
 }
 
 void Model::drop_graph() {
-  if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
+  graph_exec.reset();
   graph_key = GraphKey();
-}
-
-void Model::free_workspace() {
-  for (int i = 0; i < 2; ++i) if (buf[i]) { (void)hipFree(buf[i]); buf[i] = nullptr; }
-  for (void* p : {(void*)d_x_stage, (void*)d_y_stage, (void*)d_y_stage2, (void*)d_aff, (void*)d_nonfinite, (void*)d_splitk, (void*)d_solver_state}) if (p) (void)hipFree(p);
-  d_y_stage2 = nullptr;
-  if (copy_stream) { (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
-  for (int b = 0; b < 2; ++b) {
-    if (ev_computed[b]) { (void)hipEventDestroy(ev_computed[b]); ev_computed[b] = nullptr; }
-    if (ev_copied[b]) { (void)hipEventDestroy(ev_copied[b]); ev_copied[b] = nullptr; }
-  }
-  d_solver_state = nullptr; solver_state_elems = 0; d_splitk = nullptr; splitk_floats = 0;
-  d_x_stage = d_y_stage = nullptr; d_aff = nullptr; d_nonfinite = nullptr;
-  ws_chunk = 0; stage_chunk = 0; ws_per_sample = 0;
 }
 
 int Model::init_device() {
@@ -172,13 +152,8 @@ int Model::init_device() {
   if (device >= cnt) { set_error("device index out of range"); return SRCFD_EINVAL; }
   HIPCHECK(hipSetDevice(device));
   { hipDeviceProp_t prop; HIPCHECK(hipGetDeviceProperties(&prop, device)); num_cus = prop.multiProcessorCount; }
-  HIPCHECK(hipMalloc(&d_pack, pack.size() * sizeof(float)));
-  HIPCHECK(hipMemcpy(d_pack, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!pack_x3.empty()) {
-    HIPCHECK(hipMalloc(&d_pack_x3, pack_x3.size() * sizeof(uint16_t)));
-    HIPCHECK(hipMemcpy(d_pack_x3, pack_x3.data(), pack_x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
-  return SRCFD_OK;
+  int rc = d_pack.upload(pack);
+  return rc ? rc : d_pack_x3.upload(pack_x3);
 }
 
 static bool tail32_disabled() {
@@ -212,11 +187,8 @@ int Model::ensure_workspace(int n) {
   const size_t per = max_act_elems();   // depends on the precision: the bring-up path materialises every layer
   if (chunk <= ws_chunk && per <= ws_per_sample) return SRCFD_OK;
   drop_graph();  // a captured forward holds the old buffers' addresses
-  for (int i = 0; i < 2; ++i) if (buf[i]) { HIPCHECK(hipFree(buf[i])); buf[i] = nullptr; }
   ws_chunk = 0;
-  size_t bytes = (size_t)chunk * per * sizeof(float);
-  for (int i = 0; i < 2; ++i) HIPCHECK(hipMalloc(&buf[i], bytes));
-  ws_per_sample = per;
+  for (auto& b : buf) { int rc = b.alloc((size_t)chunk * per); if (rc) return rc; }
   size_t need = 0;
   for (size_t i = 0; i < ops.size();) {  // the ops of one layer (ConvT output phases) are launched together: their slabs coexist
     size_t j = i;
@@ -228,9 +200,9 @@ int Model::ensure_workspace(int n) {
       need = std::max(need, gemm_group_ws_floats(ds, cnt));
     i = j;
   }
-  if (d_splitk) { HIPCHECK(hipFree(d_splitk)); d_splitk = nullptr; }
-  splitk_floats = need;
-  if (need) HIPCHECK(hipMalloc(&d_splitk, need * sizeof(float)));
+  int rc = need ? d_splitk.alloc(need) : d_splitk.release();
+  if (rc) return rc;
+  ws_per_sample = per;
   ws_chunk = chunk;
   return SRCFD_OK;
 }
@@ -240,9 +212,9 @@ int Model::launch(const char* name, hipStream_t s, const std::function<hipError_
   if (profiling) {
     if (prof_used == prof_events.size()) {
       ProfEvent e;
-      HIPCHECK(hipEventCreate(&e.a));
-      HIPCHECK(hipEventCreate(&e.b));
-      prof_events.push_back(e);
+      HIPCHECK(hipEventCreate(e.a.out()));
+      HIPCHECK(hipEventCreate(e.b.out()));
+      prof_events.push_back(std::move(e));
     }
     pe = &prof_events[prof_used++];
     pe->name = name;
@@ -267,6 +239,9 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
   int prev_layer = -1;
   size_t first = 0;
   const bool no_enc32 = !sw.enc32;   // functional A/B switch of the tests (Switches, engine.h)
+  const float* const d_pack = this->d_pack.get();
+  const uint16_t* const d_pack_x3 = this->d_pack_x3.get();
+  float* const buf[2] = {this->buf[0].get(), this->buf[1].get()};
   if (enc32_ok && !naive && !no_enc32) {   // standardise + the encoder's four layers: one launch, latent vectors into buf[0]
     Enc32Params ep;
     ep.x = x_dev; ep.affine = aff_in; ep.n = n;
@@ -390,7 +365,7 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
       static const bool no_big = [] { const char* e = getenv("SRCFD_NO_GEMM32_BIG"); return e && atoi(e) != 0; }();
       const bool big = !no_big && gemm32_big_qualifies(ds, cnt);
       rc = launch(desc.layers[op.layer].name.c_str(), s, [&] {
-        return big ? launch_gemm32_big(ds, cnt, X, Bs, biases, Y, s) : launch_gemm_mfma_group(ds, cnt, X, Bs, biases, Y, s, d_splitk, splitk_floats);
+        return big ? launch_gemm32_big(ds, cnt, X, Bs, biases, Y, s) : launch_gemm_mfma_group(ds, cnt, X, Bs, biases, Y, s, d_splitk.get(), d_splitk.size());
       });
       if (rc) return rc;
       i = j - 1;
@@ -408,7 +383,7 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
       if (rc) return rc;
       continue;
     }
-    rc = launch(op.name.c_str(), s, [&] { return naive ? launch_gemm_naive(d, X, B, bias, Y, s) : launch_gemm_mfma(d, X, B, bias, Y, s, d_splitk, splitk_floats); });
+    rc = launch(op.name.c_str(), s, [&] { return naive ? launch_gemm_naive(d, X, B, bias, Y, s) : launch_gemm_mfma(d, X, B, bias, Y, s, d_splitk.get(), d_splitk.size()); });
     if (rc) return rc;
   }
   cur ^= 1;
@@ -467,13 +442,13 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
     if (key == last_key && !(key == graph_key)) {
       // second identical call: every buffer and attribute is set up, so the launches can be captured
       drop_graph();
-      if (!graph_stream) HIPCHECK(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
+      if (!graph_stream) HIPCHECK(hipStreamCreateWithFlags(graph_stream.out(), hipStreamNonBlocking));
       HIPCHECK(hipStreamBeginCapture(graph_stream, hipStreamCaptureModeThreadLocal));
       int rc = run(graph_stream);
       hipGraph_t g = nullptr;
       hipError_t e = hipStreamEndCapture(graph_stream, &g);
       if (rc == SRCFD_OK && e == hipSuccess && g) {
-        e = hipGraphInstantiate(&graph_exec, g, nullptr, nullptr, 0);
+        e = hipGraphInstantiate(graph_exec.out(), g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e == hipSuccess) {
           graph_key = key;
@@ -482,7 +457,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
           plan.graph = 1;
           return SRCFD_OK;
         }
-        graph_exec = nullptr;
+        graph_exec.reset();
       } else if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();  // capture not possible here: fall through to plain launches
     }
@@ -518,43 +493,43 @@ int Model::predict_host(const float* x, int n, const float* aff_in, const float*
   // On the overlapped path an error exit must not leave earlier chunks' copies into the caller's array in flight (the caller drops
   // the array, the pool hands the buffer to the next call): whatever way this function is left, both streams are drained first.
   struct Drain {
-    bool armed; hipStream_t* cs;
+    bool armed; const Stream* cs;
     ~Drain() { if (armed) { if (*cs) (void)hipStreamSynchronize(*cs); (void)hipStreamSynchronize(nullptr); } }
   } drain{pinned, &copy_stream};
   int chunk = std::min(n, pinned ? 128 : STAGE_SAMPLES);
   if (chunk > stage_chunk || (pinned && !d_y_stage2)) {
     chunk = std::max(chunk, stage_chunk);
-    for (void* p : {(void*)d_x_stage, (void*)d_y_stage, (void*)d_y_stage2, (void*)d_aff}) if (p) HIPCHECK(hipFree(p));
-    d_x_stage = d_y_stage = d_y_stage2 = nullptr; d_aff = nullptr; stage_chunk = 0;
+    stage_chunk = 0;
     drop_graph();   // a captured forward holds the old staging addresses
-    HIPCHECK(hipMalloc(&d_x_stage, chunk * in_elems * sizeof(float)));
-    HIPCHECK(hipMalloc(&d_y_stage, chunk * out_elems * sizeof(float)));
-    if (pinned) HIPCHECK(hipMalloc(&d_y_stage2, chunk * out_elems * sizeof(float)));
-    HIPCHECK(hipMalloc(&d_aff, (size_t)chunk * 4 * sizeof(float)));
+    int rc = d_x_stage.alloc(chunk * in_elems);
+    if (!rc) rc = d_y_stage.alloc(chunk * out_elems);
+    if (!rc) rc = pinned ? d_y_stage2.alloc(chunk * out_elems) : d_y_stage2.release();
+    if (!rc) rc = d_aff.alloc((size_t)chunk * 4);
+    if (rc) return rc;
     stage_chunk = chunk;
   }
   if (pinned && !copy_stream) {
-    HIPCHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    HIPCHECK(hipStreamCreateWithFlags(copy_stream.out(), hipStreamNonBlocking));
     for (int b = 0; b < 2; ++b) {
-      HIPCHECK(hipEventCreateWithFlags(&ev_computed[b], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_copied[b], hipEventDisableTiming));
+      HIPCHECK(hipEventCreateWithFlags(ev_computed[b].out(), hipEventDisableTiming));
+      HIPCHECK(hipEventCreateWithFlags(ev_copied[b].out(), hipEventDisableTiming));
     }
   }
-  if (!d_nonfinite) HIPCHECK(hipMalloc(&d_nonfinite, sizeof(unsigned long long)));
-  HIPCHECK(hipMemsetAsync(d_nonfinite, 0, sizeof(unsigned long long), nullptr));
+  if (!d_nonfinite) { int rc = d_nonfinite.alloc(1); if (rc) return rc; }
+  HIPCHECK(hipMemsetAsync(d_nonfinite.get(), 0, sizeof(unsigned long long), nullptr));
   const int step = pinned ? std::min(stage_chunk, 128) : stage_chunk;
   int k = 0;
   for (int i = 0; i < n; i += step, ++k) {
     int c = std::min(step, n - i);
     const int b = pinned ? (k & 1) : 0;
-    float* ydev = b ? d_y_stage2 : d_y_stage;
-    HIPCHECK(hipMemcpyAsync(d_x_stage, x + (size_t)i * in_elems, c * in_elems * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    float* ydev = (b ? d_y_stage2 : d_y_stage).get();
+    HIPCHECK(hipMemcpyAsync(d_x_stage.get(), x + (size_t)i * in_elems, c * in_elems * sizeof(float), hipMemcpyHostToDevice, nullptr));
     float* ain = nullptr;
     float* aout = nullptr;
-    if (aff_in) { ain = d_aff; HIPCHECK(hipMemcpyAsync(ain, aff_in + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
-    if (aff_out) { aout = d_aff + 2 * (size_t)stage_chunk; HIPCHECK(hipMemcpyAsync(aout, aff_out + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
+    if (aff_in) { ain = d_aff.get(); HIPCHECK(hipMemcpyAsync(ain, aff_in + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
+    if (aff_out) { aout = d_aff.get() + 2 * (size_t)stage_chunk; HIPCHECK(hipMemcpyAsync(aout, aff_out + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
     if (pinned && k >= 2) HIPCHECK(hipStreamWaitEvent(nullptr, ev_copied[b], 0));   // the buffer's previous contents have left
-    int rc = predict_device(d_x_stage, c, ain, aout, ydev, SRCFD_F32, flags, d_nonfinite, nullptr);
+    int rc = predict_device(d_x_stage.get(), c, ain, aout, ydev, SRCFD_F32, flags, d_nonfinite.get(), nullptr);
     if (rc) return rc;
     if (sink) { rc = sink(ydev, i, c); if (rc) return rc; HIPCHECK(hipStreamSynchronize(nullptr)); }
     else if (pinned) {
@@ -571,7 +546,7 @@ int Model::predict_host(const float* x, int n, const float* aff_in, const float*
   if (pinned && !sink) { HIPCHECK(hipStreamSynchronize(copy_stream)); HIPCHECK(hipStreamSynchronize(nullptr)); drain.armed = false; }
   if (n_nonfinite) {
     unsigned long long v = 0;
-    HIPCHECK(hipMemcpy(&v, d_nonfinite, sizeof(v), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(&v, d_nonfinite.get(), sizeof(v), hipMemcpyDeviceToHost));
     *n_nonfinite = (int64_t)v;
   }
   return SRCFD_OK;

@@ -472,9 +472,9 @@ struct FineBatch {
   std::vector<srcfd_coarse_problem> pb;
   int n = 0, device = 0;
   BDev g{};
-  hipStream_t stream = nullptr;
-  Status* host_st = nullptr;   // page-locked, n blocks
-  char* d_mem = nullptr;
+  PinnedBuf<Status> host_st;   // n blocks
+  DevBuf<char> d_mem;
+  Stream stream;               // declared last: destroyed before the memory its work uses
   size_t state_bytes = 0;      // fields and status blocks: what init clears
   int count = 0;               // outer iterations of the live cases since the last init
   bool primed = false;
@@ -483,12 +483,7 @@ struct FineBatch {
   int predict[3] = {16, 16, SWEEP_CAP};         // chunk sizes: the largest count of the previous solve + margin
   int64_t n_mom = 0, n_p = 0, n_launch = 0, n_sync = 0;
 
-  ~FineBatch() {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (d_mem) (void)hipFree(d_mem);
-    if (host_st) (void)hipHostFree(host_st);
-  }
+  ~FineBatch() { (void)hipSetDevice(device); }   // for the members' destructors (device_mem.h)
   bool bfs() const { return pb[0].case_type == SRCFD_CASE_BFS; }
   bool live(int c) const { return state[c] == SRCFD_CASE_RUNNING; }
   bool any_live() const {
@@ -541,15 +536,18 @@ struct FineBatch {
     const size_t field_bytes = (size_t)n_cases * g.stride * sizeof(double);
     s->state_bytes = field_bytes + (size_t)n_cases * sizeof(Status);
     const size_t total = s->state_bytes + (size_t)n_cases * sizeof(CaseP);
-    HIPCHECK_F(hipMalloc(&s->d_mem, total));
-    g.base = reinterpret_cast<double*>(s->d_mem);
-    g.st = reinterpret_cast<Status*>(s->d_mem + field_bytes);
-    g.cp = reinterpret_cast<const CaseP*>(s->d_mem + s->state_bytes);
-    HIPCHECK_F(hipMemset(s->d_mem, 0, s->state_bytes));
-    HIPCHECK_F(hipMemcpy(s->d_mem + s->state_bytes, cp.data(), cp.size() * sizeof(CaseP), hipMemcpyHostToDevice));
-    HIPCHECK_F(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    HIPCHECK_F(hipHostMalloc(reinterpret_cast<void**>(&s->host_st), (size_t)n_cases * sizeof(Status), hipHostMallocDefault));
-    std::memset(s->host_st, 0, (size_t)n_cases * sizeof(Status));
+    int rc = s->d_mem.alloc(total);
+    if (rc) return rc;
+    char* const mem = s->d_mem.get();
+    g.base = reinterpret_cast<double*>(mem);
+    g.st = reinterpret_cast<Status*>(mem + field_bytes);
+    g.cp = reinterpret_cast<const CaseP*>(mem + s->state_bytes);
+    HIPCHECK_F(hipMemset(mem, 0, s->state_bytes));
+    HIPCHECK_F(hipMemcpy(mem + s->state_bytes, cp.data(), cp.size() * sizeof(CaseP), hipMemcpyHostToDevice));
+    HIPCHECK_F(hipStreamCreateWithFlags(s->stream.out(), hipStreamNonBlocking));
+    rc = s->host_st.alloc((size_t)n_cases);
+    if (rc) return rc;
+    std::memset(s->host_st.get(), 0, (size_t)n_cases * sizeof(Status));
     *out = s.release();
     return SRCFD_OK;
   }
@@ -562,7 +560,7 @@ struct FineBatch {
   }
   int sync_status() {   // all n status blocks in one copy
     ++n_sync;
-    HIPCHECK_F(hipMemcpyAsync(host_st, g.st, (size_t)n * sizeof(Status), hipMemcpyDeviceToHost, stream));
+    HIPCHECK_F(hipMemcpyAsync(host_st.get(), g.st, (size_t)n * sizeof(Status), hipMemcpyDeviceToHost, stream));
     HIPCHECK_F(hipStreamSynchronize(stream));
     return SRCFD_OK;
   }
@@ -582,7 +580,7 @@ struct FineBatch {
   int reset(const char* keep_var) {
     primed = false;
     if (!keep_var) {
-      HIPCHECK_F(hipMemsetAsync(d_mem, 0, state_bytes, stream));
+      HIPCHECK_F(hipMemsetAsync(d_mem.get(), 0, state_bytes, stream));
       ++n_launch;
       return SRCFD_OK;
     }
@@ -682,14 +680,14 @@ struct FineBatch {
       if ((rc = sync_status())) return rc;
       bool all_stopped = true;
       for (int c = 0; c < n; ++c)
-        if (live(c) && !(which < 2 ? host_st[c].m_stop : host_st[c].p_stop)) all_stopped = false;
+        if (live(c) && !(which < 2 ? host_st.get()[c].m_stop : host_st.get()[c].p_stop)) all_stopped = false;
       if (all_stopped || done >= SWEEP_CAP) break;
       chunk = chunk < 8 ? 8 : 2 * chunk;
     }
     int most = 0;
     for (int c = 0; c < n; ++c) {
       if (!live(c)) continue;
-      const int s = which < 2 ? host_st[c].m_sweeps : host_st[c].p_sweeps;
+      const int s = which < 2 ? host_st.get()[c].m_sweeps : host_st.get()[c].p_sweeps;
       last_sweeps[3 * c + which] = s;
       if (s > most) most = s;
     }
@@ -742,7 +740,7 @@ struct FineBatch {
       if (rc) { primed = false; return rc; }
       for (int c = 0; c < n; ++c) {
         if (!live(c)) continue;
-        const Status& st = host_st[c];
+        const Status& st = host_st.get()[c];
         iters[c] = count;
         state[c] = st.state;   // a diverged case is frozen on the device already; the others go on
         for (int k = 0; k < 3; ++k) rms[3 * c + k] = st.rms[k];

@@ -18,25 +18,24 @@
 namespace srcfd {
 
 struct Pack16 {  // one per operand type (bf16, f16)
-  uint16_t* d_w = nullptr;
-  void* d_consts = nullptr;
-  void* d_w2f = nullptr;
-  void* d_w1f = nullptr;   // mid16: ConvT#1 operands
-  uint16_t* d_w0t = nullptr;   // mid16: ConvT#0 weights as the 16 KB LDS images of its stages, per output phase (offsets in w0t_off)
+  DevBuf<uint16_t> d_w;
+  DevBuf<uint8_t> d_consts;
+  DevBuf<uint16_t> d_w2f;
+  DevBuf<uint16_t> d_w1f;   // mid16: ConvT#1 operands
+  DevBuf<uint16_t> d_w0t;   // mid16: ConvT#0 weights as the 16 KB LDS images of its stages, per output phase (offsets in w0t_off)
   size_t w0t_off[4] = {0, 0, 0, 0};
-  void* d_encf = nullptr;  // enc16: conv2d_1, dense, latent_vector operand fragments (one blob)
+  DevBuf<uint16_t> d_encf;  // enc16: conv2d_1, dense, latent_vector operand fragments (one blob)
   size_t enc_wd_off = 0, enc_wl_off = 0;  // byte offsets of the dense / latent fragments in d_encf
-  float* d_encb = nullptr; // enc16: conv2d_1 bias fragments (128 floats)
-  float* d_midb = nullptr; // mid16: bias fragments (b0f 128 floats, then b1f 64 floats)
+  DevBuf<float> d_encb; // enc16: conv2d_1 bias fragments (128 floats)
+  DevBuf<float> d_midb; // mid16: bias fragments (b0f 128 floats, then b1f 64 floats)
   bool built = false;
 };
 
 struct FusedState : Fused32Pack {   // host side: operand_pack.h
-  float* d_f32 = nullptr;
+  DevBuf<float> d_f32;
   Pack16 packs[2];
-  uint16_t* act[2] = {nullptr, nullptr};
-  float* d_part = nullptr;  // split-K partial-sum slabs
-  size_t part_elems = 0;
+  DevBuf<uint16_t> act[2];
+  DevBuf<float> d_part;  // split-K partial-sum slabs
   int cap = 0;
   int t1_buf = 0;  // which act[] holds ConvT#1's output after the last forward
   int num_cus = 256;
@@ -64,16 +63,7 @@ int fused_init(Model& m) {
                  de.MH == 1 && de.MW == 1 && de.K == 3200 && de.N == 128 && fs->ops[1].Kpad == 3200 &&
                  la.MH == 1 && la.MW == 1 && la.K == 128 && la.N == 64 && fs->ops[2].Kpad == 128;
   }
-  HIPCHECK(hipMalloc(&fs->d_f32, fs->f32.size() * sizeof(float)));
-  HIPCHECK(hipMemcpy(fs->d_f32, fs->f32.data(), fs->f32.size() * sizeof(float), hipMemcpyHostToDevice));
-  return SRCFD_OK;
-}
-
-template <class T, class D> static int upload(const std::vector<T>& v, D** d) {
-  if (v.empty()) return SRCFD_OK;
-  HIPCHECK(hipMalloc(d, v.size() * sizeof(T)));
-  HIPCHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return SRCFD_OK;
+  return fs->d_f32.upload(fs->f32);
 }
 
 // the 16-bit operands of one type (operand_pack.cpp, pack_fused16), uploaded
@@ -84,36 +74,21 @@ static int build_pack(Model& m, FusedState* fs, bool f16) {
   pack_fused16(m.desc, m.ops, m.pack, *fs, fs->enc_ok, f16, h);
   P.enc_wd_off = h.enc_wd_off; P.enc_wl_off = h.enc_wl_off;
   std::copy(h.w0t_off, h.w0t_off + 4, P.w0t_off);
-  int rc = upload(h.w, &P.d_w);
-  if (!rc) rc = upload(h.encf, &P.d_encf);
-  if (!rc) rc = upload(h.encb, &P.d_encb);
-  if (!rc) rc = upload(h.consts, &P.d_consts);
-  if (!rc) rc = upload(h.w2f, &P.d_w2f);
-  if (!rc) rc = upload(h.w0t, &P.d_w0t);
-  if (!rc) rc = upload(h.w1f, &P.d_w1f);
-  if (!rc) rc = upload(h.midb, &P.d_midb);
+  int rc = P.d_w.upload(h.w);
+  if (!rc) rc = P.d_encf.upload(h.encf);
+  if (!rc) rc = P.d_encb.upload(h.encb);
+  if (!rc) rc = P.d_consts.upload(h.consts);
+  if (!rc) rc = P.d_w2f.upload(h.w2f);
+  if (!rc) rc = P.d_w0t.upload(h.w0t);
+  if (!rc) rc = P.d_w1f.upload(h.w1f);
+  if (!rc) rc = P.d_midb.upload(h.midb);
   if (rc) return rc;
   P.built = true;
   return SRCFD_OK;
 }
 
 void fused_free(Model& m) {
-  FusedState* fs = m.fused;
-  if (!fs) return;
-  for (auto& P : fs->packs) {
-    if (P.d_w) (void)hipFree(P.d_w);
-    if (P.d_consts) (void)hipFree(P.d_consts);
-    if (P.d_w2f) (void)hipFree(P.d_w2f);
-    if (P.d_w1f) (void)hipFree(P.d_w1f);
-    if (P.d_w0t) (void)hipFree(P.d_w0t);
-    if (P.d_midb) (void)hipFree(P.d_midb);
-    if (P.d_encf) (void)hipFree(P.d_encf);
-    if (P.d_encb) (void)hipFree(P.d_encb);
-  }
-  if (fs->d_f32) (void)hipFree(fs->d_f32);
-  for (auto* b : fs->act) if (b) (void)hipFree(b);
-  if (fs->d_part) (void)hipFree(fs->d_part);
-  delete fs;
+  delete m.fused;   // FusedState is complete only here
   m.fused = nullptr;
 }
 
@@ -123,7 +98,7 @@ int fused_debug_read(Model& m, int index, void* dst, size_t bytes) {
   if (bytes > (size_t)fs->cap * 160000 * sizeof(uint16_t)) { set_error("read past the activation buffer"); return SRCFD_EINVAL; }
   HIPCHECK(hipSetDevice(m.device));
   HIPCHECK(hipDeviceSynchronize());
-  HIPCHECK(hipMemcpy(dst, fs->act[index == 0 ? fs->t1_buf : fs->t1_buf ^ 1], bytes, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(dst, fs->act[index == 0 ? fs->t1_buf : fs->t1_buf ^ 1].get(), bytes, hipMemcpyDeviceToHost));
   return SRCFD_OK;
 }
 
@@ -140,12 +115,10 @@ int fused_reserve(Model& m, int n) {
   const int want = std::min(n, 1024);
   if (want > fs->cap) {
     m.drop_graph();  // a captured forward holds the old buffers' addresses
-    for (auto*& b : fs->act) if (b) { HIPCHECK(hipFree(b)); b = nullptr; }
     fs->cap = 0;
-    for (auto*& b : fs->act) HIPCHECK(hipMalloc(&b, (size_t)want * ACT_ELEMS * sizeof(uint16_t)));
-    if (fs->d_part) { HIPCHECK(hipFree(fs->d_part)); fs->d_part = nullptr; }
-    fs->part_elems = (size_t)16 * want * 128;  // dense(3200->128): up to 16 K-slice slabs of (rows x 128) f32
-    HIPCHECK(hipMalloc(&fs->d_part, fs->part_elems * sizeof(float)));
+    for (auto& b : fs->act) { rc = b.alloc((size_t)want * ACT_ELEMS); if (rc) return rc; }
+    rc = fs->d_part.alloc((size_t)16 * want * 128);  // dense(3200->128): up to 16 K-slice slabs of (rows x 128) f32
+    if (rc) return rc;
     fs->cap = want;
   }
   return SRCFD_OK;
@@ -159,6 +132,8 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
   int rc = fused_reserve(m, n);
   if (rc) return rc;
   const Pack16& P = fs->packs[f16 ? 1 : 0];
+  const float* const d_f32 = fs->d_f32.get();
+  uint16_t* const act[2] = {fs->act[0].get(), fs->act[1].get()};
   const size_t osz = out_dtype == SRCFD_F32 ? 4 : 2;
   for (int i0 = 0; i0 < n; i0 += fs->cap) {
     const int c = std::min(fs->cap, n - i0);
@@ -174,11 +149,11 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
     if (use_enc) {
       EncParams ep;
       ep.x = xin; ep.affine = ain; ep.n = c;
-      ep.w1 = fs->d_f32 + fs->c1w_off; ep.b1 = fs->d_f32 + fs->c1b_off;
-      ep.w2f = P.d_encf; ep.b2f = P.d_encb;
-      ep.wdf = (const char*)P.d_encf + P.enc_wd_off; ep.bd = fs->d_f32 + fs->ops[1].b_off;
-      ep.wlf = (const char*)P.d_encf + P.enc_wl_off; ep.bl = fs->d_f32 + fs->ops[2].b_off;
-      ep.z = fs->act[1];
+      ep.w1 = d_f32 + fs->c1w_off; ep.b1 = d_f32 + fs->c1b_off;
+      ep.w2f = P.d_encf.get(); ep.b2f = P.d_encb.get();
+      ep.wdf = (const char*)P.d_encf.get() + P.enc_wd_off; ep.bd = d_f32 + fs->ops[1].b_off;
+      ep.wlf = (const char*)P.d_encf.get() + P.enc_wl_off; ep.bl = d_f32 + fs->ops[2].b_off;
+      ep.z = act[1];
       ep.act_dense = fs->ops[1].d.act; ep.act_latent = fs->ops[2].d.act;
       ep.prof = nullptr;
 #ifdef SRCFD_DIAG
@@ -202,7 +177,7 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
 #endif
       cur = 1;   // where the layer-by-layer chain leaves the latent vectors, too
     } else {
-      rc = m.launch("conv2d", s, [&] { return launch_enc_conv1_16(f16, xin, ain, fs->d_f32 + fs->c1w_off, fs->d_f32 + fs->c1b_off, fs->act[0], c, s); });
+      rc = m.launch("conv2d", s, [&] { return launch_enc_conv1_16(f16, xin, ain, d_f32 + fs->c1w_off, d_f32 + fs->c1b_off, act[0], c, s); });
       if (rc) return rc;
     }
     int prev_layer = -1;
@@ -213,30 +188,30 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
       prev_layer = o.layer;
       GemmDesc d = o.d;
       d.M = c * d.MH * d.MW;
-      const uint16_t* X = fs->act[cur];
-      uint16_t* Y = fs->act[cur ^ 1];
+      const uint16_t* X = act[cur];
+      uint16_t* Y = act[cur ^ 1];
       // dense layers with few rows and a long K: split K over workgroups (f32 slabs + finish kernel)
       int splits = 1;
       if (d.MH == 1 && d.MW == 1 && d.K >= 1024) splits = std::max(1, std::min(16, d.K / 256));
-      if (splits > 1 && (size_t)splits * d.M * d.Npad > fs->part_elems) splits = 1;
+      if (splits > 1 && (size_t)splits * d.M * d.Npad > fs->d_part.size()) splits = 1;
       if (use_d1 && o.layer == 4 && dense1_16_qualifies(d, o.Kpad))
-        rc = m.launch(o.name.c_str(), s, [&] { return launch_dense1_16(f16, d, X, P.d_w + o.w_off, fs->d_f32 + o.b_off, Y, s); });
+        rc = m.launch(o.name.c_str(), s, [&] { return launch_dense1_16(f16, d, X, P.d_w.get() + o.w_off, d_f32 + o.b_off, Y, s); });
       else
-        rc = m.launch(o.name.c_str(), s, [&] { return launch_gemm16(f16, d, X, P.d_w + o.w_off, o.Kpad, fs->d_f32 + o.b_off, Y, fs->d_part, splits, s); });
+        rc = m.launch(o.name.c_str(), s, [&] { return launch_gemm16(f16, d, X, P.d_w.get() + o.w_off, o.Kpad, d_f32 + o.b_off, Y, fs->d_part.get(), splits, s); });
       if (rc) return rc;
     }
     if (use_mid) {
       cur ^= 1;  // dense_1 output
       MidParams mp;
-      mp.in = fs->act[cur];
-      mp.out = fs->act[cur ^ 1];
+      mp.in = act[cur];
+      mp.out = act[cur ^ 1];
       mp.n = c;
       int ph = 0;
       for (const Op16& o : fs->ops)
-        if (o.layer == 5) { mp.w0[ph] = P.d_w + o.w_off; mp.kpad[ph] = o.Kpad; mp.w0t[ph] = P.d_w0t + P.w0t_off[ph]; ++ph; }
-      mp.b0f = P.d_midb;
-      mp.w1f = P.d_w1f;
-      mp.b1f = P.d_midb + 128;
+        if (o.layer == 5) { mp.w0[ph] = P.d_w.get() + o.w_off; mp.kpad[ph] = o.Kpad; mp.w0t[ph] = P.d_w0t.get() + P.w0t_off[ph]; ++ph; }
+      mp.b0f = P.d_midb.get();
+      mp.w1f = P.d_w1f.get();
+      mp.b1f = P.d_midb.get() + 128;
       mp.ablate = 0;
       mp.order = m.sw.mid_order;
       mp.prof = nullptr;
@@ -270,11 +245,11 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
     cur ^= 1;
     fs->t1_buf = cur;
     TailParams tp;
-    tp.in = fs->act[cur];
+    tp.in = act[cur];
     tp.out = (char*)y_dev + (size_t)i0 * 160000 * osz;
     tp.n = c;
-    tp.consts = P.d_consts;
-    tp.w2frags = P.d_w2f;
+    tp.consts = P.d_consts.get();
+    tp.w2frags = P.d_w2f.get();
     tp.aff_out = aout;
     tp.nan_guard = flags & SRCFD_FLAG_NAN_GUARD;
     tp.nonfinite = nonfinite;

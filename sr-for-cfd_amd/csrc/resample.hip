@@ -122,21 +122,18 @@ __global__ void __launch_bounds__(256) widen_f64(const float* __restrict__ x, do
 struct Resampler {
   int device = 0;
   int H = 0, W = 0, OH = 0, OW = 0;
-  double* d_Ry = nullptr;   // [OH][H]
-  double* d_RxT = nullptr;  // [W][OW]
-  double* d_T = nullptr;    // [cap][H][OW]
-  double* d_out = nullptr;  // [cap][OH][OW]
+  DevBuf<double> d_Ry;   // [OH][H]
+  DevBuf<double> d_RxT;  // [W][OW]
+  DevBuf<double> d_T;    // [cap][H][OW]
+  DevBuf<double> d_out;  // [cap][OH][OW]
   int cap = 0;
-  ~Resampler() {
-    (void)hipSetDevice(device);
-    for (void* p : {(void*)d_Ry, (void*)d_RxT, (void*)d_T, (void*)d_out}) if (p) (void)hipFree(p);
-  }
+  ~Resampler() { (void)hipSetDevice(device); }   // for the members' destructors (device_mem.h)
   int reserve(int n) {
     if (n <= cap) return SRCFD_OK;
-    for (void* p : {(void*)d_T, (void*)d_out}) if (p) HIPCHECK(hipFree(p));
-    d_T = d_out = nullptr; cap = 0;
-    HIPCHECK(hipMalloc(&d_T, (size_t)n * H * OW * sizeof(double)));
-    HIPCHECK(hipMalloc(&d_out, (size_t)n * OH * OW * sizeof(double)));
+    cap = 0;
+    int rc = d_T.alloc((size_t)n * H * OW);
+    if (!rc) rc = d_out.alloc((size_t)n * OH * OW);
+    if (rc) return rc;
     cap = n;
     return SRCFD_OK;
   }
@@ -146,6 +143,8 @@ struct Resampler {
   int run(const float* in_dev, int n, double* out_dev, hipStream_t s) {
     int rc = reserve(n);
     if (rc) return rc;
+    const double *d_Ry = this->d_Ry.get(), *d_RxT = this->d_RxT.get();
+    double* d_T = this->d_T.get();
     if (rx_identity && ry_identity) {
       hipLaunchKernelGGL(widen_f64, dim3((unsigned)(((int64_t)n * H * W + 255) / 256)), dim3(256), 0, s, in_dev, out_dev, (int64_t)n * H * W);
     } else if (rx_identity) {
@@ -234,9 +233,9 @@ int predict_solver_fields(Model* mm, srcfd_resampler* r, const float* x, int n_s
     if (!rr) return write(y_dev, false, ny, nx);
     int rc = rr->reserve(count);
     if (rc) return rc;
-    rc = rr->run(y_dev, count, rr->d_out, nullptr);
+    rc = rr->run(y_dev, count, rr->d_out.get(), nullptr);
     if (rc) return rc;
-    return write(rr->d_out, true, ny, nx);
+    return write(rr->d_out.get(), true, ny, nx);
   });
 }
 
@@ -256,13 +255,9 @@ int predict_solver_state(Model* mm, srcfd_resampler* r, const float* x, const fl
     }
     const size_t var_elems = (size_t)3 * (nx + 2) * (ny + 2);
     const size_t need = var_elems + prof.size();
-    if (need > mm->solver_state_elems) {
-      if (mm->d_solver_state) { HIPCHECK(hipFree(mm->d_solver_state)); mm->d_solver_state = nullptr; mm->solver_state_elems = 0; }
-      HIPCHECK(hipMalloc(&mm->d_solver_state, need * sizeof(double)));
-      mm->solver_state_elems = need;
-    }
-    double* d_out = mm->d_solver_state;
-    double* d_prof = any_profile ? mm->d_solver_state + var_elems : nullptr;
+    if (need > mm->d_solver_state.size()) { int rc = mm->d_solver_state.alloc(need); if (rc) return rc; }
+    double* d_out = mm->d_solver_state.get();
+    double* d_prof = any_profile ? d_out + var_elems : nullptr;
     if (any_profile) HIPCHECK(hipMemcpyAsync(d_prof, prof.data(), prof.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
     const unsigned blocks = (unsigned)((var_elems + 255) / 256);
     if (f64) hipLaunchKernelGGL((solver_state_f64<double>), dim3(blocks), dim3(256), 0, nullptr, static_cast<const double*>(fields), ny, nx, b, d_prof, d_out);
@@ -404,10 +399,9 @@ int srcfd_resampler_create(int device, const double* Ry, const double* Rx, int i
     };
     r->ry_identity = is_identity(Ry, out_h, in_h);
     r->rx_identity = is_identity(Rx, out_w, in_w);
-    HIPCHECK(hipMalloc(&r->d_Ry, (size_t)out_h * in_h * sizeof(double)));
-    HIPCHECK(hipMalloc(&r->d_RxT, rxt.size() * sizeof(double)));
-    HIPCHECK(hipMemcpy(r->d_Ry, Ry, (size_t)out_h * in_h * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(r->d_RxT, rxt.data(), rxt.size() * sizeof(double), hipMemcpyHostToDevice));
+    int rc = r->d_Ry.upload(Ry, (size_t)out_h * in_h);
+    if (!rc) rc = r->d_RxT.upload(rxt);
+    if (rc) return rc;
     *out = reinterpret_cast<srcfd_resampler*>(r.release());
     return SRCFD_OK;
   });
@@ -437,9 +431,9 @@ int srcfd_predict_resampled(srcfd_model* m, srcfd_resampler* r, const float* x, 
     return mm->predict_host(x, n, in_affine, out_affine, nullptr, flags, n_nonfinite, [&](const float* y_dev, int first, int count) -> int {
       int rc = rr->reserve(count);
       if (rc) return rc;
-      rc = rr->run(y_dev, count, rr->d_out, nullptr);
+      rc = rr->run(y_dev, count, rr->d_out.get(), nullptr);
       if (rc) return rc;
-      HIPCHECK(hipMemcpyAsync(y + (size_t)first * rr->OH * rr->OW, rr->d_out, (size_t)count * rr->OH * rr->OW * sizeof(double), hipMemcpyDeviceToHost,
+      HIPCHECK(hipMemcpyAsync(y + (size_t)first * rr->OH * rr->OW, rr->d_out.get(), (size_t)count * rr->OH * rr->OW * sizeof(double), hipMemcpyDeviceToHost,
                               nullptr));
       return SRCFD_OK;
     });

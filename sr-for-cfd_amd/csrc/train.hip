@@ -453,7 +453,7 @@ struct TrainOp {
   size_t w_off, b_off;    // into the packed forward buffer (same layout as Model::pack)
   int layer;              // compute-layer ordinal
   std::vector<int> gmap;  // (K+1) x Npad -> flat param index + 1 (0: padding)
-  int* d_gmap = nullptr;
+  DevBuf<int> d_gmap;
   size_t part_off = 0, part_cap = 0;   // this op's own slab space in Trainer::d_part (floats)
 };
 
@@ -469,14 +469,41 @@ struct Trainer {
   // device
   // ONE packed operand buffer, gathered from the flat parameters by ONE launch at the head of a step:
   // [forward operands | data-gradient operands | the fused tail's operands (scaled slots)]
-  float* d_pack = nullptr; int* d_pack_map = nullptr; size_t pack_elems = 0;
-  float* d_dpack = nullptr; size_t dpack_off = 0, dpack_elems = 0;   // d_dpack = d_pack + dpack_off
-  float* d_zero_bias = nullptr; size_t zero_bias_elems = 0;
-  std::vector<float*> Z, Y;       // per compute layer (Y aliases Z for linear layers)
+  DevBuf<float> d_pack; DevBuf<int> d_pack_map; size_t pack_elems = 0;
+  float* d_dpack = nullptr; size_t dpack_off = 0, dpack_elems = 0;   // d_dpack = d_pack + dpack_off (a view)
+  DevBuf<float> d_zero_bias; size_t zero_bias_elems = 0;
+  std::vector<DevBuf<float>> Z, Y;   // per compute layer; Y is empty for a linear layer: y(li) is then Z
+  float* y(int li) const { return (Y[li] ? Y[li] : Z[li]).get(); }
   // dZ of every layer has a buffer of its own (dz[li], n x out_elems), + dpred with the fused tail: nothing in the backward
   // pass ever waits for a buffer to be free.
-  std::vector<float*> dz;
-  float* d_dpred = nullptr;
+  std::vector<DevBuf<float>> dz;
+  DevBuf<float> d_dpred;
+  int aux_from = -1;
+  bool packed_once = false;          // the operand packs were gathered at least once (SRCFD_TRAIN_SAME_PARAMS needs that)
+  bool overlap = true;                             // SRCFD_TRAIN_OVERLAP=0: everything on the caller's stream
+  bool use_graph = true;                           // SRCFD_TRAIN_GRAPH=0: plain launches
+  bool fuse_epilogues = true;                      // SRCFD_TRAIN_FUSE=0: stand-alone swish_fwd / swish_bwd passes
+  DevBuf<float> d_xs, d_ys; size_t x_elems = 0, y_elems = 0;   // per-sample sizes of the staging buffers
+  DevBuf<float> d_part;
+  DevBuf<float> d_splitk;
+  DevBuf<double> d_loss_partial;
+  // The last four layers as two launches (train_tail.h): tail32<TRAIN> forward, tail_bwd32 backward.  SRCFD_TRAIN_TAIL=0: layer by layer.
+  TrainTailPlan tail;
+  bool use_tail = false;
+  // encoder_10's four layers forward as two launches (train_enc.hip) instead of six.  SRCFD_TRAIN_ENC=0: layer by layer.
+  bool use_enc = false;
+  DevBuf<float> d_enc_partial;    // [50][max_batch][128]
+  int num_cus = 256;
+  size_t tail_pack_off = 0;          // the tail's operands sit behind the forward pack in d_pack
+  DevBuf<float> d_pack_scale;     // factors of those slots
+  DevBuf<float> d_tail_slabs;     // [num_cus][TT_PARAMS]
+  DevBuf<int> d_tail_gmap;        // slab slot -> flat parameter + 1
+  // Streams, events and graph executables come last: they are destroyed first, before the buffers above that they reference.
+  Event ev_fork;
+  // (A third stream for the slab sums was tried: two forked streams that wait on each other send hipStreamEndCapture into an
+  // endless recursion on ROCm 7.2, and with one-way dependencies the three-branch graph replayed level by level, 0.83 ms
+  // against 0.72 for two branches.  The sums are ONE launch at the end of the aux stream instead: wgrad_finish_all_f32.)
+  Event ev_fin;                                    // end of the aux stream's work of the step
   // The weight gradients of a layer depend only on its dZ and on the forward activations, not on the data-gradient chain.
   // In a replayed hipGraph every node with two successors costs ~10 us before EITHER successor starts (tools/prof_train_step.sh:
   // the data-gradient GEMM and the weight gradient of a layer started together, 9-11 us after their common predecessor), so
@@ -487,15 +514,8 @@ struct Trainer {
   // main stream, the two streams join once in front of the slab sums.  SRCFD_TRAIN_AUX_FROM=n moves the split (n >= number of
   // layers: one stream); measured at batch 8 / 16 / 32 (ms per step): n = 2: 0.463 / 0.606 / 0.863, 3: 0.447 / 0.586 / 0.833,
   // 4: 0.459 / 0.592 / 0.831, 5: 0.466 / - / 0.854, 6: 0.510 / - / 0.913; the per-layer forks of round 3: 0.503 / - / 0.90.
-  hipStream_t aux = nullptr;
-  int aux_from = -1;
-  bool packed_once = false;          // the operand packs were gathered at least once (SRCFD_TRAIN_SAME_PARAMS needs that)
-  hipEvent_t ev_fork = nullptr;
-  // (A third stream for the slab sums was tried: two forked streams that wait on each other send hipStreamEndCapture into an
-  // endless recursion on ROCm 7.2, and with one-way dependencies the three-branch graph replayed level by level, 0.83 ms
-  // against 0.72 for two branches.  The sums are ONE launch at the end of the aux stream instead: wgrad_finish_all_f32.)
-  hipEvent_t ev_fin = nullptr;                     // end of the aux stream's work of the step
-  bool overlap = true;                             // SRCFD_TRAIN_OVERLAP=0: everything on the caller's stream
+  Stream aux;
+  Stream cap_stream;
   // A step is ~100 launches and event operations of 5-40 us kernels: issued one by one the host cannot keep the device
   // fed (20 % of the step was idle gaps).  The second time a step with the same buffers and batch size is asked for it is
   // captured (both streams: the aux branch forks and joins inside the capture) and replayed as one hipGraph launch.
@@ -504,54 +524,11 @@ struct Trainer {
     const float* params = nullptr; float* grads = nullptr; double* sse = nullptr; int n = 0, flags = 0; float loss_scale = 0.f;
     bool operator==(const StepKey& o) const { return params == o.params && grads == o.grads && sse == o.sse && n == o.n && flags == o.flags && loss_scale == o.loss_scale; }
   };
-  struct StepGraph { StepKey key; int seen = 0; hipGraphExec_t exec = nullptr; };
+  struct StepGraph { StepKey key; int seen = 0; GraphExec exec; };
   std::vector<StepGraph> graphs;                   // at most 8 keys (full batches, the ragged last batch, ...)
-  bool use_graph = true;                           // SRCFD_TRAIN_GRAPH=0: plain launches
-  bool fuse_epilogues = true;                      // SRCFD_TRAIN_FUSE=0: stand-alone swish_fwd / swish_bwd passes
-  hipStream_t cap_stream = nullptr;
-  float* d_xs = nullptr; float* d_ys = nullptr; size_t x_elems = 0, y_elems = 0;   // per-sample sizes of the staging buffers
-  float* d_part = nullptr; size_t part_elems = 0;
-  float* d_splitk = nullptr; size_t splitk_floats = 0;
-  double* d_loss_partial = nullptr;
-  // The last four layers as two launches (train_tail.h): tail32<TRAIN> forward, tail_bwd32 backward.  SRCFD_TRAIN_TAIL=0: layer by layer.
-  TrainTailPlan tail;
-  bool use_tail = false;
-  // encoder_10's four layers forward as two launches (train_enc.hip) instead of six.  SRCFD_TRAIN_ENC=0: layer by layer.
-  bool use_enc = false;
-  float* d_enc_partial = nullptr;    // [50][max_batch][128]
-  int num_cus = 256;
-  size_t tail_pack_off = 0;          // the tail's operands sit behind the forward pack in d_pack
-  float* d_pack_scale = nullptr;     // factors of those slots
-  float* d_tail_slabs = nullptr;     // [num_cus][TT_PARAMS]
-  int* d_tail_gmap = nullptr;        // slab slot -> flat parameter + 1
-  ~Trainer();
+  // A replayed step graph runs its aux branch on a stream of the runtime's own: destroyed before the DEVICE had drained, it kept 56 MiB (measured).
+  ~Trainer() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }   // then the members' destructors (device_mem.h)
 };
-
-Trainer::~Trainer() {
-  (void)hipSetDevice(device);
-  for (auto& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  if (cap_stream) (void)hipStreamDestroy(cap_stream);
-  if (aux) { (void)hipStreamSynchronize(aux); (void)hipStreamDestroy(aux); }
-  if (ev_fin) (void)hipEventDestroy(ev_fin);
-  if (ev_fork) (void)hipEventDestroy(ev_fork);
-  if (d_xs) (void)hipFree(d_xs);
-  if (d_ys) (void)hipFree(d_ys);
-  for (float* b : dz) if (b) (void)hipFree(b);
-  for (void* p : {(void*)d_pack, (void*)d_pack_map, (void*)d_dpred, (void*)d_enc_partial, (void*)d_zero_bias, (void*)d_part, (void*)d_loss_partial, (void*)d_splitk, (void*)d_pack_scale, (void*)d_tail_slabs,
-                  (void*)d_tail_gmap})
-    if (p) (void)hipFree(p);
-  for (size_t i = 0; i < Z.size(); ++i) {
-    if (Y[i] && Y[i] != Z[i]) (void)hipFree(Y[i]);
-    if (Z[i]) (void)hipFree(Z[i]);
-  }
-  for (auto& o : ops) if (o.d_gmap) (void)hipFree(o.d_gmap);
-}
-
-static int upload_map(const std::vector<int>& m, int** d_map) {
-  HIPCHECK(hipMalloc(d_map, std::max<size_t>(m.size(), 1) * sizeof(int)));
-  HIPCHECK(hipMemcpy(*d_map, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice));
-  return SRCFD_OK;
-}
 
 static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   t.device = model.device;
@@ -590,13 +567,12 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     t.use_tail = t.tail.ok && !(e && atoi(e) == 0) && (uint64_t)max_batch * t.tail.H * t.tail.W * t.tail.H * t.tail.W < (1ull << 32);
   }
   if (t.use_tail) {
-    HIPCHECK(hipMalloc(&t.d_pack_scale, t.tail.scale.size() * sizeof(float)));
-    HIPCHECK(hipMemcpy(t.d_pack_scale, t.tail.scale.data(), t.tail.scale.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHECK(hipMalloc(&t.d_tail_slabs, (size_t)t.num_cus * TT_PARAMS * sizeof(float)));
     std::vector<int> gm(TT_PARAMS);
     std::iota(gm.begin(), gm.end(), (int)t.tail.param_off + 1);
-    HIPCHECK(hipMalloc(&t.d_tail_gmap, TT_PARAMS * sizeof(int)));
-    HIPCHECK(hipMemcpy(t.d_tail_gmap, gm.data(), TT_PARAMS * sizeof(int), hipMemcpyHostToDevice));
+    int rc = t.d_pack_scale.upload(t.tail.scale);
+    if (!rc) rc = t.d_tail_slabs.alloc((size_t)t.num_cus * TT_PARAMS);
+    if (!rc) rc = t.d_tail_gmap.upload(gm);
+    if (rc) return rc;
   }
   size_t part_need = 0;   // every op has slab space of its own: the sum of one op never has to finish before the next op's slabs are written
   for (const Op& op : iops) {
@@ -609,8 +585,8 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     to.layer = ci;
     const GemmDesc& d = op.d;
     to.gmap = wgrad_gmap(op, ipack);
-    HIPCHECK(hipMalloc(&to.d_gmap, to.gmap.size() * sizeof(int)));
-    HIPCHECK(hipMemcpy(to.d_gmap, to.gmap.data(), to.gmap.size() * sizeof(int), hipMemcpyHostToDevice));
+    int rc = to.d_gmap.upload(to.gmap);
+    if (rc) return rc;
     size_t op_need = 1;
     for (int b = 1; b <= max_batch; ++b) {  // the slab count is not monotonic in the batch
       GemmDesc db = d;
@@ -623,15 +599,16 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     part_need += (op_need + 63) / 64 * 64;
     t.ops.push_back(std::move(to));
   }
-  t.part_elems = part_need;
-  HIPCHECK(hipMalloc(&t.d_part, t.part_elems * sizeof(float)));
+  int rc = t.d_part.alloc(part_need);
+  if (rc) return rc;
   {
     const char* e = getenv("SRCFD_TRAIN_ENC");
     bool ok = !(e && atoi(e) == 0) && t.ops.size() >= 5 && t.layers.size() >= 4;
     for (int i = 0; ok && i < 4; ++i) ok = t.ops[i].layer == i;                 // one op per layer, the first four layers
     ok = ok && t.ops[4].layer != 3 && train_enc_qualifies(t.ops[0].fwd, t.ops[1].fwd, t.ops[2].fwd, t.ops[3].fwd);
     t.use_enc = ok;
-    if (ok) HIPCHECK(hipMalloc(&t.d_enc_partial, (size_t)50 * max_batch * 128 * sizeof(float)));
+    if (ok) rc = t.d_enc_partial.alloc((size_t)50 * max_batch * 128);
+    if (rc) return rc;
   }
   // dgrad plan
   std::vector<float> dpack;
@@ -639,32 +616,33 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   const GatherMap gm = gather_map(ipack, dpack, t.use_tail ? &t.tail.map : nullptr);
   t.dpack_off = gm.dpack_off; t.dpack_elems = gm.dpack_elems; t.tail_pack_off = gm.tail_off;
   t.pack_elems = gm.map.size();
-  int rc = upload_map(gm.map, &t.d_pack_map);
+  rc = t.d_pack_map.upload(gm.map);
+  if (!rc) rc = t.d_pack.alloc(t.pack_elems);
   if (rc) return rc;
-  HIPCHECK(hipMalloc(&t.d_pack, t.pack_elems * sizeof(float)));
-  t.d_dpack = t.d_pack + t.dpack_off;
+  t.d_dpack = t.d_pack.get() + t.dpack_off;
   int maxn = 32;
   for (auto& o : t.dops) maxn = std::max(maxn, o.d.Npad);
   t.zero_bias_elems = maxn;
-  HIPCHECK(hipMalloc(&t.d_zero_bias, maxn * sizeof(float)));
-  HIPCHECK(hipMemset(t.d_zero_bias, 0, maxn * sizeof(float)));
+  rc = t.d_zero_bias.alloc(maxn);
+  if (rc) return rc;
+  HIPCHECK(hipMemset(t.d_zero_bias.get(), 0, maxn * sizeof(float)));
   // activations
   for (size_t li = 0; li < t.layers.size(); ++li) {
     const LayerInfo& L = t.layers[li];
-    float *z = nullptr, *y = nullptr;
+    t.Z.emplace_back();   // owned by the trainer from here on, whatever fails below
+    t.Y.emplace_back();
     if (!(t.use_tail && (int)li >= t.tail.first_layer)) {   // the fused tail keeps nothing of its four layers (0.6 GB at batch 32)
-      HIPCHECK(hipMalloc(&z, (size_t)max_batch * L.out_elems * sizeof(float)));
-      if (L.swish) HIPCHECK(hipMalloc(&y, (size_t)max_batch * L.out_elems * sizeof(float)));
-      else y = z;
+      rc = t.Z[li].alloc((size_t)max_batch * L.out_elems);
+      if (!rc && L.swish) rc = t.Y[li].alloc((size_t)max_batch * L.out_elems);
+      if (rc) return rc;
     }
-    t.Z.push_back(z);
-    t.Y.push_back(y);
   }
   {
     const int Lg = t.use_tail ? t.tail.first_layer : (int)t.layers.size();
-    t.dz.assign(Lg, nullptr);
-    for (int li = 0; li < Lg; ++li) HIPCHECK(hipMalloc(&t.dz[li], (size_t)max_batch * t.layers[li].out_elems * sizeof(float)));
-    if (t.use_tail) HIPCHECK(hipMalloc(&t.d_dpred, (size_t)max_batch * t.layers.back().out_elems * sizeof(float)));
+    t.dz.resize(Lg);
+    for (int li = 0; li < Lg && !rc; ++li) rc = t.dz[li].alloc((size_t)max_batch * t.layers[li].out_elems);
+    if (!rc && t.use_tail) rc = t.d_dpred.alloc((size_t)max_batch * t.layers.back().out_elems);
+    if (rc) return rc;
     const char* e = getenv("SRCFD_TRAIN_AUX_FROM");
     t.aux_from = e ? std::max(atoi(e), 0) : std::max(Lg - 4, 0);
   }
@@ -673,16 +651,18 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   { const char* e = getenv("SRCFD_TRAIN_FUSE"); t.fuse_epilogues = !(e && atoi(e) == 0); }
   if (t.use_graph) {
     t.x_elems = t.layers.front().in_elems; t.y_elems = t.layers.back().out_elems;
-    HIPCHECK(hipMalloc(&t.d_xs, (size_t)max_batch * t.x_elems * sizeof(float)));
-    HIPCHECK(hipMalloc(&t.d_ys, (size_t)max_batch * t.y_elems * sizeof(float)));
-    HIPCHECK(hipStreamCreateWithFlags(&t.cap_stream, hipStreamNonBlocking));
+    rc = t.d_xs.alloc((size_t)max_batch * t.x_elems);
+    if (!rc) rc = t.d_ys.alloc((size_t)max_batch * t.y_elems);
+    if (rc) return rc;
+    HIPCHECK(hipStreamCreateWithFlags(t.cap_stream.out(), hipStreamNonBlocking));
   }
   if (t.overlap) {
-    HIPCHECK(hipStreamCreateWithFlags(&t.aux, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&t.ev_fin, hipEventDisableTiming));
-    HIPCHECK(hipEventCreateWithFlags(&t.ev_fork, hipEventDisableTiming));
+    HIPCHECK(hipStreamCreateWithFlags(t.aux.out(), hipStreamNonBlocking));
+    HIPCHECK(hipEventCreateWithFlags(t.ev_fin.out(), hipEventDisableTiming));
+    HIPCHECK(hipEventCreateWithFlags(t.ev_fork.out(), hipEventDisableTiming));
   }
-  HIPCHECK(hipMalloc(&t.d_loss_partial, 1024 * sizeof(double)));
+  rc = t.d_loss_partial.alloc(1024);
+  if (rc) return rc;
   size_t sk = 0;
   for (int b = 1; b <= max_batch; ++b) {
     for (size_t i = 0; i < t.ops.size();) {  // the forward GEMMs of one layer are launched together: their slabs coexist
@@ -695,9 +675,7 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     }
     for (const DgradOp& op : t.dops) { GemmDesc d = op.d; d.M = b * d.MH * d.MW; sk = std::max(sk, gemm_splitk_ws_floats(d, false)); }
   }
-  t.splitk_floats = sk;
-  if (sk) HIPCHECK(hipMalloc(&t.d_splitk, sk * sizeof(float)));
-  return SRCFD_OK;
+  return sk ? t.d_splitk.alloc(sk) : SRCFD_OK;
 }
 
 static int trainer_step(Trainer& t, const float* params, const float* x, const float* y, int n, float loss_scale, float* grads, double* sse_dev,
@@ -711,8 +689,8 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   //    SRCFD_TRAIN_SAME_PARAMS: the caller vouches that params_dev holds what it held at this trainer's previous call (the second
   //    and later micro-batches of one optimiser step): the packs are still right, the launch is skipped.
   if (!((flags & SRCFD_TRAIN_SAME_PARAMS) && t.packed_once))
-    hipLaunchKernelGGL(gather_pack_f32, grid(t.pack_elems / 4), dim3(256), 0, s, params, t.d_pack_map, t.d_pack, (int64_t)t.pack_elems,
-                       (const float*)t.d_pack_scale, (int64_t)(t.use_tail ? t.tail_pack_off : t.pack_elems));
+    hipLaunchKernelGGL(gather_pack_f32, grid(t.pack_elems / 4), dim3(256), 0, s, params, t.d_pack_map.get(), t.d_pack.get(), (int64_t)t.pack_elems,
+                       (const float*)t.d_pack_scale.get(), (int64_t)(t.use_tail ? t.tail_pack_off : t.pack_elems));
   t.packed_once = true;
   // 2. forward, keeping Z (pre-activation) and Y (post) of every layer; with the fused tail the last four layers are one
   //    streaming launch that ends in the loss gradient (nothing of them is kept: tail_bwd32 recomputes what it needs)
@@ -722,14 +700,14 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   if (t.use_enc && Lg >= 4) {
     TrainEncParams q;
     q.x = x; q.n = n;
-    q.w0 = t.d_pack + t.ops[0].w_off; q.b0 = t.d_pack + t.ops[0].b_off;
-    q.w1 = t.d_pack + t.ops[1].w_off; q.b1 = t.d_pack + t.ops[1].b_off;
-    q.wd = t.d_pack + t.ops[2].w_off; q.bd = t.d_pack + t.ops[2].b_off;
-    q.wl = t.d_pack + t.ops[3].w_off; q.bl = t.d_pack + t.ops[3].b_off;
+    q.w0 = t.d_pack.get() + t.ops[0].w_off; q.b0 = t.d_pack.get() + t.ops[0].b_off;
+    q.w1 = t.d_pack.get() + t.ops[1].w_off; q.b1 = t.d_pack.get() + t.ops[1].b_off;
+    q.wd = t.d_pack.get() + t.ops[2].w_off; q.bd = t.d_pack.get() + t.ops[2].b_off;
+    q.wl = t.d_pack.get() + t.ops[3].w_off; q.bl = t.d_pack.get() + t.ops[3].b_off;
     q.nl = t.ops[3].fwd.N; q.nl_pad = t.ops[3].fwd.Npad;
     for (int li = 0; li < 4; ++li) q.swish[li] = t.layers[li].swish ? 1 : 0;
-    q.z0 = t.Z[0]; q.y0 = t.Y[0]; q.z1 = t.Z[1]; q.y1 = t.Y[1]; q.z2 = t.Z[2]; q.y2 = t.Y[2]; q.z3 = t.Z[3]; q.y3 = t.Y[3];
-    q.partial = t.d_enc_partial;
+    q.z0 = t.Z[0].get(); q.y0 = t.y(0); q.z1 = t.Z[1].get(); q.y1 = t.y(1); q.z2 = t.Z[2].get(); q.y2 = t.y(2); q.z3 = t.Z[3].get(); q.y3 = t.y(3);
+    q.partial = t.d_enc_partial.get();
     HIPCHECK(launch_train_enc(q, s));
     i0 = 4;
   }
@@ -743,40 +721,40 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     size_t j = i;
     for (; j < t.ops.size() && t.ops[j].layer == op.layer && cnt < 4; ++j) {  // ConvT output phases: one launch
       ds[cnt] = t.ops[j].fwd; ds[cnt].M = n * ds[cnt].MH * ds[cnt].MW;
-      Bs[cnt] = t.d_pack + t.ops[j].w_off; biases[cnt] = t.d_pack + t.ops[j].b_off;
+      Bs[cnt] = t.d_pack.get() + t.ops[j].w_off; biases[cnt] = t.d_pack.get() + t.ops[j].b_off;
       ++cnt;
     }
-    const float* X = op.layer == 0 ? x : t.Y[op.layer - 1];
+    const float* X = op.layer == 0 ? x : t.y(op.layer - 1);
     // swish layers: the GEMM epilogue stores both Z and swish(Z) (EpiAux mode 1) when every GEMM of the layer takes it
     bool fuse = t.fuse_epilogues && t.layers[op.layer].swish;
     for (int q = 0; fuse && q < cnt; ++q) fuse = gemm_supports_epi_aux(ds[q]);
     EpiAux aux;
-    if (fuse) { aux.mode = 1; aux.y2 = t.Y[op.layer]; }
-    HIPCHECK(launch_gemm_mfma_group(ds, cnt, X, Bs, biases, t.Z[op.layer], s, t.d_splitk, t.splitk_floats, false, aux));
+    if (fuse) { aux.mode = 1; aux.y2 = t.y(op.layer); }
+    HIPCHECK(launch_gemm_mfma_group(ds, cnt, X, Bs, biases, t.Z[op.layer].get(), s, t.d_splitk.get(), t.d_splitk.size(), false, aux));
     i = j;
     const bool last_of_layer = i == t.ops.size() || t.ops[i].layer != op.layer;
     if (last_of_layer && t.layers[op.layer].swish && !fuse) {
       int64_t e = (int64_t)n * t.layers[op.layer].out_elems;
-      hipLaunchKernelGGL(swish_fwd_f32, grid(e), dim3(256), 0, s, t.Z[op.layer], t.Y[op.layer], e);
+      hipLaunchKernelGGL(swish_fwd_f32, grid(e), dim3(256), 0, s, t.Z[op.layer].get(), t.y(op.layer), e);
     }
   }
   // 3. loss and its gradient (sr-ae-conv.ipynb:c314): sum of squared errors; dpred = 2 scale (pred - y)
   int nb;
-  const float* tp = t.d_pack + t.tail_pack_off;
+  const float* tp = t.d_pack.get() + t.tail_pack_off;
   if (t.use_tail) {
     Tail32Params q;
-    q.in = t.Y[Lg - 1]; q.out = t.d_dpred; q.n = n; q.H = t.tail.H; q.W = t.tail.W;
+    q.in = t.y(Lg - 1); q.out = t.d_dpred.get(); q.n = n; q.H = t.tail.H; q.W = t.tail.W;
     q.w1f = tp + t.tail.t32_w1; q.b1 = tp + t.tail.t32_b1; q.w2f = tp + t.tail.t32_w2; q.b2 = tp + t.tail.t32_b2;
     q.w3f = tp + t.tail.t32_w3; q.b3 = tp + t.tail.t32_b3; q.wc = tp + t.tail.t32_wc;
     q.aff_out = nullptr; q.nan_guard = 0; q.nonfinite = nullptr; q.out_dtype = SRCFD_F32;
     q.seg = tail32_segments(n, q.H, t.num_cus);
-    q.target = y; q.two_scale = 2.0f * loss_scale; q.sse_partial = t.d_loss_partial;
+    q.target = y; q.two_scale = 2.0f * loss_scale; q.sse_partial = t.d_loss_partial.get();
     nb = tail32_blocks(n, q.seg, t.num_cus);
     HIPCHECK(launch_tail32(q, t.num_cus, s));
   } else {
     int64_t oe = (int64_t)n * t.layers[L - 1].out_elems;
     nb = (int)std::min<int64_t>(1024, (oe + 255) / 256);
-    hipLaunchKernelGGL(mse_grad_f32, dim3(nb), dim3(256), 0, s, t.Y[L - 1], y, t.dz[L - 1], oe, loss_scale, t.d_loss_partial);
+    hipLaunchKernelGGL(mse_grad_f32, dim3(nb), dim3(256), 0, s, t.y(L - 1), y, t.dz[L - 1].get(), oe, loss_scale, t.d_loss_partial.get());
   }
   // 4. backward.  Main stream: [tail_bwd32 ->] swish' -> data gradient -> swish' -> ... (the dependent chain), then the weight
   //    gradients of the layers below aux_from; second stream, forked ONCE (when dZ of layer aux_from exists): the weight
@@ -789,13 +767,13 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   bool sse_pending = sse_dev != nullptr;
   if (t.use_tail) {      // every gradient of the last four layers + dZ of layer Lg - 1, from dpred and that layer's Z / Y
     TailBwdParams q;
-    q.y1 = t.Y[Lg - 1]; q.z1 = t.Z[Lg - 1]; q.dpred = t.d_dpred; q.dz1 = t.dz[Lg - 1]; q.slabs = t.d_tail_slabs;
+    q.y1 = t.y(Lg - 1); q.z1 = t.Z[Lg - 1].get(); q.dpred = t.d_dpred.get(); q.dz1 = t.dz[Lg - 1].get(); q.slabs = t.d_tail_slabs.get();
     q.wf = tp + t.tail.wf; q.wb = tp + t.tail.wb; q.wt = tp + t.tail.wt; q.bias = tp + t.tail.bias;
     q.n = n; q.H = t.tail.H; q.W = t.tail.W;
     HIPCHECK(launch_tail_bwd32(q, t.num_cus, s));
     dz_done = true;
     FinishOp& fo = ftab.op[ftab.nops++];
-    fo.part = t.d_tail_slabs; fo.map = t.d_tail_gmap; fo.elems = TT_PARAMS; fo.nslices = tail_bwd32_blocks(n, q.H, q.W, t.num_cus);
+    fo.part = t.d_tail_slabs.get(); fo.map = t.d_tail_gmap.get(); fo.elems = TT_PARAMS; fo.nslices = tail_bwd32_blocks(n, q.H, q.W, t.num_cus);
     fo.K = 0x7fffffff; fo.N = 1; fo.Npad = 1; fo.CO = 1;   // one column, no bias row: every slot is a parameter of its own
     fo.groups = fo.nslices >= 256 ? 32 : (fo.nslices >= 64 ? 8 : (fo.nslices >= 8 ? 4 : 1));
     fo.block0 = fblocks; fo.bias_skip = 0; fo.nextra = 0;
@@ -803,7 +781,7 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   }
   // the weight gradients of layer li on stream st: one wgrad launch per op, the slab sums entered in the table
   auto wgrad_layer = [&](const int li, hipStream_t st) -> int {
-    const float* X = li == 0 ? x : t.Y[li - 1];
+    const float* X = li == 0 ? x : t.y(li - 1);
     int first = -1;
     for (const TrainOp& op : t.ops) {
       if (op.layer != li) continue;
@@ -812,13 +790,13 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
       const WgradPlan wp = wgrad_plan(d);
       const int64_t elems = (int64_t)(d.K + 1) * d.Npad;
       if ((size_t)wp.nslices * elems > op.part_cap) { set_error("training: gradient slab buffer too small"); return SRCFD_EINVAL; }
-      float* part = t.d_part + op.part_off;
-      launch_wgrad(d, wp, X, t.dz[li], part, st);
+      float* part = t.d_part.get() + op.part_off;
+      launch_wgrad(d, wp, X, t.dz[li].get(), part, st);
       const int groups = wp.nslices >= 256 ? 32 : (wp.nslices >= 64 ? 8 : (wp.nslices >= 8 ? 4 : 1)), epb = 256 / groups;
       if (ftab.nops >= MAX_FINISH_OPS) { set_error("training: more weight-gradient ops than the finish table holds"); return SRCFD_EINVAL; }
       const int me = ftab.nops++;
       FinishOp& fo = ftab.op[me];
-      fo.part = part; fo.map = op.d_gmap; fo.elems = elems; fo.nslices = wp.nslices; fo.K = d.K; fo.N = d.N; fo.Npad = d.Npad; fo.CO = d.CO;
+      fo.part = part; fo.map = op.d_gmap.get(); fo.elems = elems; fo.nslices = wp.nslices; fo.K = d.K; fo.N = d.N; fo.Npad = d.Npad; fo.CO = d.CO;
       fo.groups = groups; fo.block0 = fblocks; fo.bias_skip = 0; fo.nextra = 0;
       fblocks += (int)((elems + epb - 1) / epb);
       // ops of one layer (the output phases of ConvT#0) share the layer's bias: the first one sums the others' bias rows too
@@ -833,27 +811,27 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     return SRCFD_OK;
   };
   for (int li = Lg - 1; li >= 0; --li) {
-    float* dZ = t.dz[li];
+    float* dZ = t.dz[li].get();
     int64_t e = (int64_t)n * t.layers[li].out_elems;
-    if (t.layers[li].swish && !dz_done) hipLaunchKernelGGL(swish_bwd_f32, grid(e), dim3(256), 0, s, t.Z[li], dZ, e);
+    if (t.layers[li].swish && !dz_done) hipLaunchKernelGGL(swish_bwd_f32, grid(e), dim3(256), 0, s, t.Z[li].get(), dZ, e);
     dz_done = false;
     if (li == aux_from) {          // the one fork: dZ of the layers aux_from .. Lg - 1 exist
       HIPCHECK(hipEventRecord(t.ev_fork, s));
       HIPCHECK(hipStreamWaitEvent(t.aux, t.ev_fork, 0));
       for (int lj = Lg - 1; lj >= aux_from; --lj) { const int rc = wgrad_layer(lj, t.aux); if (rc) return rc; }
-      if (sse_pending) { hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, t.aux, t.d_loss_partial, nb, sse_dev, overwrite); sse_pending = false; }
+      if (sse_pending) { hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, t.aux, t.d_loss_partial.get(), nb, sse_dev, overwrite); sse_pending = false; }
     }
     if (li > 0) {
       const DgradOp& dg = t.dops[li - 1];
       GemmDesc d = dg.d;
       d.M = n * d.MH * d.MW;
       EpiAux aux;
-      if (t.fuse_epilogues && t.layers[li - 1].swish && gemm_supports_epi_aux(d)) { aux.mode = 2; aux.zaux = t.Z[li - 1]; dz_done = true; }
-      HIPCHECK(launch_gemm_mfma(d, dZ, t.d_dpack + dg.w_off, t.d_zero_bias, t.dz[li - 1], s, t.d_splitk, t.splitk_floats, false, aux));
+      if (t.fuse_epilogues && t.layers[li - 1].swish && gemm_supports_epi_aux(d)) { aux.mode = 2; aux.zaux = t.Z[li - 1].get(); dz_done = true; }
+      HIPCHECK(launch_gemm_mfma(d, dZ, t.d_dpack + dg.w_off, t.d_zero_bias.get(), t.dz[li - 1].get(), s, t.d_splitk.get(), t.d_splitk.size(), false, aux));
     }
   }
   for (int li = std::min(aux_from, Lg) - 1; li >= 0; --li) { const int rc = wgrad_layer(li, s); if (rc) return rc; }
-  if (sse_pending) hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, s, t.d_loss_partial, nb, sse_dev, overwrite);
+  if (sse_pending) hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, s, t.d_loss_partial.get(), nb, sse_dev, overwrite);
   if (aux_from < Lg) {
     HIPCHECK(hipEventRecord(t.ev_fin, t.aux));
     HIPCHECK(hipStreamWaitEvent(s, t.ev_fin, 0));  // aux is in order: this covers all of its kernels
@@ -933,11 +911,11 @@ int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev,
     if (((uintptr_t)x_dev | (uintptr_t)y_dev) % 16 == 0 && xe % 4 == 0 && ye % 4 == 0) {
       const int64_t nx = (int64_t)(xe / 4), ny = (int64_t)(ye / 4);
       hipLaunchKernelGGL(srcfd::stage_xy_f32, dim3((unsigned)std::min<int64_t>(2048, (nx + ny + 255) / 256)), dim3(256), 0, s,
-                         reinterpret_cast<const float4*>(x_dev), reinterpret_cast<float4*>(tt.d_xs), nx, reinterpret_cast<const float4*>(y_dev),
-                         reinterpret_cast<float4*>(tt.d_ys), ny);
+                         reinterpret_cast<const float4*>(x_dev), reinterpret_cast<float4*>(tt.d_xs.get()), nx, reinterpret_cast<const float4*>(y_dev),
+                         reinterpret_cast<float4*>(tt.d_ys.get()), ny);
     } else {
-      HIPCHECK(hipMemcpyAsync(tt.d_xs, x_dev, xe * sizeof(float), hipMemcpyDeviceToDevice, s));
-      HIPCHECK(hipMemcpyAsync(tt.d_ys, y_dev, ye * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(tt.d_xs.get(), x_dev, xe * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(tt.d_ys.get(), y_dev, ye * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     Trainer::StepKey key;
     key.params = params_dev; key.grads = grads_dev; key.sse = sse_dev; key.n = n; key.flags = flags; key.loss_scale = loss_scale;
@@ -947,19 +925,19 @@ int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev,
     if (slot && slot->exec) { HIPCHECK(hipGraphLaunch(slot->exec, s)); return SRCFD_OK; }
     if (slot && ++slot->seen == 2) {  // every one-time set-up (function attributes, ...) happened on the first, plain pass
       HIPCHECK(hipStreamBeginCapture(tt.cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = srcfd::trainer_step(tt, params_dev, tt.d_xs, tt.d_ys, n, loss_scale, grads_dev, sse_dev, flags, tt.cap_stream);
+      int rc = srcfd::trainer_step(tt, params_dev, tt.d_xs.get(), tt.d_ys.get(), n, loss_scale, grads_dev, sse_dev, flags, tt.cap_stream);
       hipGraph_t g = nullptr;
       hipError_t e = hipStreamEndCapture(tt.cap_stream, &g);
       if (rc == SRCFD_OK && e == hipSuccess && g) {
-        e = hipGraphInstantiate(&slot->exec, g, nullptr, nullptr, 0);
+        e = hipGraphInstantiate(slot->exec.out(), g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e == hipSuccess) { HIPCHECK(hipGraphLaunch(slot->exec, s)); return SRCFD_OK; }
-        slot->exec = nullptr;
+        slot->exec.reset();
       } else if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();  // capture not possible here: plain launches from now on for this key
       slot->seen = 3;
     }
-    return srcfd::trainer_step(tt, params_dev, tt.d_xs, tt.d_ys, n, loss_scale, grads_dev, sse_dev, flags, s);
+    return srcfd::trainer_step(tt, params_dev, tt.d_xs.get(), tt.d_ys.get(), n, loss_scale, grads_dev, sse_dev, flags, s);
   });
 }
 

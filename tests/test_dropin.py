@@ -214,10 +214,22 @@ def test_harness_bfs_with_resampling_and_blend_matches_reference_recipe(srcfd, o
         assert np.linalg.norm(out[c] - ref[c]) / scale <= 2e-5
 
 
+def page_locked(shape):
+    """A float32 array over a srcfd_host_alloc buffer, and the call that frees the buffer."""
+    import ctypes as C
+    L = importlib.import_module("sr-for-cfd_amd._lib")
+    nbytes = int(np.prod(shape)) * 4
+    p = C.c_void_p()
+    L.check(L.lib.srcfd_host_alloc(nbytes, C.byref(p)))
+    return np.frombuffer((C.c_char * nbytes).from_address(p.value), dtype=np.float32).reshape(shape), lambda: L.lib.srcfd_host_free(p)
+
+
 @pytest.mark.gpu
 def test_reserve_is_the_set_up_a_first_call_would_do(srcfd, enc_weights, dec_weights):
     """srcfd_model_reserve(n): the lazy set-up of a forward (16-bit operand packs, activation workspaces) done on request;
-    results are those of an unreserved handle, a smaller or repeated reserve is a no-op, a larger one re-allocates."""
+    results are those of an unreserved handle, a smaller or repeated reserve is a no-op, a larger one re-allocates.
+    The buffers that grow without a reserve call likewise: a resampler's planes and the staging buffers of the host entry,
+    after growing, give the bits of a handle that was never smaller."""
     require_gpu(srcfd)
     rng = np.random.default_rng(31)
     x = rng.standard_normal((7, 10, 10, 1)).astype(np.float32)
@@ -233,6 +245,32 @@ def test_reserve_is_the_set_up_a_first_call_would_do(srcfd, enc_weights, dec_wei
         b.reserve(40)
         np.testing.assert_array_equal(b.predict(x), ya)
         np.testing.assert_array_equal(b.predict(np.concatenate([x] * 5))[7:14], ya)
+    # a resampler applied to 2 fields, then to 5 (Resampler::reserve)
+    import torch
+    rs = importlib.import_module("sr-for-cfd_amd.resample")
+    Ry, Rx = rng.standard_normal((37, 40)), rng.standard_normal((70, 40))
+    f = torch.from_numpy(rng.standard_normal((5, 40, 40)).astype(np.float32)).cuda()
+    grown, fresh = rs.Resampler(Ry, Rx, 0), rs.Resampler(Ry, Rx, 0)
+    grown.apply_device(f[:2])
+    assert torch.equal(grown.apply_device(f), fresh.apply_device(f))
+    # 4 samples, then 300 into pageable memory (the staging buffers grow), then the same 300 into a page-locked array (the second
+    # result buffer, the copy stream and its events are created late)
+    xs = rng.standard_normal((300, 10, 10, 1)).astype(np.float32)
+    grown = srcfd.SRModel.from_weights(enc_weights, dec_weights, device=0)
+    fresh = srcfd.SRModel.from_weights(enc_weights, dec_weights, device=0)
+    grown.precision = fresh.precision = "bf16"
+    ref, y = np.empty((300, 400, 400, 1), np.float32), np.empty((300, 400, 400, 1), np.float32)
+    fresh.predict(xs, out=ref)
+    grown.predict(xs[:4], out=y[:4])
+    grown.predict(xs, out=y)
+    np.testing.assert_array_equal(y, ref)
+    y_locked, free_locked = page_locked(ref.shape)
+    try:
+        grown.predict(xs, out=y_locked)
+        np.testing.assert_array_equal(y_locked, ref)
+    finally:
+        del y_locked
+        free_locked()
 
 
 @pytest.mark.gpu

@@ -263,27 +263,44 @@ def test_full_size_batch256_properties(srcfd, oracle, enc_weights, dec_weights, 
 
 
 def test_handles_release_their_device_memory(srcfd, enc_weights, dec_weights):
-    """Create / use / destroy models, trainers and resamplers repeatedly: free device memory must come back
-    (every hipMalloc of a handle is released by its destroy call)."""
+    """Create / use / destroy models, trainers, resamplers and fine-mesh batches repeatedly, reaching every owner of device
+    memory, streams, events and graph executables in them: free device memory must come back (every hipMalloc of a handle is
+    released by its destroy call).  The trainer is closed with its captured two-stream step graph just replayed and no device-wide
+    wait in between: destroyed like that, a trainer that only waited for its own streams lost 56 MiB per cycle."""
     require_gpu(srcfd)
     import gc
     import importlib
     import torch
+    from test_dropin import page_locked
     tr = importlib.import_module("sr-for-cfd_amd.train")
     rs = importlib.import_module("sr-for-cfd_amd.resample")
+    fine = importlib.import_module("sr-for-cfd_amd.fine")
     x = np.random.default_rng(1).standard_normal((4, 10, 10, 1)).astype(np.float32)
 
     def cycle():
         m = srcfd.SRModel.from_weights(enc_weights, dec_weights, device=0)
-        for prec in ("fp32", "bf16", "f16"):
+        for prec in ("fp32", "fp32x3", "bf16", "f16"):
             m.precision = prec
             m.predict(x)
+        y_locked, free_locked = page_locked((4, 400, 400, 1))   # the copy stream, its four events, the second result buffer
+        m.predict(x, out=y_locked)
+        del y_locked
+        free_locked()
+        xd, yd = torch.from_numpy(x[:3]).cuda(), torch.empty((3, 400, 400, 1), device="cuda")
+        for _ in range(3):                                      # the second call captures a graph, the third replays it
+            m.predict_device(xd, yd)
+        assert m.last_plan()["graph"] == "replay"
+        m.predict_into_solver_state(x[:3], np.zeros((3, 4), np.int32), np.zeros((3, 4)))
         t = tr.Trainer(m, max_batch=2)
-        t.step(torch.from_numpy(x[:2]).cuda(), torch.zeros((2, 400, 400, 1), device="cuda"))
+        xt, yt = torch.from_numpy(x[:2]).cuda(), torch.zeros((2, 400, 400, 1), device="cuda")
+        for _ in range(2):                                      # the second identical step is captured
+            t.step(xt, yt)
         r = rs.Resampler(np.eye(400), np.eye(400), 0)
         m.predict_resampled(x[:3], r)
-        t.close(); r.close(); m.close()
-        del t, r, m
+        b = fine.FineSolverBatch([fine.problem(100.0, 12, 10), fine.problem(200.0, 12, 10)])
+        b.run(2)
+        t.close(); r.close(); b.close(); m.close()
+        del t, r, b, m
         gc.collect()
 
     cycle()  # first cycle: one-time allocations of the runtime itself
