@@ -59,7 +59,13 @@ typedef enum { SRCFD_ACT_LINEAR = 0, SRCFD_ACT_SWISH = 1, SRCFD_ACT_RELU = 2, SR
 
 /* One Keras layer (sr-ae-conv.ipynb:c162-169, c277-287).  Kernel layouts are
  * Keras': Conv2D (kh,kw,Cin,Cout); Conv2DTranspose (kh,kw,Cout,Cin); Dense
- * (in,out).  Pointers are host memory, copied at create. */
+ * (in,out).  Pointers are host memory, copied at create.
+ * same_padding, per axis with kernel k and stride s:
+ *   Conv2D:           0 'valid': out = (in - k) / s + 1;  1 'same': out = ceil(in / s), TensorFlow's padding (the odd pixel goes after).
+ *   Conv2DTranspose:  0 'valid': out = (in - 1) s + k, full[s i + a] += x[i] W[a] (no kernel flip);
+ *                     1 'same':  out = in s, rows [pb, pb + in s) of that 'valid' result, pb = (k - s) / 2 (integer division);
+ *                                bias and activation come after the crop.  k = 3, s = 2: pb = 0, the LAST row and column go.
+ *                                k == s: the same layer as 'valid'.  k < s is refused at create / load. */
 typedef struct {
   int kind;        /* srcfd_layer_kind */
   int activation;  /* srcfd_activation */
@@ -118,6 +124,12 @@ int srcfd_model_reserve(srcfd_model* m, int n);
 int srcfd_model_footprint(const srcfd_model* m, int n, int precision, size_t bytes[4]);
 /* 1 when the bf16/f16 fused decoder_400 kernels apply to this layer graph. */
 int srcfd_model_has_fused_path(const srcfd_model* m);
+/* 1 when srcfd_model_set_precision(m, precision) would be accepted (works on a host-only handle).  The f32 precisions: every graph.
+ * SRCFD_PREC_BF16 / SRCFD_PREC_F16: the fused graph above, or a graph whose first four compute layers are encoder_10's, that ends
+ * in a 3x3 stride-1 'same' Conv2D to ONE channel (linear, 16 .. 64 input channels, a multiple of 16) and whose layers in between are
+ * Dense or 2x2 / 3x3 stride-2 Conv2DTranspose ('valid' or 'same'), swish or linear, input channels a multiple of 16: encoder_10 +
+ * decoder_{10,20,50,80,100} of the notebook.  Those run layer by layer (srcfd_model_last_plan: decoder=any16). */
+int srcfd_model_supports_precision(const srcfd_model* m, int precision);
 
 /* ---- forward -------------------------------------------------------------
  * srcfd_predict replaces `inference_model.predict(x, verbose=0)`

@@ -116,6 +116,7 @@ Model::~Model() {
     (void)hipSetDevice(device);   // for the members' destructors (device_mem.h)
     fused_free(*this);
   }
+  any16_free(*this);   // a host-only handle holds the plan only
 }
 
 Switches Switches::from_env() {
@@ -155,6 +156,11 @@ int Model::init_device() {
   int rc = d_pack.upload(pack);
   return rc ? rc : d_pack_x3.upload(pack_x3);
 }
+
+// bf16 / f16 need 16-bit kernels for every layer: the fused encoder_10 + decoder_400 kernels, or any16_forward's layer loop
+static const char* const LOWP_REFUSAL =
+    "bf16/f16 precision needs encoder_10 in front, Dense / 2x2 or 3x3 stride-2 Conv2DTranspose layers with input channels a multiple of 16 behind it and a "
+    "3x3 'same' Conv2D to one channel at the end (the encoder_10+decoder_400 layer graph is one); use SRCFD_PREC_FP32 for other graphs";
 
 static bool tail32_disabled() {
   static const bool off = [] { const char* e = getenv("SRCFD_NO_TAIL32"); return e && atoi(e) != 0; }();
@@ -403,8 +409,9 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   sw = Switches::from_env();
   const bool use_fused = (precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16);
   plan = Plan();
-  plan.sw = sw; plan.precision = precision; plan.fused = use_fused;
-  if (use_fused && !has_fused) { set_error("bf16/f16 precision needs the encoder_10+decoder_400 layer graph; use SRCFD_PREC_FP32 for other graphs"); return SRCFD_EINVAL; }
+  const bool use_any16 = use_fused && !has_fused && any16;
+  plan.sw = sw; plan.precision = precision; plan.fused = use_fused && !use_any16; plan.any16 = use_any16;
+  if (use_fused && !lowp_ok()) { set_error(LOWP_REFUSAL); return SRCFD_EINVAL; }
   if (!use_fused) {
     int rc = ensure_workspace(n);  // (re)allocates before anything is captured; drops a stale graph when it does
     if (rc) return rc;
@@ -414,6 +421,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   const size_t out_elems = (size_t)os[0] * os[1] * os[2];
   const size_t osz = out_dtype == SRCFD_F32 ? 4 : 2;
   auto run = [&](hipStream_t st) -> int {
+    if (use_any16) return any16_forward(*this, (const float*)x_dev, n, aff_in, aff_out, y_dev, out_dtype, flags, nonfinite, st);
     if (use_fused) return fused_forward(*this, (const float*)x_dev, n, aff_in, aff_out, y_dev, out_dtype, flags, nonfinite, st);
     for (int i = 0; i < n; i += ws_chunk) {
       int c = std::min(ws_chunk, n - i);
@@ -566,10 +574,15 @@ static int finish_create(std::unique_ptr<Model>& m, srcfd_model** out) {
     return SRCFD_EINVAL;
   }
   m->has_fused = m->desc.is_sr_10_400();
+  if (!m->has_fused) any16_create(*m);   // host only: which other graphs run in bf16 / f16 (srcfd_model_supports_precision)
   int rc = m->init_device();
   if (rc) return rc;
   if (m->device >= 0 && m->has_fused) {
     rc = fused_init(*m);
+    if (rc) return rc;
+  }
+  if (m->device >= 0 && m->any16) {
+    rc = any16_init(*m);
     if (rc) return rc;
   }
   *out = reinterpret_cast<srcfd_model*>(m.release());
@@ -754,8 +767,8 @@ int64_t srcfd_model_macs_per_sample(const srcfd_model* m) { return m ? M(m)->des
 int srcfd_model_set_precision(srcfd_model* m, int precision) {
   return srcfd::abi_guard("srcfd_model_set_precision", [&]() -> int {
     if (!m || precision < 0 || precision > SRCFD_PREC_FP32X3) { set_error("bad precision"); return SRCFD_EINVAL; }
-    if ((precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16) && !M(m)->has_fused) {
-      set_error("bf16/f16 precision needs the encoder_10+decoder_400 layer graph");
+    if ((precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16) && !M(m)->lowp_ok()) {
+      set_error(srcfd::LOWP_REFUSAL);
       return SRCFD_EINVAL;
     }
     M(m)->precision = precision;
@@ -771,8 +784,8 @@ int srcfd_model_reserve(srcfd_model* m, int n) {
     if (n == 0) return SRCFD_OK;
     HIPCHECK(hipSetDevice(mm.device));
     if (mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) {
-      if (!mm.has_fused) { set_error("bf16/f16 precision needs the encoder_10+decoder_400 layer graph; use SRCFD_PREC_FP32 for other graphs"); return SRCFD_EINVAL; }
-      return srcfd::fused_reserve(mm, n);
+      if (!mm.lowp_ok()) { set_error(srcfd::LOWP_REFUSAL); return SRCFD_EINVAL; }
+      return mm.has_fused ? srcfd::fused_reserve(mm, n) : srcfd::any16_reserve(mm, n);
     }
     return mm.ensure_workspace(n);
   });
@@ -780,6 +793,7 @@ int srcfd_model_reserve(srcfd_model* m, int n) {
 
 int srcfd_model_get_precision(const srcfd_model* m) { return m ? M(m)->precision : SRCFD_EINVAL; }
 int srcfd_model_has_fused_path(const srcfd_model* m) { return m ? (int)M(m)->has_fused : 0; }
+int srcfd_model_supports_precision(const srcfd_model* m, int precision) { return (!m || precision < 0 || precision > SRCFD_PREC_FP32X3) ? 0 : (precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16) ? (int)M(m)->lowp_ok() : 1; }
 
 int srcfd_predict(srcfd_model* m, const float* x, int n, const float* in_affine, const float* out_affine, float* y, int flags,
                   int64_t* n_nonfinite) {
@@ -801,6 +815,12 @@ int srcfd_predict_device(srcfd_model* m, const void* x_dev, int n, const float* 
 int srcfd_model_workspace(srcfd_model* m, int n, size_t* bytes) {
   return srcfd::abi_guard("srcfd_model_workspace", [&]() -> int {
     if (!m) { set_error("null model"); return SRCFD_EINVAL; }
+    const Model& mm = *M(m);
+    if ((mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) && !mm.has_fused && mm.any16) {   // any16_forward: chunks of up to 1024 samples
+      const int chunk16 = std::min(std::max(n, 1), 1024);
+      if (bytes) *bytes = srcfd::any16_workspace_bytes(mm, chunk16);
+      return chunk16;
+    }
     int chunk = std::min(std::max(n, 1), M(m)->chunk_cap());
     if (bytes) *bytes = 2 * (size_t)chunk * M(m)->max_act_elems() * sizeof(float);
     return chunk;
@@ -812,14 +832,17 @@ int srcfd_model_footprint(const srcfd_model* m, int n, int precision, size_t byt
     if (!m || !bytes || n < 0 || precision < 0 || precision > SRCFD_PREC_FP32X3) { set_error("bad arguments"); return SRCFD_EINVAL; }
     const srcfd::Model& mm = *M(m);
     const bool lowp = precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16;
-    if (lowp && !mm.has_fused) { set_error("bf16/f16 precision needs the encoder_10+decoder_400 layer graph"); return SRCFD_EINVAL; }
+    if (lowp && !mm.lowp_ok()) { set_error(srcfd::LOWP_REFUSAL); return SRCFD_EINVAL; }
     int shp_in[3] = {0, 0, 0}, shp_out[3] = {0, 0, 0};
     (void)srcfd_model_input_shape(m, shp_in);
     (void)srcfd_model_output_shape(m, shp_out);
     const size_t in_elems = (size_t)shp_in[0] * shp_in[1] * shp_in[2], out_elems = (size_t)shp_out[0] * shp_out[1] * shp_out[2];
     size_t params = 0;
     for (const auto& L : mm.desc.layers) params += L.kernel.size() + L.bias.size();
-    if (lowp) {
+    if (lowp && !mm.has_fused) {
+      bytes[0] = srcfd::any16_workspace_bytes(mm, n);   // any16_reserve: two activation buffers + the dense split-K slabs
+      bytes[1] = params * (sizeof(float) + 2 * sizeof(uint16_t));
+    } else if (lowp) {
       const size_t want = (size_t)std::min(n, 1024);
       bytes[0] = want ? 2 * want * 160000 * sizeof(uint16_t) + 16 * want * 128 * sizeof(float) : 0;   // fused_reserve: two activation buffers + the dense split-K slabs
       bytes[1] = params * (sizeof(float) + 2 * sizeof(uint16_t));   // f32 weights + the 16-bit GEMM layout + fragment re-orderings (upper bound: every layer twice)
@@ -872,7 +895,10 @@ int srcfd_model_last_plan(const srcfd_model* m, char* buf, size_t buf_len) {
     const srcfd::Plan& p = M(m)->plan;
     const char* prec = p.precision == SRCFD_PREC_BF16 ? "bf16" : p.precision == SRCFD_PREC_F16 ? "f16" : p.precision == SRCFD_PREC_FP32 ? "fp32" : p.precision == SRCFD_PREC_FP32X3 ? "fp32x3" : "fp32_naive";
     char tmp[256];
-    if (p.fused)
+    if (p.any16)
+      snprintf(tmp, sizeof(tmp), "precision=%s encoder=%s decoder=any16 graph=%s", prec, p.sw.enc16 ? "enc16" : "layers",
+               p.graph == 2 ? "replay" : p.graph == 1 ? "capture" : "eager");
+    else if (p.fused)
       snprintf(tmp, sizeof(tmp), "precision=%s encoder=%s dense_1=%s middle=%s tail=%s tail_seg=%d graph=%s", prec, p.sw.enc16 ? "enc16" : "layers",
                p.sw.dense1_16 ? "dense1_16" : "gemm16", p.sw.mid16 ? (p.sw.mid_waves == 4 ? "mid16_4x32" : p.sw.mid_waves == 16 ? "mid16_16x32" : p.sw.mid_shape == 1 ? "mid16_8x32" : p.sw.mid_shape == 2 ? "mid16_8x64" : "mid16_4x64") : "gemm16", p.sw.tail16s ? "tail16s" : "tail16", p.tail_seg,
                p.graph == 2 ? "replay" : p.graph == 1 ? "capture" : "eager");

@@ -310,4 +310,146 @@ int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, cons
   return SRCFD_OK;
 }
 
+// ---------------------------------------------------------------------------
+// any16: the 16-bit forward of encoder_10 + the other decoders of the family.  enc16 -> per layer gemm16 (CI % 64 == 0) or
+// gemm16n (CI 16 / 32) -> outconv16; the layer-by-layer encoder stays reachable with SRCFD_ENC=0, like on the fused path.
+// ---------------------------------------------------------------------------
+struct Any16State : Any16Pack {
+  struct Dev {
+    DevBuf<uint16_t> d_w, d_encf;
+    DevBuf<float> d_encb, d_wout;
+    size_t enc_wd_off = 0, enc_wl_off = 0;
+    std::vector<size_t> w_off;
+    bool built = false;
+  } packs[2];
+  DevBuf<float> d_f32;
+  DevBuf<uint16_t> act[2];
+  DevBuf<float> d_part;
+  int cap = 0;
+};
+
+void any16_create(Model& m) {
+  Any16State* st = new Any16State();
+  any16_plan(m.desc, m.ops, m.pack, *st);
+  if (!st->ok) { delete st; return; }
+  m.any16 = st;
+}
+
+void any16_free(Model& m) {
+  delete m.any16;
+  m.any16 = nullptr;
+}
+
+int any16_init(Model& m) { return m.any16->d_f32.upload(m.any16->f32); }
+
+static int any16_build_pack(Model& m, Any16State* st, bool f16) {
+  Any16State::Dev& P = st->packs[f16 ? 1 : 0];
+  if (P.built) return SRCFD_OK;
+  Any16Host h;
+  pack_any16(m.desc, m.ops, m.pack, *st, f16, h);
+  P.enc_wd_off = h.enc_wd_off; P.enc_wl_off = h.enc_wl_off;
+  P.w_off.clear();
+  for (const Op16& o : st->ops) P.w_off.push_back(o.w_off);
+  int rc = P.d_w.upload(h.w);
+  if (!rc) rc = P.d_encf.upload(h.encf);
+  if (!rc) rc = P.d_encb.upload(h.encb);
+  if (!rc) rc = P.d_wout.upload(h.wout);
+  if (rc) return rc;
+  P.built = true;
+  return SRCFD_OK;
+}
+
+// two activation buffers of the graph's largest activation + the dense split-K slabs, for min(n, 1024) samples
+size_t any16_workspace_bytes(const Model& m, int n) {
+  const size_t want = (size_t)std::min(std::max(n, 0), 1024);
+  return want ? 2 * want * m.any16->max_act * sizeof(uint16_t) + 16 * want * 128 * sizeof(float) : 0;
+}
+
+int any16_reserve(Model& m, int n) {
+  Any16State* st = m.any16;
+  if (!st) { set_error("any16 path not initialised"); return SRCFD_EINVAL; }
+  int rc = any16_build_pack(m, st, m.precision == SRCFD_PREC_F16);
+  if (rc) return rc;
+  const int want = std::min(n, 1024);
+  if (want > st->cap) {
+    m.drop_graph();  // a captured forward holds the old buffers' addresses
+    st->cap = 0;
+    for (auto& b : st->act) { rc = b.alloc((size_t)want * st->max_act); if (rc) return rc; }
+    rc = st->d_part.alloc((size_t)16 * want * 128);
+    if (rc) return rc;
+    st->cap = want;
+  }
+  return SRCFD_OK;
+}
+
+int any16_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
+                  unsigned long long* nonfinite, hipStream_t s) {
+  Any16State* st = m.any16;
+  if (!st) { set_error("any16 path not initialised"); return SRCFD_EINVAL; }
+  const bool f16 = m.precision == SRCFD_PREC_F16;
+  int rc = any16_reserve(m, n);
+  if (rc) return rc;
+  const Any16State::Dev& P = st->packs[f16 ? 1 : 0];
+  const float* const d_f32 = st->d_f32.get();
+  uint16_t* const act[2] = {st->act[0].get(), st->act[1].get()};
+  const size_t osz = out_dtype == SRCFD_F32 ? 4 : 2;
+  const size_t out_elems = (size_t)st->out_H * st->out_W;
+  for (int i0 = 0; i0 < n; i0 += st->cap) {
+    const int c = std::min(st->cap, n - i0);
+    const float* xin = x_dev + (size_t)i0 * 100;
+    const float* ain = aff_in ? aff_in + 2 * (size_t)i0 : nullptr;
+    const float* aout = aff_out ? aff_out + 2 * (size_t)i0 : nullptr;
+    int cur = 0;
+    const bool use_enc = m.sw.enc16;   // false: layer-by-layer encoder (functional A/B switch, part of the hipGraph key)
+    if (use_enc) {
+      EncParams ep;
+      ep.x = xin; ep.affine = ain; ep.n = c;
+      ep.w1 = d_f32 + st->c1w_off; ep.b1 = d_f32 + st->c1b_off;
+      ep.w2f = P.d_encf.get(); ep.b2f = P.d_encb.get();
+      ep.wdf = (const char*)P.d_encf.get() + P.enc_wd_off; ep.bd = d_f32 + st->ops[1].b_off;
+      ep.wlf = (const char*)P.d_encf.get() + P.enc_wl_off; ep.bl = d_f32 + st->ops[2].b_off;
+      ep.z = act[1];
+      ep.act_dense = st->ops[1].d.act; ep.act_latent = st->ops[2].d.act;
+      ep.prof = nullptr;
+      rc = m.launch("encoder(conv2d..latent_vector)", s, [&] { return launch_enc16(f16, ep, s); });
+      if (rc) return rc;
+      cur = 1;   // where the layer-by-layer chain leaves the latent vectors, too
+    } else {
+      rc = m.launch("conv2d", s, [&] { return launch_enc_conv1_16(f16, xin, ain, d_f32 + st->c1w_off, d_f32 + st->c1b_off, act[0], c, s); });
+      if (rc) return rc;
+    }
+    int prev_layer = -1;
+    for (size_t oi = 0; oi < st->ops.size(); ++oi) {
+      const Op16& o = st->ops[oi];
+      if (use_enc && o.layer < 4) continue;  // conv2d_1, dense, latent_vector ran inside enc16
+      if (o.layer != prev_layer && prev_layer >= 0) cur ^= 1;
+      prev_layer = o.layer;
+      GemmDesc d = o.d;
+      d.M = c * d.MH * d.MW;
+      const uint16_t* X = act[cur];
+      uint16_t* Y = act[cur ^ 1];
+      const uint16_t* W = P.d_w.get() + P.w_off[oi];
+      if (any16_narrow(d)) {
+        rc = m.launch(o.name.c_str(), s, [&] { return launch_gemm16n(f16, d, X, W, o.Kpad, d_f32 + o.b_off, Y, s); });
+      } else {
+        int splits = 1;   // dense layers with few rows and a long K: split K over workgroups (f32 slabs + finish kernel)
+        if (d.MH == 1 && d.MW == 1 && d.K >= 1024) splits = std::max(1, std::min(16, d.K / 256));
+        if (splits > 1 && (size_t)splits * d.M * d.Npad > st->d_part.size()) splits = 1;
+        rc = m.launch(o.name.c_str(), s, [&] { return launch_gemm16(f16, d, X, W, o.Kpad, d_f32 + o.b_off, Y, st->d_part.get(), splits, s); });
+      }
+      if (rc) return rc;
+    }
+    cur ^= 1;   // the last GEMM layer's output
+    OutConv16Params op;
+    op.in = act[cur];
+    op.out = (char*)y_dev + (size_t)i0 * out_elems * osz;
+    op.n = c; op.H = st->out_H; op.W = st->out_W; op.C = st->out_C;
+    op.w = P.d_wout.get(); op.bias = st->out_bias;
+    op.aff_out = aout; op.nan_guard = flags & SRCFD_FLAG_NAN_GUARD; op.nonfinite = nonfinite; op.out_dtype = out_dtype;
+    rc = m.launch(m.desc.layers[st->cl.back()].name.c_str(), s, [&] { return launch_outconv16(f16, op, s); });
+    if (rc) return rc;
+  }
+  return SRCFD_OK;
+}
+
 }  // namespace srcfd

@@ -99,4 +99,20 @@ hipError_t launch_tail16(bool f16, const TailParams& p, int blocks, hipStream_t 
 hipError_t launch_tail16s(bool f16, const TailParams& p, int blocks, hipStream_t s);   // second implementation (kernels_tail16s.hip, SRCFD_TAIL=s): 8 waves, MFMAs inside the swish stream
 int tail_lds_bytes();
 
+// kernels_any16.hip: the 16-bit kernels of the family graphs outside encoder_10 + decoder_400
+// Implicit GEMM for CI 16 / 32 (k-step 16); Wt[Npad][Kpad] with Npad % 32 == 0, bias[Npad]; same GemmDesc as launch_gemm16
+hipError_t launch_gemm16n(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y, hipStream_t s);
+struct OutConv16Params {
+  const uint16_t* in;      // (n, H, W, C) 16-bit NHWC, C % 8 == 0, C <= 64
+  void* out;               // (n, H, W) of out_dtype
+  int n, H, W, C;
+  const float* w;          // [9 * C] (ty, tx, ci): the 16-bit-rounded weights as f32
+  float bias;
+  const float* aff_out;    // (n, 2) mean, std or null
+  int nan_guard;
+  unsigned long long* nonfinite;
+  int out_dtype;
+};
+hipError_t launch_outconv16(bool f16, const OutConv16Params& p, hipStream_t s);
+
 }  // namespace srcfd

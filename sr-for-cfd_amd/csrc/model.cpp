@@ -32,6 +32,16 @@ int act_from_name(const std::string& s) {
 
 static int same_out(int in, int s) { return (in + s - 1) / s; }
 
+// Conv2DTranspose padding='same', one axis: the (input pixel i, tap a) pairs whose VALID position s i + a lies in the kept range
+// [pb, pb + in s), pb = (k - s) / 2
+static int64_t convt_same_pairs(int in, int k, int s) {
+  const int pb = (k - s) / 2;
+  int64_t c = 0;
+  for (int i = 0; i < in; ++i)
+    for (int a = 0; a < k; ++a) c += s * i + a >= pb && s * i + a < pb + in * s;
+  return c;
+}
+
 void ModelDesc::infer_shapes() {
   int cur[3] = {in_shape[0], in_shape[1], in_shape[2]};
   if (cur[0] <= 0 || cur[1] <= 0 || cur[2] <= 0) throw std::runtime_error("bad input shape");
@@ -51,9 +61,16 @@ void ModelDesc::infer_shapes() {
       }
       case SRCFD_LAYER_CONV2D_TRANSPOSE: {
         if (L.cin != cur[2]) throw std::runtime_error("layer '" + L.name + "': channel mismatch");
-        if (L.same) throw std::runtime_error("layer '" + L.name + "': Conv2DTranspose padding='same' unsupported");
         int oh = (cur[0] - 1) * L.stride + L.kh, ow = (cur[1] - 1) * L.stride + L.kw;
-        L.macs = (int64_t)cur[0] * cur[1] * L.kh * L.kw * L.cin * L.cout;
+        int64_t pairs_y = (int64_t)cur[0] * L.kh, pairs_x = (int64_t)cur[1] * L.kw;   // (input pixel, tap) pairs that land inside the output
+        if (L.same) {   // rows / columns [pb, pb + in * stride) of the VALID result, pb = (k - stride) / 2 (srcfd.h, srcfd_layer)
+          if (L.kh < L.stride || L.kw < L.stride)
+            throw std::runtime_error("layer '" + L.name + "': Conv2DTranspose padding='same' with a kernel smaller than the stride is unsupported");
+          oh = cur[0] * L.stride; ow = cur[1] * L.stride;
+          pairs_y = convt_same_pairs(cur[0], L.kh, L.stride);
+          pairs_x = convt_same_pairs(cur[1], L.kw, L.stride);
+        }
+        L.macs = pairs_y * pairs_x * L.cin * L.cout;
         cur[0] = oh; cur[1] = ow; cur[2] = L.cout;
         if ((int64_t)L.kernel.size() != (int64_t)L.kh * L.kw * L.cin * L.cout) throw std::runtime_error("layer '" + L.name + "': kernel size mismatch");
         break;
@@ -116,6 +133,7 @@ bool ModelDesc::is_sr_10_400() const {
     if (L.kind != p.kind || L.cin != p.cin || L.cout != p.cout || L.act != p.act) return false;
     if (L.kind != SRCFD_LAYER_DENSE && (L.kh != p.k || L.kw != p.k || L.stride != p.s)) return false;
     if (L.kind == SRCFD_LAYER_CONV2D && !L.same) return false;
+    if (L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.same && L.kh != L.stride) return false;   // 'same' crops unless kernel == stride
     if (L.bias.empty()) return false;
   }
   return pi == sizeof(pat) / sizeof(pat[0]) && layers.back().out_shape[0] == 400;

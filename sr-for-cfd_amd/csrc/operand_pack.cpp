@@ -107,8 +107,9 @@ void build_plan(const ModelDesc& desc, std::vector<Op>& ops, std::vector<float>&
       d.ay = d.ax = L.stride; d.by = d.bx = 1; d.cy = -pt; d.cx = -pl;
       d.K = L.kh * L.kw * L.cin; d.N = L.cout; d.Npad = round_up(d.N, 32);
       emit(d, L.name, L.kernel, L.bias);  // (kh,kw,Cin,Cout) is already [K][N]
-    } else {  // Conv2DTranspose, VALID, kernel (kh,kw,Cout,Cin)
+    } else {  // Conv2DTranspose, kernel (kh,kw,Cout,Cin).  VALID: full[s i + a] += x[i] W[a]; SAME: out[o] = full[o + pb], pb = (k - s) / 2
       const int s = L.stride;
+      const int pby = L.same ? (L.kh - s) / 2 : 0, pbx = L.same ? (L.kw - s) / 2 : 0;
       auto W = [&](int a, int b, int co, int ci) { return L.kernel[(((size_t)a * L.kw + b) * L.cout + co) * L.cin + ci]; };
       if (L.kh == s && L.kw == s) {
         d.MH = IH; d.MW = IW; d.TY = d.TX = 1;
@@ -128,12 +129,15 @@ void build_plan(const ModelDesc& desc, std::vector<Op>& ops, std::vector<float>&
             GemmDesc p = d;
             p.TY = py < L.kh ? (L.kh - py + s - 1) / s : 0;
             p.TX = px < L.kw ? (L.kw - px + s - 1) / s : 0;
-            p.MH = py < OH ? (OH - py + s - 1) / s : 0;
-            p.MW = px < OW ? (OW - px + s - 1) / s : 0;
+            // phase (py, px) of the VALID result: its position s m' + py is output row s my + ry, m' = my + shy (pb = 0: ry = py, shy = 0)
+            const int ry = ((py - pby) % s + s) % s, rx = ((px - pbx) % s + s) % s;
+            const int shy = (ry + pby - py) / s, shx = (rx + pbx - px) / s;
+            p.MH = ry < OH ? (OH - ry + s - 1) / s : 0;
+            p.MW = rx < OW ? (OW - rx + s - 1) / s : 0;
             if (p.MH == 0 || p.MW == 0) continue;
-            p.ay = p.ax = 1; p.by = p.bx = -1; p.cy = p.cx = 0;
+            p.ay = p.ax = 1; p.by = p.bx = -1; p.cy = shy; p.cx = shx;
             p.K = p.TY * p.TX * L.cin; p.N = L.cout; p.Npad = round_up(p.N, 32);
-            p.os = s; p.oy0 = py; p.ox0 = px;
+            p.os = s; p.oy0 = ry; p.ox0 = rx;
             std::vector<float> B((size_t)std::max(p.K, 1) * p.N, 0.f);
             for (int ty = 0; ty < p.TY; ++ty)
               for (int tx = 0; tx < p.TX; ++tx)
@@ -484,6 +488,128 @@ void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::ve
   acc_bias(P.midb.data() + 128, 2, [&](int row) { return (float)(L1.bias[row] * LOG2E); });
 }
 
+// the generic 16-bit path: which graphs it takes, and their operands
+static float from16(uint16_t v, bool f16) {
+  uint32_t u;
+  if (!f16) u = (uint32_t)v << 16;
+  else {
+    const uint32_t sign = (uint32_t)(v & 0x8000u) << 16, e = (v >> 10) & 31u, m = v & 0x3ffu;
+    if (e == 0) {
+      if (m == 0) u = sign;
+      else { int sh = 0; uint32_t mm = m; while (!(mm & 0x400u)) { mm <<= 1; ++sh; } u = sign | ((uint32_t)(113 - sh) << 23) | ((mm & 0x3ffu) << 13); }
+    } else if (e == 31) u = sign | 0x7f800000u | (m << 13);
+    else u = sign | ((e + 112u) << 23) | (m << 13);
+  }
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A) {
+  A = Any16Pack();
+  auto no = [&](const std::string& w) { A.why = w; };
+  for (size_t i = 0; i < md.layers.size(); ++i)
+    if (md.layers[i].kind != SRCFD_LAYER_FLATTEN && md.layers[i].kind != SRCFD_LAYER_RESHAPE) A.cl.push_back((int)i);
+  const int n = (int)A.cl.size();
+  if (n < 6) return no("fewer layers than encoder_10 + a dense layer + an output convolution");
+  auto L = [&](int i) -> const Layer& { return md.layers[A.cl[i]]; };
+  auto act_ok = [](int a) { return a == SRCFD_ACT_SWISH || a == SRCFD_ACT_LINEAR; };
+  // 1. the first four compute layers are encoder_10's (enc16 is written for exactly these)
+  if (md.in_shape[0] != 10 || md.in_shape[1] != 10 || md.in_shape[2] != 1) return no("input is not (10, 10, 1)");
+  const Layer &c1 = L(0), &c2 = L(1), &de = L(2), &la = L(3);
+  if (c1.kind != SRCFD_LAYER_CONV2D || c1.kh != 3 || c1.kw != 3 || c1.stride != 2 || !c1.same || c1.cin != 1 || c1.cout != 64 || c1.act != SRCFD_ACT_SWISH ||
+      c2.kind != SRCFD_LAYER_CONV2D || c2.kh != 3 || c2.kw != 3 || c2.stride != 1 || !c2.same || c2.cin != 64 || c2.cout != 128 || c2.act != SRCFD_ACT_SWISH ||
+      de.kind != SRCFD_LAYER_DENSE || de.cin != 3200 || de.cout != 128 || !act_ok(de.act) || la.kind != SRCFD_LAYER_DENSE || la.cin != 128 || la.cout > 64 ||
+      !act_ok(la.act))
+    return no("the first four layers are not encoder_10's");
+  // 2. the last layer: 3x3 stride-1 SAME Conv2D to one channel, linear
+  const Layer& lo = L(n - 1);
+  if (lo.kind != SRCFD_LAYER_CONV2D || lo.kh != 3 || lo.kw != 3 || lo.stride != 1 || !lo.same || lo.cout != 1 || lo.act != SRCFD_ACT_LINEAR || lo.cin % 16 != 0 ||
+      lo.cin > 64)
+    return no("the last layer is not a 3x3 stride-1 'same' Conv2D from 16 / 32 / 48 / 64 channels to one, linear");
+  // 3. everything in between has a 16-bit kernel
+  for (int i = 4; i < n - 1; ++i) {
+    const Layer& l = L(i);
+    if (!act_ok(l.act)) return no("layer '" + l.name + "': activation");
+    if (l.kind == SRCFD_LAYER_DENSE) {
+      if (!(i == 4 ? l.cin <= 64 : l.cin % 64 == 0) || l.cout % 64 != 0) return no("layer '" + l.name + "': dense width");
+    } else if (l.kind == SRCFD_LAYER_CONV2D_TRANSPOSE) {
+      const bool k2 = l.kh == 2 && l.kw == 2 && l.stride == 2, k3 = l.kh == 3 && l.kw == 3 && l.stride == 2;
+      if (!k2 && !k3) return no("layer '" + l.name + "': only 2x2 and 3x3 stride-2 transposed convolutions");
+      if (l.cin % 16 != 0 || l.cout % 4 != 0) return no("layer '" + l.name + "': channel counts");
+    } else return no("layer '" + l.name + "': no 16-bit kernel for this layer kind");
+  }
+  if (L(4).kind != SRCFD_LAYER_DENSE) return no("the layer behind latent_vector is not Dense");
+  // conv1 (VALU kernel): f32 weights, scaled
+  {
+    const double sw = scale_w(md, A.cl, 0), so = scale_out(md, A.cl, 0);
+    A.c1w_off = A.f32.size();
+    for (float v : c1.kernel) A.f32.push_back((float)(v * sw));
+    A.c1b_off = A.f32.size();
+    for (float v : c1.bias) A.f32.push_back((float)(v * so));
+  }
+  A.max_act = 3200;   // conv2d_1's output when the encoder runs layer by layer
+  for (const Op& op : ops) {
+    int ci = -1;
+    for (int k = 0; k < n; ++k) if (A.cl[k] == op.layer) ci = k;
+    if (ci < 1 || ci >= n - 1) continue;
+    Op16 o;
+    o.d = op.d; o.name = op.name; o.layer = ci;
+    if (ci == 3) { o.d.N = 64; o.d.CO = 64; o.d.OC = 64; }   // latent -> 64 zero-padded channels
+    if (ci == 4) { o.d.CI = 64; o.d.K = 64; }                // the dense layer behind it reads the padded latent
+    const bool narrow = any16_narrow(o.d);
+    o.d.Npad = round_up(o.d.N, narrow ? 32 : 64);
+    o.Kpad = narrow ? o.d.K : round_up(o.d.K, 64);
+    if (o.d.K <= 0 || o.d.N % 4 != 0 || o.d.CO % 4 != 0 || o.d.OC % 4 != 0 || o.d.CI % 16 != 0 || (!narrow && o.d.K % 64 != 0)) {
+      A.ops.clear();
+      return no("layer '" + md.layers[op.layer].name + "': GEMM shape");
+    }
+    const double so = scale_out(md, A.cl, ci);
+    while (A.f32.size() % 4) A.f32.push_back(0.f);
+    o.b_off = A.f32.size();
+    for (int q = 0; q < o.d.Npad; ++q) A.f32.push_back(q < op.d.N ? (float)(pack[op.b_off + q] * so) : 0.f);
+    A.ops.push_back(o);
+    const Layer& l = md.layers[op.layer];
+    A.max_act = std::max(A.max_act, (size_t)l.out_shape[0] * l.out_shape[1] * (ci == 3 ? 64 : l.out_shape[2]));
+  }
+  if (A.ops.size() < 4 || A.ops[0].layer != 1 || A.ops[1].layer != 2 || A.ops[2].layer != 3) { A.ops.clear(); return no("unexpected plan shape"); }
+  A.out_C = lo.cin; A.out_H = lo.in_shape[0]; A.out_W = lo.in_shape[1]; A.out_bias = lo.bias[0];
+  A.ok = true;
+}
+
+void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A, bool f16, Any16Host& P) {
+  const int n = (int)A.cl.size();
+  size_t oi = 0;
+  for (const Op& op : ops) {
+    int ci = -1;
+    for (int k = 0; k < n; ++k) if (A.cl[k] == op.layer) ci = k;
+    if (ci < 1 || ci >= n - 1) continue;
+    Op16& o = A.ops[oi++];
+    const double sw = scale_w(md, A.cl, ci);
+    while (P.w.size() % 8) P.w.push_back(0);
+    o.w_off = P.w.size();
+    P.w.resize(P.w.size() + (size_t)o.d.Npad * o.Kpad, 0);
+    for (int q = 0; q < op.d.N; ++q)
+      for (int k = 0; k < op.d.K; ++k) P.w[o.w_off + (size_t)q * o.Kpad + k] = to16((float)(pack[op.w_off + (size_t)k * op.d.Npad + q] * sw), f16);
+  }
+  // enc16 operands: as pack_fused16
+  const uint16_t* W2 = P.w.data() + A.ops[0].w_off;   // [128][576]
+  const uint16_t* WD = P.w.data() + A.ops[1].w_off;   // [128][3200]
+  const uint16_t* WL = P.w.data() + A.ops[2].w_off;   // [64][128]
+  P.enc_wd_off = (size_t)4 * 36 * 1024; P.enc_wl_off = P.enc_wd_off + (size_t)8 * 100 * 1024;
+  P.encf.resize((size_t)(4 * 36 + 8 * 100 + 4 * 4) * 512);
+  a_frags(P.encf.data(), 32, 4, 36, [&](int r, int k) { return W2[(size_t)r * 576 + k]; });
+  a_frags(P.encf.data() + P.enc_wd_off / 2, 16, 8, 100, [&](int r, int k) { return WD[(size_t)r * 3200 + k]; });
+  a_frags(P.encf.data() + P.enc_wl_off / 2, 16, 4, 4, [&](int r, int k) { return WL[(size_t)r * 128 + k]; });
+  P.encb.resize(128);
+  acc_bias(P.encb.data(), 4, [&](int row) { return A.f32[A.ops[0].b_off + row]; });
+  // output convolution: Keras kernel (3, 3, C, 1) = (ty, tx, ci)
+  const Layer& lo = md.layers[A.cl[n - 1]];
+  const double si = scale_in(md, A.cl, n - 1);
+  P.wout.resize(lo.kernel.size());
+  for (size_t i = 0; i < lo.kernel.size(); ++i) P.wout[i] = from16(to16((float)(lo.kernel[i] * si), f16), f16);
+}
+
 // trainer
 ModelDesc index_model(const ModelDesc& src, std::vector<LayerInfo>& layers, int64_t& n_params, std::vector<float>& init) {
   ModelDesc im = src;
@@ -542,9 +668,10 @@ void build_dgrad(const ModelDesc& md, const std::vector<LayerInfo>& layers, std:
           for (int co = 0; co < L.cout; ++co)
             for (int c = 0; c < L.cin; ++c)
               B[((size_t)(ky * L.kw + kx) * L.cout + co) * d.N + c] = L.kernel[(((size_t)ky * L.kw + kx) * L.cin + c) * L.cout + co];
-    } else {  // Conv2DTranspose VALID, kernel (kh,kw,Cout,Cin): dX[i,j,ci] = sum dZ[s i + a, s j + b, co] W[a,b,co,ci]
+    } else {  // Conv2DTranspose, kernel (kh,kw,Cout,Cin): dX[i,j,ci] = sum dZ[s i + a - pb, s j + b - pb, co] W[a,b,co,ci] (0 outside; VALID: pb = 0)
       d.MH = IH; d.MW = IW; d.TY = L.kh; d.TX = L.kw; d.CI = L.cout; d.IH = OH; d.IW = OW; d.OH = IH; d.OW = IW;
-      d.ay = d.ax = L.stride; d.by = d.bx = 1; d.cy = d.cx = 0;
+      d.ay = d.ax = L.stride; d.by = d.bx = 1;
+      d.cy = L.same ? -((L.kh - L.stride) / 2) : 0; d.cx = L.same ? -((L.kw - L.stride) / 2) : 0;
       d.K = L.kh * L.kw * L.cout;
       B = L.kernel;  // already [(a,b,co)][ci]
     }

@@ -80,6 +80,31 @@ struct Pack16Host {  // one per operand type (bf16, f16); the device copies are 
 // sets fs.ops[].w_off; the enc16 fragments only when `enc` (FusedState::enc_ok)
 void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs, bool enc, bool f16, Pack16Host& P);
 
+// ---- bf16 / f16 path of the other family graphs (fused_bf16.hip, any16_forward) ----
+// encoder_10 (enc16) -> per layer gemm16 (CI % 64 == 0) or the narrow-channel GEMM (CI 16 / 32, kernels_any16.hip) -> outconv16.
+// Same log2(e) folding as the fused path: swish outputs are stored scaled by log2e, consumers fold 1 / log2e into their weights.
+struct Any16Pack {
+  bool ok = false;           // the graph is eligible (any16_plan); `why` says what is not
+  std::string why;
+  std::vector<int> cl;       // indices of the compute layers in ModelDesc::layers
+  std::vector<Op16> ops;     // GEMM ops of compute layers 1 .. last - 1 (Op16::layer = compute-layer ordinal); Kpad: row pitch of Wt
+  std::vector<float> f32;    // conv1 weights [9][64] + bias [64] (scaled), per-op biases [Npad] (scaled)
+  size_t c1w_off = 0, c1b_off = 0;
+  int out_C = 0, out_H = 0, out_W = 0;   // the output convolution: 3x3 SAME, C -> 1
+  float out_bias = 0.f;
+  size_t max_act = 0;        // largest 16-bit activation per sample, elements
+};
+struct Any16Host {           // one per operand type
+  std::vector<uint16_t> w;       // Wt[Npad][Kpad] per op
+  std::vector<uint16_t> encf;    // enc16 fragments, as Pack16Host
+  size_t enc_wd_off = 0, enc_wl_off = 0;
+  std::vector<float> encb;
+  std::vector<float> wout;       // output convolution (ty, tx, ci): the 16-bit-rounded weights (x 1 / log2e behind a swish) as f32
+};
+inline bool any16_narrow(const GemmDesc& d) { return d.CI % 64 != 0; }
+void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A);
+void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A, bool f16, Any16Host& P);   // sets A.ops[].w_off
+
 // ---- trainer (train.hip) ----
 // a compute layer: its index in ModelDesc::layers, elements per sample, flat parameter offsets
 struct LayerInfo { int desc_index; size_t in_elems, out_elems; bool swish; size_t kernel_off, bias_off; };

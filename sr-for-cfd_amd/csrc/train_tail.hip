@@ -410,8 +410,8 @@ void train_tail_plan(const ModelDesc& desc, const int* desc_index, const size_t*
   const int f = n_compute_layers - 4;
   const Layer &L1 = desc.layers[desc_index[f]], &L2 = desc.layers[desc_index[f + 1]], &L3 = desc.layers[desc_index[f + 2]],
               &LO = desc.layers[desc_index[f + 3]];
-  auto convt = [](const Layer& L, int cin, int cout) {
-    return L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2 && !L.same && L.cin == cin && L.cout == cout &&
+  auto convt = [](const Layer& L, int cin, int cout) {   // kernel == stride: padding 'same' and 'valid' are the same layer
+    return L.kind == SRCFD_LAYER_CONV2D_TRANSPOSE && L.kh == 2 && L.kw == 2 && L.stride == 2 && L.cin == cin && L.cout == cout &&
            L.act == SRCFD_ACT_SWISH;
   };
   if (!convt(L1, 64, 32) || !convt(L2, 32, 16) || !convt(L3, 16, 8)) return;

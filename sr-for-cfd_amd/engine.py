@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib as L
+from . import family
 
 PRECISIONS = {"fp32": L.PREC_FP32, "float32": L.PREC_FP32, "bf16": L.PREC_BF16, "bfloat16": L.PREC_BF16,
               "fp32_naive": L.PREC_FP32_NAIVE, "f16": L.PREC_F16, "fp16": L.PREC_F16, "float16": L.PREC_F16,
@@ -28,28 +29,12 @@ def device_count() -> int:
     return int(L.lib.srcfd_device_count())
 
 
-def layers_from_weights(enc_w: Optional[Dict[str, np.ndarray]], dec_w: Optional[Dict[str, np.ndarray]]) -> List[dict]:
-    """Layer specs of encoder_10 and/or decoder_400 (sr-ae-conv.ipynb:c162-169,
-    c277-287) from ``{'<layer>/kernel', '<layer>/bias'}`` dicts."""
-    specs: List[dict] = []
-    if enc_w is not None:
-        specs += [
-            dict(kind="conv2d", name="conv2d", k=3, stride=2, same=True, act="swish", w=enc_w["conv2d/kernel"], b=enc_w["conv2d/bias"]),
-            dict(kind="conv2d", name="conv2d_1", k=3, stride=1, same=True, act="swish", w=enc_w["conv2d_1/kernel"], b=enc_w["conv2d_1/bias"]),
-            dict(kind="flatten", name="flatten"),
-            dict(kind="dense", name="dense", act="swish", w=enc_w["dense/kernel"], b=enc_w["dense/bias"]),
-            dict(kind="dense", name="latent_vector", act="linear", w=enc_w["latent_vector/kernel"], b=enc_w["latent_vector/bias"]),
-        ]
-    if dec_w is not None:
-        specs += [dict(kind="dense", name="dense_1", act="swish", w=dec_w["dense_1/kernel"], b=dec_w["dense_1/bias"]),
-                  dict(kind="reshape", name="reshape", shape=(12, 12, 256))]
-        for i, k in enumerate((3, 2, 2, 2, 2)):
-            name = "conv2d_transpose" + ("" if i == 0 else f"_{i}")
-            specs.append(dict(kind="conv2d_transpose", name=name, k=k, stride=2, same=False, act="swish",
-                              w=dec_w[f"{name}/kernel"], b=dec_w[f"{name}/bias"]))
-        specs.append(dict(kind="conv2d", name="output_image_400", k=3, stride=1, same=True, act="linear",
-                          w=dec_w["output_image_400/kernel"], b=dec_w["output_image_400/bias"]))
-    return specs
+def layers_from_weights(enc_w: Optional[Dict[str, np.ndarray]], dec_w: Optional[Dict[str, np.ndarray]],
+                        lr_dim: Optional[int] = None, hr_dim: Optional[int] = None) -> List[dict]:
+    """Layer specs of encoder_{lr} and/or decoder_{hr} (sr-ae-conv.ipynb: build_encoder_* / build_decoder_*; family.py)
+    from ``{'<layer>/kernel', '<layer>/bias'}`` dicts.  Which member a dict belongs to is read from its kernel shapes and
+    its ``output_image_{hr}`` layer (encoder_10 unless ``lr_dim`` says otherwise where the shapes leave it open)."""
+    return family.layers_from_weights(enc_w, dec_w, lr_dim, hr_dim)
 
 
 class _PinnedPool:
@@ -210,9 +195,9 @@ class SRModel:
         return cls(h, dev)
 
     @classmethod
-    def from_weights(cls, enc_w, dec_w, device=None) -> "SRModel":
-        in_shape = (10, 10, 1) if enc_w is not None else (1, 1, 50)
-        return cls.from_layers(layers_from_weights(enc_w, dec_w), in_shape, device)
+    def from_weights(cls, enc_w, dec_w, device=None, lr_dim=None, hr_dim=None) -> "SRModel":
+        """Any encoder and/or decoder of the notebook's family (family.py) from weight dicts."""
+        return cls.from_layers(layers_from_weights(enc_w, dec_w, lr_dim, hr_dim), family.input_shape(enc_w, dec_w, lr_dim), device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -246,6 +231,10 @@ class SRModel:
     def has_fused_path(self) -> bool:
         return bool(L.lib.srcfd_model_has_fused_path(self._h))
 
+    def supports_precision(self, name: str) -> bool:
+        """Would `self.precision = name` be accepted?  (srcfd_model_supports_precision; works on a host-only handle.)"""
+        return bool(L.lib.srcfd_model_supports_precision(self._h, PRECISIONS[name]))
+
     @property
     def precision(self) -> str:
         p = L.lib.srcfd_model_get_precision(self._h)
@@ -253,6 +242,8 @@ class SRModel:
 
     @precision.setter
     def precision(self, name: str):
+        if name not in PRECISIONS:
+            raise ValueError(f"unknown precision {name!r}")
         L.check(L.lib.srcfd_model_set_precision(self._h, PRECISIONS[name]))
 
     def reserve(self, n: int) -> None:

@@ -101,8 +101,8 @@ def _device_handle(paths: Tuple[Optional[str], ...], precision: str, device: Opt
         del _HANDLE_CACHE[key]
     enc, dec = (paths + (None,))[:2]
     m = SRModel.load_h5(enc, dec, device=dev)
-    if precision in ("bf16", "f16") and not m.has_fused_path:
-        precision = "fp32"  # the fused path needs the encoder_10 + decoder_400 pair
+    if not m.supports_precision(precision):
+        precision = "fp32"  # no 16-bit kernels for this graph (srcfd_model_supports_precision)
     m.precision = precision
     _HANDLE_CACHE[key] = (stamp, m)
     return m
@@ -200,7 +200,7 @@ class LoadedModel(Model):
 
     def predict(self, x, batch_size=None, verbose=0, **kwargs):
         x = np.ascontiguousarray(x, dtype=np.float32)
-        y = _device_handle((self.path,), "fp32" if not self._host.has_fused_path else (self._precision or _DEFAULT_PRECISION)).predict(x)
+        y = _device_handle((self.path,), self._precision or _DEFAULT_PRECISION).predict(x)
         oh, ow, oc = self._host.output_shape
         return y.reshape(y.shape[0], oc) if (oh, ow) == (1, 1) else y
 

@@ -1,7 +1,8 @@
 """Counterpart of the training notebook's `__main__` (sr-ae-conv.ipynb:c374-604) on libsrcfd:
 load the simulation files, split by Reynolds number per boundary condition, standardise per
-component, train SuperResolutionAE(encoder_10, decoder_400), evaluate MAE / NMAE on the held-out
-Reynolds numbers, save `vanilla_encoder…h5`, `vanilla_decoder…h5` and the stats file.
+component, train SuperResolutionAE(encoder_{LR}, decoder_{HR}), evaluate MAE / NMAE on the held-out
+Reynolds numbers, save `vanilla_encoder…h5`, `vanilla_decoder…h5` and the stats file.  The decoder is picked by
+`--hr-dim` as the notebook's control panel does (`globals()[f'build_decoder_{HR_DIM}']`); see family.py.
 
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
         sr-for-cfd_amd/train_main.py --data simulation_result.h5 simulation_result_double_lid.h5 --epochs 500
@@ -45,6 +46,20 @@ def evaluate_for_re(re_val, model, data, hr_dim) -> Dict[str, List[float]]:
     return {"mae": maes, "nmae_percent": nmaes}
 
 
+def build_model(lr_dim: int, hr_dim: int, seed: int, device):
+    """SuperResolutionAE(build_encoder_{lr_dim}(), build_decoder_{hr_dim}()) with Keras' default initialisation, as an SRModel.
+    Refuses what the family does not define and the encoders the trainer cannot differentiate."""
+    srcfd = importlib.import_module("sr-for-cfd_amd")
+    family = importlib.import_module("sr-for-cfd_amd.family")
+    if lr_dim not in family.ENCODER_CONVS or hr_dim not in family.DECODER_CONVTS:
+        raise SystemExit(f"the family defines encoders {sorted(family.ENCODER_CONVS)} and decoders {sorted(family.DECODER_CONVTS)}")
+    if lr_dim not in family.TRAINABLE_ENCODERS:
+        raise SystemExit(f"encoder_{lr_dim} has strided convolutions behind its first layer, which the trainer does not differentiate; "
+                         f"trainable encoders: {list(family.TRAINABLE_ENCODERS)}")
+    enc, dec = family.keras_default_init(lr_dim, hr_dim, seed)  # same seed on every rank: identical replicas
+    return srcfd.SRModel.from_weights(enc, dec, device=device, lr_dim=lr_dim, hr_dim=hr_dim)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", nargs="*", default=[], help="simulation_result*.h5 files (none: the notebook's dummy recipe)")
@@ -58,8 +73,6 @@ def main(argv=None):
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--log-every", type=int, default=50)
     args = ap.parse_args(argv)
-    if (args.lr_dim, args.hr_dim) != (10, 400):
-        raise SystemExit("only encoder_10 / decoder_400 are built (the pair the solvers load)")
 
     import torch
     import torch.distributed as dist
@@ -68,7 +81,7 @@ def main(argv=None):
     srcfd = importlib.import_module("sr-for-cfd_amd")
     tr = importlib.import_module("sr-for-cfd_amd.train")
     ds = importlib.import_module("sr-for-cfd_amd.datasets")
-    synth = importlib.import_module("sr-for-cfd_amd.synth")
+    build_model(args.lr_dim, args.hr_dim, args.seed, device=-1)   # refuse an undefined or untrainable pair before anything is loaded
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -88,8 +101,7 @@ def main(argv=None):
     data = ds.prepare_training_set(args.data, args.lr_dim, args.hr_dim, cfg, verbose=rank == 0)
     if len(data["res_train"]) == 0:
         raise SystemExit("training set is empty")
-    enc, dec = synth.keras_default_init(args.seed)  # same seed on every rank: identical replicas
-    trainer = tr.Trainer(srcfd.SRModel.from_weights(enc, dec, device=local), max_batch=args.batch_size)
+    trainer = tr.Trainer(build_model(args.lr_dim, args.hr_dim, args.seed, device=local), max_batch=args.batch_size)
     hist = tr.fit(trainer, data["x_lr_train"], data["x_hr_train"], epochs=args.epochs, batch_size=args.batch_size, seed=args.seed,
                   log_every=args.log_every)
     if rank == 0:
