@@ -345,6 +345,9 @@ int srcfd_fine_solver_get_state(srcfd_fine_solver* s, double* var);
  * enqueued (kernel launches, memsets), [3] host synchronisations; all since create.  last_sweeps: sweeps of the u, v and p
  * solves of the last outer iteration.  Either may be NULL. */
 int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], int last_sweeps[3]);
+/* srcfd_fine_batch_set_mode on the batch of one that a srcfd_fine_solver is.  A resident run that meets NaN / Inf fails as
+ * srcfd_fine_solver_run always does. */
+int srcfd_fine_solver_set_mode(srcfd_fine_solver* s, int mode);
 
 /* ---- batches of fine-mesh cases (the sweeps that make training data) ---------------------------------
  * Replaces the loop over Reynolds numbers of sr-simulation-data-creation.ipynb cell 2: n_cases problems with one nx, ny, scheme
@@ -386,8 +389,26 @@ int srcfd_fine_batch_get_state(srcfd_fine_batch* b, int case_index, double* var)
 /* counters as srcfd_fine_solver_counters, with [0] and [1] counting per inner solve the sweeps of the live case that took the
  * most (the launches that did work); last_sweeps[n][3]: each case's own sweeps in its last outer iteration. */
 int srcfd_fine_batch_counters(const srcfd_fine_batch* b, int64_t counters[4], int* last_sweeps);
-/* Device bytes a batch allocates: n_cases x ((14 planes x (nx+2)(ny+2) + 9 nx) x 8 + one status block + one parameter
- * block).  Needs no device. */
+/* ---- resident mode: small meshes, one workgroup per case, many outer iterations per launch ------------
+ * SRCFD_FINE_MODE_LAUNCHES (the default) issues one launch per inner sweep, which is what a 400x400 mesh wants and what costs a
+ * small mesh its whole solve.  SRCFD_FINE_MODE_RESIDENT gives every case one workgroup that runs the case's outer loop, inner
+ * sweeps included, for up to 100 outer iterations per launch; the cases then advance at their own pace.  The state is the same
+ * device state and the bits are the same bits (tests/fine_solver_spec.py), so the mode may change between any two run calls
+ * and init, init_from_prediction, run and get_state work alike in both.  run() launches chunks that end at the next multiple of
+ * 100 of the batch's iteration count or with the budget, with one launch, one status copy and one host synchronisation each.
+ * Counters in resident mode: [2] and [3] count one launch and one synchronisation per chunk; [0] and [1] grow per chunk by the
+ * largest momentum (u and v) and the largest pressure sweep total that a live case ran in it; last_sweeps is unchanged in
+ * meaning.
+ * srcfd_fine_resident_supported: 1 when a mesh can run resident, else 0 -- 3 <= nx, ny <= 64, the largest
+ * mesh at which it measured faster than a launch per sweep.  Needs no device.
+ * set_mode: SRCFD_EINVAL for an unknown mode and for RESIDENT on an unsupported mesh, with the mesh and the bound in the
+ * message; the handle keeps its mode. */
+#define SRCFD_FINE_MODE_LAUNCHES 0
+#define SRCFD_FINE_MODE_RESIDENT 1
+int srcfd_fine_resident_supported(int nx, int ny);
+int srcfd_fine_batch_set_mode(srcfd_fine_batch* b, int mode);
+/* Device bytes a batch allocates: n_cases x ((14 planes x (nx+2)(ny+2) + 9 nx) x 8 + one status block + one resident record +
+ * one parameter block).  Needs no device. */
 int srcfd_fine_batch_footprint(int nx, int ny, int n_cases, int64_t* device_bytes);
 
 /* ---- training -----------------------------------------------------------

@@ -21,6 +21,7 @@ LAYER_CONV2D, LAYER_CONV2D_TRANSPOSE, LAYER_DENSE, LAYER_FLATTEN, LAYER_RESHAPE 
 ACT_LINEAR, ACT_SWISH, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
 FLAG_NAN_GUARD = 1
 CASE_RUNNING, CASE_CONVERGED, CASE_DIVERGED = 0, 1, 2
+FINE_MODE_LAUNCHES, FINE_MODE_RESIDENT = 0, 1
 
 
 class SrcfdError(RuntimeError):
@@ -142,6 +143,9 @@ _protos = {
     "srcfd_fine_batch_get_state": (C.c_int, [_p, C.c_int, _p]),
     "srcfd_fine_batch_counters": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "srcfd_fine_batch_footprint": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "srcfd_fine_resident_supported": (C.c_int, [C.c_int, C.c_int]),
+    "srcfd_fine_batch_set_mode": (C.c_int, [_p, C.c_int]),
+    "srcfd_fine_solver_set_mode": (C.c_int, [_p, C.c_int]),
     "srcfd_adam_step": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _p]),
     "srcfd_stats_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "srcfd_stats_save": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),

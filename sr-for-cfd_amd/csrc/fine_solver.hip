@@ -153,12 +153,11 @@ __device__ __forceinline__ double atw(const Dev& g, const double* A, int k, int 
   return A[idx];
 }
 
-// ---------------------------------------------------------------- boundary conditions, apply_bc + apply_bfs_inlet of plane k
-__global__ void __launch_bounds__(NT) bc_kernel(BDev bd, int k) {
-  if (frozen(bd)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
-  const Bc& b = bd.cp[blockIdx.y].bc[k];
-  const int t = blockIdx.x * NT + threadIdx.x + 1;
+// ---------------------------------------------------------------- cell expressions
+// One copy of every expression: the launch-per-sweep kernels and the resident kernel (below) both call these, so a cell rounds the
+// same way on either path.
+// apply_bc + apply_bfs_inlet of plane k at edge index t (1 .. max(nx, ny))
+__device__ __forceinline__ void bc_cell(const Dev& g, const Bc& b, int k, int t) {
   double* V = g.Var + (size_t)k * g.sx;
   if (t <= g.ny) {
     const int j = t;
@@ -188,19 +187,7 @@ __global__ void __launch_bounds__(NT) bc_kernel(BDev bd, int k) {
   }
 }
 
-// ---------------------------------------------------------------- element-wise passes over the interior (one thread per cell)
-__device__ __forceinline__ bool interior(const BDev& g, int& i, int& j) {
-  const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
-  if (c >= (int64_t)g.nx * g.ny) return false;
-  i = (int)(c / g.ny) + 1;
-  j = (int)(c - (int64_t)(i - 1) * g.ny) + 1;
-  return true;
-}
-
-__global__ void __launch_bounds__(NT) linear_interpolation(BDev bd) {   // PyCFD_ML_accelerated.py:148-155
-  int i, j;
-  if (frozen(bd) || !interior(bd, i, j)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
+__device__ __forceinline__ void interpolation_cell(const Dev& g, int i, int j) {   // PyCFD_ML_accelerated.py:148-155
   const double* V = g.Var;
   double* F = g.Ff;
   const size_t c = (size_t)i * g.sy + j;
@@ -210,44 +197,29 @@ __global__ void __launch_bounds__(NT) linear_interpolation(BDev bd) {   // PyCFD
   F[3 * (size_t)g.sx + c] = -(at(g, V, 1, i, j) + at(g, V, 1, i, j - 1)) * g.dx * 0.5;
 }
 
-// Ends a momentum solve: the result sits in Jb when the case's own sweep count is odd; BFS under-relaxes against Old
+// Ends a momentum solve of `sweeps` sweeps: the result sits in Jb when the count is odd; BFS under-relaxes against Old
 // (bfs...:371-375).
-__global__ void __launch_bounds__(NT) momentum_finish(BDev bd, int k, int relax) {
-  int i, j;
-  if (frozen(bd) || !interior(bd, i, j)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
+__device__ __forceinline__ void finish_cell(const Dev& g, int k, int i, int j, int sweeps, int relax, double alpha) {
   const size_t c = (size_t)k * g.sx + (size_t)i * g.sy + j;
-  double v = (g.st->m_sweeps & 1) ? g.Jb[c] : g.Var[c];
+  double v = (sweeps & 1) ? g.Jb[c] : g.Var[c];
   if (relax) {
-    const double alpha = bd.cp[blockIdx.y].relax[k];
     const double o = g.Old[c];
     v = o + alpha * (v - o);
   }
   g.Var[c] = v;
 }
 
-__global__ void __launch_bounds__(NT) under_relax(BDev bd, int k) {
-  int i, j;
-  if (frozen(bd) || !interior(bd, i, j)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
-  const double alpha = bd.cp[blockIdx.y].relax[k];
+__device__ __forceinline__ void relax_cell(const Dev& g, int k, int i, int j, double alpha) {
   const size_t c = (size_t)k * g.sx + (size_t)i * g.sy + j;
   const double o = g.Old[c];
   g.Var[c] = o + alpha * (g.Var[c] - o);
 }
 
-__global__ void __launch_bounds__(NT) pressure_rhs(BDev bd) {   // the RHS of solve_pressure: Ff is constant inside the solve
-  int i, j;
-  if (frozen(bd) || !interior(bd, i, j)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
-  const size_t c = (size_t)i * g.sy + j;
-  g.rhs[c] = g.rho / g.dt * (g.Ff[c] + g.Ff[g.sx + c] + g.Ff[2 * (size_t)g.sx + c] + g.Ff[3 * (size_t)g.sx + c]);
+__device__ __forceinline__ double rhs_cell(const Dev& g, size_t c) {   // the RHS of solve_pressure: Ff is constant inside the solve
+  return g.rho / g.dt * (g.Ff[c] + g.Ff[g.sx + c] + g.Ff[2 * (size_t)g.sx + c] + g.Ff[3 * (size_t)g.sx + c]);
 }
 
-__global__ void __launch_bounds__(NT) update_flux(BDev bd) {   // PyCFD_ML_accelerated.py:242-249
-  int i, j;
-  if (frozen(bd) || !interior(bd, i, j)) return;
-  const Dev g = case_dev(bd, blockIdx.y);
+__device__ __forceinline__ void flux_cell(const Dev& g, int i, int j) {   // PyCFD_ML_accelerated.py:242-249
   const double* P = g.Var + 2 * (size_t)g.sx;
   double* F = g.Ff;
   const size_t c = (size_t)i * g.sy + j;
@@ -256,6 +228,125 @@ __global__ void __launch_bounds__(NT) update_flux(BDev bd) {   // PyCFD_ML_accel
   F[g.sx + c] += -g.dt / g.rho * (P[c + 1] - p) * g.dx / g.dy;
   F[2 * (size_t)g.sx + c] += -g.dt / g.rho * (P[c - g.sy] - p) * g.dy / g.dx;
   F[3 * (size_t)g.sx + c] += -g.dt / g.rho * (P[c - 1] - p) * g.dx / g.dy;
+}
+
+// One Jacobi update of plane k at (i, j): reads S, writes D, returns the residual R
+template <bool QUICK>
+__device__ __forceinline__ double momentum_cell(const Dev& g, const double* S, double* D, int k, int i, int j) {
+  const size_t c0 = (size_t)i * g.sy + j;
+  const double fe = g.Ff[c0], fn = g.Ff[g.sx + c0], fw = g.Ff[2 * (size_t)g.sx + c0], fs = g.Ff[3 * (size_t)g.sx + c0];
+  const double c = at(g, S, k, i, j);
+  const double ve = at(g, S, k, i + 1, j), vw_ = at(g, S, k, i - 1, j), vn = at(g, S, k, i, j + 1), vs = at(g, S, k, i, j - 1);
+  double ue, uw, un, us, sum = 0.0;
+  if (!QUICK) {   // simple_upwind, PyCFD_ML_accelerated.py:157-189
+    if (fe >= 0) { ue = c; sum += fe; } else ue = ve;
+    if (fw >= 0) { uw = c; sum += fw; } else uw = vw_;
+    if (fn >= 0) { un = c; sum += fn; } else un = vn;
+    if (fs >= 0) { us = c; sum += fs; } else us = vs;
+  } else {        // quick_scheme, :191-231
+    if (fe >= 0) { ue = 0.75 * c + 0.375 * ve - 0.125 * vw_; sum += 0.75 * fe; }
+    else { ue = 0.75 * ve + 0.375 * c - 0.125 * atw(g, S, k, i + 2, j); sum += 0.375 * fe; }
+    if (fw >= 0) { uw = 0.75 * c + 0.375 * vw_ - 0.125 * ve; sum += 0.75 * fw; }
+    else { uw = 0.75 * vw_ + 0.375 * c - 0.125 * atw(g, S, k, i - 2, j); sum += 0.375 * fw; }
+    if (fn >= 0) { un = 0.75 * c + 0.375 * vn - 0.125 * vs; sum += 0.75 * fn; }
+    else { un = 0.75 * vn + 0.375 * c - 0.125 * atw(g, S, k, i, j + 2); sum += 0.375 * fn; }
+    if (fs >= 0) { us = 0.75 * c + 0.375 * vs - 0.125 * vn; sum += 0.75 * fs; }
+    else { us = 0.75 * vs + 0.375 * c - 0.125 * atw(g, S, k, i, j - 2); sum += 0.375 * fs; }
+  }
+  const double Fc = ue * fe + uw * fw + un * fn + us * fs;
+  const double ap_c = sum * g.volp;
+  const double Fd = g.volp * ((ve - 2.0 * c + vw_) / (g.dx * g.dx) + (vn - 2.0 * c + vs) / (g.dy * g.dy));
+  const double ap_d = -g.volp * (2.0 / (g.dx * g.dx) + 2.0 / (g.dy * g.dy));
+  const double R = -(g.volp / g.dt * (c - at(g, g.Old, k, i, j)) + Fc + (-g.nu) * Fd);
+  const double ap = g.volp / g.dt + ap_c + (-g.nu) * ap_d;
+  D[(size_t)k * g.sx + c0] = c + R / ap;
+  return R;
+}
+
+__device__ __forceinline__ double pressure_ap_d(const Dev& g) { return -g.volp * (2.0 / (g.dx * g.dx) + 2.0 / (g.dy * g.dy)); }
+// One red-black update of the pressure plane P (global, or a copy of it in LDS) at flat index c, returns the residual R
+__device__ __forceinline__ double pressure_cell(const Dev& g, double* P, const double* rhs, size_t c, double ap_d) {
+  const double p = P[c];
+  const double Fd = g.volp * ((P[c + g.sy] - 2.0 * p + P[c - g.sy]) / (g.dx * g.dx) + (P[c + 1] - 2.0 * p + P[c - 1]) / (g.dy * g.dy));
+  const double R = rhs[c] - Fd;
+  P[c] = p + R / ap_d;
+  return R;
+}
+
+// correct_velocity at (i, j) (PyCFD_ML_accelerated.py:323-335); d: the changes of u, v, p against Old
+__device__ __forceinline__ void correct_cell(const Dev& g, int i, int j, double d[3]) {
+  const double* P = g.Var + 2 * (size_t)g.sx;
+  const size_t c = (size_t)i * g.sy + j;
+  const double u = g.Var[c] - g.dt / g.rho * (P[c + g.sy] - P[c - g.sy]) / (2 * g.dx);
+  const double v = g.Var[g.sx + c] - g.dt / g.rho * (P[c + 1] - P[c - 1]) / (2 * g.dy);
+  g.Var[c] = u;
+  g.Var[g.sx + c] = v;
+  d[0] = u - g.Old[c];
+  d[1] = v - g.Old[g.sx + c];
+  d[2] = P[c] - g.Old[2 * (size_t)g.sx + c];
+}
+
+// _convergence_check (PyCFD_ML_accelerated.py:472-505) from the three sums of squares: writes the residuals and returns the state.
+// Non-finite residuals are tested first: `r > tol` is false for NaN, so the converged test alone would take a NaN for convergence.
+__device__ __forceinline__ int convergence_state(const Dev& g, const CaseP& p, const double res[3], double rms[3]) {
+  int conv = 1, bad = 0;
+  for (int k = 0; k < 3; ++k) {
+    const double r = std::sqrt(res[k] / (g.nx * g.ny)) / g.dt;
+    rms[k] = r;
+    if (!std::isfinite(r)) bad = 1;
+    if (r > p.tol[k]) conv = 0;
+  }
+  return bad ? SRCFD_CASE_DIVERGED : conv ? SRCFD_CASE_CONVERGED : SRCFD_CASE_RUNNING;
+}
+
+// ---------------------------------------------------------------- boundary conditions, apply_bc + apply_bfs_inlet of plane k
+__global__ void __launch_bounds__(NT) bc_kernel(BDev bd, int k) {
+  if (frozen(bd)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
+  bc_cell(g, bd.cp[blockIdx.y].bc[k], k, blockIdx.x * NT + threadIdx.x + 1);
+}
+
+// ---------------------------------------------------------------- element-wise passes over the interior (one thread per cell)
+__device__ __forceinline__ bool interior(const BDev& g, int& i, int& j) {
+  const int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (c >= (int64_t)g.nx * g.ny) return false;
+  i = (int)(c / g.ny) + 1;
+  j = (int)(c - (int64_t)(i - 1) * g.ny) + 1;
+  return true;
+}
+
+__global__ void __launch_bounds__(NT) linear_interpolation(BDev bd) {
+  int i, j;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  interpolation_cell(case_dev(bd, blockIdx.y), i, j);
+}
+
+// Ends a momentum solve with the case's own sweep count
+__global__ void __launch_bounds__(NT) momentum_finish(BDev bd, int k, int relax) {
+  int i, j;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
+  finish_cell(g, k, i, j, g.st->m_sweeps, relax, relax ? bd.cp[blockIdx.y].relax[k] : 0.0);
+}
+
+__global__ void __launch_bounds__(NT) under_relax(BDev bd, int k) {
+  int i, j;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  relax_cell(case_dev(bd, blockIdx.y), k, i, j, bd.cp[blockIdx.y].relax[k]);
+}
+
+__global__ void __launch_bounds__(NT) pressure_rhs(BDev bd) {
+  int i, j;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  const Dev g = case_dev(bd, blockIdx.y);
+  const size_t c = (size_t)i * g.sy + j;
+  g.rhs[c] = rhs_cell(g, c);
+}
+
+__global__ void __launch_bounds__(NT) update_flux(BDev bd) {
+  int i, j;
+  if (frozen(bd) || !interior(bd, i, j)) return;
+  flux_cell(case_dev(bd, blockIdx.y), i, j);
 }
 
 // The three planes at `dst` = those at `src` (offsets in a case's block) for every case that is not frozen: the Jb copy before a
@@ -326,33 +417,7 @@ __global__ void __launch_bounds__(NT) momentum_sweep(BDev bd, int k, int m) {
   const int i = blockIdx.x + 1;
   double acc = 0.0;
   for (int j = 1 + threadIdx.x; j <= g.ny; j += NT) {
-    const size_t c0 = (size_t)i * g.sy + j;
-    const double fe = g.Ff[c0], fn = g.Ff[g.sx + c0], fw = g.Ff[2 * (size_t)g.sx + c0], fs = g.Ff[3 * (size_t)g.sx + c0];
-    const double c = at(g, S, k, i, j);
-    const double ve = at(g, S, k, i + 1, j), vw_ = at(g, S, k, i - 1, j), vn = at(g, S, k, i, j + 1), vs = at(g, S, k, i, j - 1);
-    double ue, uw, un, us, sum = 0.0;
-    if (!QUICK) {   // simple_upwind, PyCFD_ML_accelerated.py:157-189
-      if (fe >= 0) { ue = c; sum += fe; } else ue = ve;
-      if (fw >= 0) { uw = c; sum += fw; } else uw = vw_;
-      if (fn >= 0) { un = c; sum += fn; } else un = vn;
-      if (fs >= 0) { us = c; sum += fs; } else us = vs;
-    } else {        // quick_scheme, :191-231
-      if (fe >= 0) { ue = 0.75 * c + 0.375 * ve - 0.125 * vw_; sum += 0.75 * fe; }
-      else { ue = 0.75 * ve + 0.375 * c - 0.125 * atw(g, S, k, i + 2, j); sum += 0.375 * fe; }
-      if (fw >= 0) { uw = 0.75 * c + 0.375 * vw_ - 0.125 * ve; sum += 0.75 * fw; }
-      else { uw = 0.75 * vw_ + 0.375 * c - 0.125 * atw(g, S, k, i - 2, j); sum += 0.375 * fw; }
-      if (fn >= 0) { un = 0.75 * c + 0.375 * vn - 0.125 * vs; sum += 0.75 * fn; }
-      else { un = 0.75 * vn + 0.375 * c - 0.125 * atw(g, S, k, i, j + 2); sum += 0.375 * fn; }
-      if (fs >= 0) { us = 0.75 * c + 0.375 * vs - 0.125 * vn; sum += 0.75 * fs; }
-      else { us = 0.75 * vs + 0.375 * c - 0.125 * atw(g, S, k, i, j - 2); sum += 0.375 * fs; }
-    }
-    const double Fc = ue * fe + uw * fw + un * fn + us * fs;
-    const double ap_c = sum * g.volp;
-    const double Fd = g.volp * ((ve - 2.0 * c + vw_) / (g.dx * g.dx) + (vn - 2.0 * c + vs) / (g.dy * g.dy));
-    const double ap_d = -g.volp * (2.0 / (g.dx * g.dx) + 2.0 / (g.dy * g.dy));
-    const double R = -(g.volp / g.dt * (c - at(g, g.Old, k, i, j)) + Fc + (-g.nu) * Fd);
-    const double ap = g.volp / g.dt + ap_c + (-g.nu) * ap_d;
-    D[(size_t)k * g.sx + c0] = c + R / ap;
+    const double R = momentum_cell<QUICK>(g, S, D, k, i, j);
     acc = acc + R * R;
   }
   const double s = block_sum(acc, lds);
@@ -384,14 +449,10 @@ __global__ void __launch_bounds__(NT) pressure_half_sweep(BDev bd, int colour, i
   double* P = g.Var + 2 * (size_t)g.sx;
   const int i = blockIdx.x + 1;
   const int j0 = ((i + 1) & 1) == colour ? 1 : 2;   // first j of this colour in row i
-  const double ap_d = -g.volp * (2.0 / (g.dx * g.dx) + 2.0 / (g.dy * g.dy));
+  const double ap_d = pressure_ap_d(g);
   double acc = 0.0;
   for (int j = j0 + 2 * threadIdx.x; j <= g.ny; j += 2 * NT) {
-    const size_t c = (size_t)i * g.sy + j;
-    const double p = P[c];
-    const double Fd = g.volp * ((P[c + g.sy] - 2.0 * p + P[c - g.sy]) / (g.dx * g.dx) + (P[c + 1] - 2.0 * p + P[c - 1]) / (g.dy * g.dy));
-    const double R = g.rhs[c] - Fd;
-    P[c] = p + R / ap_d;
+    const double R = pressure_cell(g, P, g.rhs, (size_t)i * g.sy + j, ap_d);
     acc = acc + R * R;
   }
   const double s = block_sum(acc, lds);
@@ -411,17 +472,12 @@ __global__ void __launch_bounds__(NT) correct_velocity(BDev bd) {   // PyCFD_ML_
   const Dev g = case_dev(bd, blockIdx.y);
   const int i = blockIdx.x + 1;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  const double* P = g.Var + 2 * (size_t)g.sx;
   for (int j = 1 + threadIdx.x; j <= g.ny; j += NT) {
-    const size_t c = (size_t)i * g.sy + j;
-    const double u = g.Var[c] - g.dt / g.rho * (P[c + g.sy] - P[c - g.sy]) / (2 * g.dx);
-    const double v = g.Var[g.sx + c] - g.dt / g.rho * (P[c + 1] - P[c - 1]) / (2 * g.dy);
-    g.Var[c] = u;
-    g.Var[g.sx + c] = v;
-    const double d0 = u - g.Old[c], d1 = v - g.Old[g.sx + c], d2 = P[c] - g.Old[2 * (size_t)g.sx + c];
-    a0 = a0 + d0 * d0;
-    a1 = a1 + d1 * d1;
-    a2 = a2 + d2 * d2;
+    double d[3];
+    correct_cell(g, i, j, d);
+    a0 = a0 + d[0] * d[0];
+    a1 = a1 + d[1] * d[1];
+    a2 = a2 + d[2] * d[2];
   }
   const double s0 = block_sum(a0, lds), s1 = block_sum(a1, lds), s2 = block_sum(a2, lds);
   if (threadIdx.x == 0) {
@@ -432,8 +488,7 @@ __global__ void __launch_bounds__(NT) correct_velocity(BDev bd) {   // PyCFD_ML_
   }
 }
 
-// _convergence_check (PyCFD_ML_accelerated.py:472-505), one workgroup per case.  Non-finite residuals are tested first:
-// `r > tol` is false for NaN, so the converged test alone would take a NaN for convergence.
+// _convergence_check, one workgroup per case
 __global__ void __launch_bounds__(NT) convergence_check(BDev bd) {
   __shared__ double lds[NT];
   if (frozen(bd)) return;
@@ -441,16 +496,194 @@ __global__ void __launch_bounds__(NT) convergence_check(BDev bd) {
   double res[3];
   for (int k = 0; k < 3; ++k) res[k] = sum_partials(res_part(g) + (size_t)k * g.nx, g.nx, lds);
   if (threadIdx.x != 0) return;
-  const CaseP& p = bd.cp[blockIdx.y];
-  int conv = 1, bad = 0;
-  for (int k = 0; k < 3; ++k) {
-    const double r = std::sqrt(res[k] / (g.nx * g.ny)) / g.dt;
-    g.st->rms[k] = r;
-    if (!std::isfinite(r)) bad = 1;
-    if (r > p.tol[k]) conv = 0;
-  }
-  g.st->state = bad ? SRCFD_CASE_DIVERGED : conv ? SRCFD_CASE_CONVERGED : SRCFD_CASE_RUNNING;
+  g.st->state = convergence_state(g, bd.cp[blockIdx.y], res, g.st->rms);
 }
+
+// ---------------------------------------------------------------- the resident path: one workgroup per case, many outer iterations per launch
+// A mesh of at most RES_MAX x RES_MAX cells is small enough for one workgroup to run the whole outer loop of its case, every
+// inner sweep included, with __syncthreads() where the launch boundaries of the path above are.  Workgroups never read each
+// other's data, so the cases of a batch run at their own pace.  The cell expressions are the functions above; what differs is
+// only how the fixed-order sums are computed ("Resident"):
+//   a mesh row (pressure: a row's cells of one colour) sits in W consecutive lanes of one wave, W the power of two at or above
+//   the element count, and is reduced by the halving tree v[t] += v[t + s], s = W/2 .. 1.  The spec's 256-slot tree adds only
+//   zeros above W, and x + 0.0 is exact for the non-negative summands, so the bits are the spec's.  The row partials (at most
+//   256) are summed by the same tree in every wave (res_sum256).  Neither depends on the number of waves.
+// The momentum solves sweep the global planes.  The pressure solve holds P and rhs in LDS, which measured faster than sweeping
+// the global plane at every mesh size.  RES_MAX is the largest mesh at which this path measured faster than a launch per sweep.
+constexpr int RES_MAX = 64;                                   // largest nx or ny; srcfd_fine_resident_supported
+constexpr int RES_NT = 512;                                   // most threads of a workgroup; the host launches fewer on small meshes
+constexpr int RES_PLANE = (RES_MAX + 2) * (RES_MAX + 2);
+constexpr int RES_PARTS = 4 * RES_MAX;                        // pressure [parity][colour][row]; momentum [parity][row]; residuals [k][row]
+static_assert(2 * RES_MAX <= 256 && RES_MAX <= 64, "res_sum256 takes at most 256 partials, a row one element per lane");
+
+struct ResRec {      // one per case; written by the resident kernel when it leaves a launch, read by the host with the status blocks
+  int iters;               // outer iterations done in this launch
+  int last[3];             // sweeps of the u, v and p solves of the last of them
+  long long mom, prs;      // sweeps of this launch: momentum (u and v), pressure
+};
+
+__device__ __forceinline__ int pow2_at_least(int n) {
+  int w = 1;
+  while (w < n) w <<= 1;
+  return w;
+}
+// halving tree over each aligned group of w lanes (w a power of two, at most 64): the group's lane 0 gets the sum
+__device__ __forceinline__ double res_tree(double v, int w) {
+  for (int s = w >> 1; s > 0; s >>= 1) v = v + __shfl_down(v, s, 64);
+  return v;
+}
+// the 256-slot tree over p[0 .. n), n <= 256; every lane of the calling wave gets the sum
+__device__ __forceinline__ double res_sum256(const double* p, int n, int lane) {
+  const double a0 = lane < n ? p[lane] : 0.0, a1 = lane + 64 < n ? p[lane + 64] : 0.0;
+  const double a2 = lane + 128 < n ? p[lane + 128] : 0.0, a3 = lane + 192 < n ? p[lane + 192] : 0.0;
+  return __shfl(res_tree((a0 + a2) + (a1 + a3), 64), 0, 64);
+}
+
+struct ResLanes {    // how a pass deals rows to waves: `rows` rows per wave, w lanes each; this lane is slot t of row `seg` of them
+  int w, rows, seg, t;
+};
+__device__ __forceinline__ ResLanes res_lanes(int elements, int lane) {
+  ResLanes m;
+  m.w = elements > 32 ? 64 : pow2_at_least(elements);
+  m.rows = 64 / m.w;
+  m.seg = lane / m.w;
+  m.t = lane - m.seg * m.w;
+  return m;
+}
+
+// One pass over the mesh rows with NV sums of squares per row: cell(i, j, a) updates cell (i, j) and leaves the NV summands in a;
+// part[v * nx + i - 1] receives row i's sum v.
+template <int NV, class F>
+__device__ __forceinline__ void res_row_pass(const Dev& g, const ResLanes& m, int wave, int nwaves, double* part, F cell) {
+  for (int r0 = wave * m.rows; r0 < g.nx; r0 += nwaves * m.rows) {
+    const int i = r0 + m.seg + 1;
+    double a[NV];
+    for (int v = 0; v < NV; ++v) a[v] = 0.0;
+    if (i <= g.nx && m.t < g.ny) cell(i, m.t + 1, a);
+    for (int v = 0; v < NV; ++v) {
+      const double s = res_tree(a[v], m.w);
+      if (m.t == 0 && i <= g.nx) part[v * g.nx + i - 1] = s;
+    }
+  }
+}
+
+template <bool QUICK>
+__global__ void __launch_bounds__(RES_NT) resident_kernel(BDev bd, ResRec* recs, int n_it, int relax) {
+  __shared__ double P[RES_PLANE], rhs[RES_PLANE], part[RES_PARTS];   // the pressure plane and its right-hand side during the pressure solve
+  const int cse = blockIdx.x;
+  if (bd.st[cse].state != SRCFD_CASE_RUNNING) return;
+  const Dev g = case_dev(bd, cse);
+  const CaseP& cp = bd.cp[cse];
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthr >> 6;
+  const int nx = g.nx, ny = g.ny, cells = nx * ny, edge = nx > ny ? nx : ny;
+  const int plane = g.sx, planes3 = 3 * g.sx;
+  const ResLanes rowmap = res_lanes(ny, lane), colmap = res_lanes((ny + 1) / 2, lane);
+  double* const Pg = g.Var + 2 * (size_t)g.sx;
+  const double ap_d = pressure_ap_d(g);
+  int state = SRCFD_CASE_RUNNING, it = 0, sw[3] = {0, 0, 0};
+  long long tot_m = 0, tot_p = 0;
+  while (it < n_it && state == SRCFD_CASE_RUNNING) {
+    for (int k = 0; k < 2; ++k) {
+      for (int c = tid; c < planes3; c += nthr) g.Jb[c] = g.Var[c];
+      __syncthreads();
+      int n = 0;
+      for (int m = 0; m < SWEEP_CAP; ++m) {
+        if (m > 0 && std::sqrt(res_sum256(part + ((m - 1) & 1) * RES_MAX, nx, lane) / (g.nx * g.ny)) < INNER_TOL) break;
+        const double* S = (m & 1) ? g.Jb : g.Var;
+        double* D = (m & 1) ? g.Var : g.Jb;
+        res_row_pass<1>(g, rowmap, wave, nwaves, part + (m & 1) * RES_MAX, [&](int i, int j, double* a) {
+          const double R = momentum_cell<QUICK>(g, S, D, k, i, j);
+          a[0] = R * R;
+        });
+        __syncthreads();
+        n = m + 1;
+      }
+      sw[k] = n;
+      tot_m += n;
+      const double alpha = relax ? cp.relax[k] : 0.0;
+      for (int c = tid; c < cells; c += nthr) finish_cell(g, k, c / ny + 1, c % ny + 1, n, relax, alpha);
+      __syncthreads();
+      for (int t = tid + 1; t <= edge; t += nthr) bc_cell(g, cp.bc[k], k, t);
+      __syncthreads();
+    }
+    // linear_interpolation and pressure_rhs: a cell's rhs takes the four fluxes of that cell alone
+    for (int c = tid; c < cells; c += nthr) {
+      const int i = c / ny + 1, j = c % ny + 1;
+      interpolation_cell(g, i, j);
+      const size_t q = (size_t)i * g.sy + j;
+      const double r = rhs_cell(g, q);
+      g.rhs[q] = r;
+      rhs[q] = r;
+    }
+    for (int c = tid; c < plane; c += nthr) P[c] = Pg[c];
+    __syncthreads();
+    {
+      int n = 0;
+      for (int m = 0; m < SWEEP_CAP; ++m) {
+        if (m > 0 && std::sqrt(res_sum256(part + ((m - 1) & 1) * 2 * RES_MAX, 2 * nx, lane) / (g.nx * g.ny)) < INNER_TOL) break;
+        for (int colour = 0; colour < 2; ++colour) {
+          double* const out = part + (m & 1) * 2 * RES_MAX + colour * nx;
+          for (int r0 = wave * colmap.rows; r0 < nx; r0 += nwaves * colmap.rows) {
+            const int i = r0 + colmap.seg + 1;
+            const int j = (((i + 1) & 1) == colour ? 1 : 2) + 2 * colmap.t;   // the t-th cell of this colour in row i
+            double a = 0.0;
+            if (i <= nx && j <= ny) {
+              const double R = pressure_cell(g, P, rhs, (size_t)i * g.sy + j, ap_d);
+              a = R * R;
+            }
+            a = res_tree(a, colmap.w);
+            if (colmap.t == 0 && i <= nx) out[i - 1] = a;
+          }
+          __syncthreads();
+        }
+        n = m + 1;
+      }
+      sw[2] = n;
+      tot_p += n;
+    }
+    for (int c = tid; c < plane; c += nthr) Pg[c] = P[c];
+    __syncthreads();
+    if (relax) {
+      for (int c = tid; c < cells; c += nthr) relax_cell(g, 2, c / ny + 1, c % ny + 1, cp.relax[2]);
+      __syncthreads();
+    }
+    for (int t = tid + 1; t <= edge; t += nthr) bc_cell(g, cp.bc[2], 2, t);
+    __syncthreads();
+    res_row_pass<3>(g, rowmap, wave, nwaves, part, [&](int i, int j, double* a) {
+      double d[3];
+      correct_cell(g, i, j, d);
+      for (int v = 0; v < 3; ++v) a[v] = d[v] * d[v];
+    });
+    __syncthreads();
+    for (int k = 0; k < 2; ++k) {
+      for (int t = tid + 1; t <= edge; t += nthr) bc_cell(g, cp.bc[k], k, t);
+      __syncthreads();
+    }
+    for (int c = tid; c < cells; c += nthr) flux_cell(g, c / ny + 1, c % ny + 1);
+    double res[3], rms[3];
+    for (int k = 0; k < 3; ++k) res[k] = res_sum256(part + k * nx, nx, lane);
+    state = convergence_state(g, cp, res, rms);
+    if (tid == 0) {
+      for (int k = 0; k < 3; ++k) g.st->rms[k] = rms[k];
+      g.st->state = state;
+    }
+    ++it;
+    if (state == SRCFD_CASE_RUNNING)
+      for (int c = tid; c < planes3; c += nthr) g.Old[c] = g.Var[c];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    ResRec& r = recs[cse];
+    r.iters = it;
+    for (int k = 0; k < 3; ++k) r.last[k] = sw[k];
+    r.mom = tot_m;
+    r.prs = tot_p;
+  }
+}
+
+// The resident path's one rule, for the host and the device alike
+bool resident_mesh_ok(int nx, int ny) { return nx >= 3 && ny >= 3 && nx <= RES_MAX && ny <= RES_MAX; }
 
 // srcfd_coarse_solve's validation rules (coarse_solver.cpp)
 bool fine_problem_ok(const srcfd_coarse_problem* pb) {
@@ -472,7 +705,11 @@ struct FineBatch {
   std::vector<srcfd_coarse_problem> pb;
   int n = 0, device = 0;
   BDev g{};
-  PinnedBuf<Status> host_st;   // n blocks
+  PinnedBuf<char> host_mem;    // n status blocks, then n resident records: what one copy per chunk brings over
+  Status* host_st = nullptr;
+  const ResRec* host_rec = nullptr;
+  ResRec* d_rec = nullptr;
+  int mode = SRCFD_FINE_MODE_LAUNCHES;
   DevBuf<char> d_mem;
   Stream stream;               // declared last: destroyed before the memory its work uses
   size_t state_bytes = 0;      // fields and status blocks: what init clears
@@ -501,7 +738,7 @@ struct FineBatch {
   }
 
   // The problems have been validated by the caller.  One allocation: the cases' field blocks, then the status blocks, then the
-  // parameter blocks.
+  // resident records, then the parameter blocks.
   static int create(const std::string& who, const srcfd_coarse_problem* problems, int n_cases, int device, FineBatch** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error(who + "no HIP device"); return SRCFD_ENODEV; }
@@ -534,20 +771,23 @@ struct FineBatch {
       }
     }
     const size_t field_bytes = (size_t)n_cases * g.stride * sizeof(double);
-    s->state_bytes = field_bytes + (size_t)n_cases * sizeof(Status);
+    s->state_bytes = field_bytes + (size_t)n_cases * (sizeof(Status) + sizeof(ResRec));
     const size_t total = s->state_bytes + (size_t)n_cases * sizeof(CaseP);
     int rc = s->d_mem.alloc(total);
     if (rc) return rc;
     char* const mem = s->d_mem.get();
     g.base = reinterpret_cast<double*>(mem);
     g.st = reinterpret_cast<Status*>(mem + field_bytes);
+    s->d_rec = reinterpret_cast<ResRec*>(g.st + n_cases);
     g.cp = reinterpret_cast<const CaseP*>(mem + s->state_bytes);
     HIPCHECK_F(hipMemset(mem, 0, s->state_bytes));
     HIPCHECK_F(hipMemcpy(mem + s->state_bytes, cp.data(), cp.size() * sizeof(CaseP), hipMemcpyHostToDevice));
     HIPCHECK_F(hipStreamCreateWithFlags(s->stream.out(), hipStreamNonBlocking));
-    rc = s->host_st.alloc((size_t)n_cases);
+    rc = s->host_mem.alloc((size_t)n_cases * (sizeof(Status) + sizeof(ResRec)));
     if (rc) return rc;
-    std::memset(s->host_st.get(), 0, (size_t)n_cases * sizeof(Status));
+    std::memset(s->host_mem.get(), 0, s->host_mem.size());
+    s->host_st = reinterpret_cast<Status*>(s->host_mem.get());
+    s->host_rec = reinterpret_cast<const ResRec*>(s->host_st + n_cases);
     *out = s.release();
     return SRCFD_OK;
   }
@@ -558,9 +798,9 @@ struct FineBatch {
     if (e != hipSuccess) { set_error(std::string("fine solver: kernel launch failed: ") + hipGetErrorString(e)); return SRCFD_EHIP; }
     return SRCFD_OK;
   }
-  int sync_status() {   // all n status blocks in one copy
+  int sync_status(bool records = false) {   // all n status blocks (and resident records) in one copy
     ++n_sync;
-    HIPCHECK_F(hipMemcpyAsync(host_st.get(), g.st, (size_t)n * sizeof(Status), hipMemcpyDeviceToHost, stream));
+    HIPCHECK_F(hipMemcpyAsync(host_st, g.st, (size_t)n * (sizeof(Status) + (records ? sizeof(ResRec) : 0)), hipMemcpyDeviceToHost, stream));
     HIPCHECK_F(hipStreamSynchronize(stream));
     return SRCFD_OK;
   }
@@ -680,14 +920,14 @@ struct FineBatch {
       if ((rc = sync_status())) return rc;
       bool all_stopped = true;
       for (int c = 0; c < n; ++c)
-        if (live(c) && !(which < 2 ? host_st.get()[c].m_stop : host_st.get()[c].p_stop)) all_stopped = false;
+        if (live(c) && !(which < 2 ? host_st[c].m_stop : host_st[c].p_stop)) all_stopped = false;
       if (all_stopped || done >= SWEEP_CAP) break;
       chunk = chunk < 8 ? 8 : 2 * chunk;
     }
     int most = 0;
     for (int c = 0; c < n; ++c) {
       if (!live(c)) continue;
-      const int s = which < 2 ? host_st.get()[c].m_sweeps : host_st.get()[c].p_sweeps;
+      const int s = which < 2 ? host_st[c].m_sweeps : host_st[c].p_sweeps;
       last_sweeps[3 * c + which] = s;
       if (s > most) most = s;
     }
@@ -730,25 +970,67 @@ struct FineBatch {
     return sync_status();
   }
 
+  int set_mode(const std::string& who, int m) {
+    if (m != SRCFD_FINE_MODE_LAUNCHES && m != SRCFD_FINE_MODE_RESIDENT) { set_error(who + ": unknown mode " + std::to_string(m)); return SRCFD_EINVAL; }
+    if (m == SRCFD_FINE_MODE_RESIDENT && !resident_mesh_ok(g.nx, g.ny)) {
+      set_error(who + ": the resident mode takes meshes of at most " + std::to_string(RES_MAX) + " x " + std::to_string(RES_MAX) + " cells, not " +
+                std::to_string(g.nx) + " x " + std::to_string(g.ny));
+      return SRCFD_EINVAL;
+    }
+    mode = m;
+    return SRCFD_OK;
+  }
+
+  // Resident mode: up to n_it outer iterations of every live case in one launch, one workgroup per case; then one copy of the
+  // status blocks and the records.  The workgroup has one wave per 128 cells: the bits do not depend on it.
+  int resident_chunk(int n_it) {
+    int waves = (g.nx * g.ny + 127) / 128;
+    waves = waves < 1 ? 1 : waves > RES_NT / 64 ? RES_NT / 64 : waves;
+    const int relax = bfs() ? 1 : 0;
+    if (pb[0].scheme == SRCFD_SCHEME_QUICK) hipLaunchKernelGGL(resident_kernel<true>, dim3(n), dim3(64 * waves), 0, stream, g, d_rec, n_it, relax);
+    else hipLaunchKernelGGL(resident_kernel<false>, dim3(n), dim3(64 * waves), 0, stream, g, d_rec, n_it, relax);
+    int rc = launched();
+    if (rc) return rc;
+    return sync_status(true);
+  }
+
   // Up to max_iterations outer iterations of the live cases; history [n][history_len][3], the other outputs per case.
+  // Launch mode advances one iteration at a time; resident mode in chunks that end at the next multiple of 100 of the common
+  // iteration count (where residual_history wants Status::rms) or with the budget.
   int run(int max_iterations, int* iterations, int* status, double* rms_out, double* history, int history_len) {
     HIPCHECK_F(hipSetDevice(device));
     std::vector<int> n_hist((size_t)n, 0);
-    for (int it = 0; it < max_iterations && any_live(); ++it) {
-      ++count;
-      int rc = outer();
+    for (int left = max_iterations; left > 0 && any_live();) {
+      const bool resident = mode == SRCFD_FINE_MODE_RESIDENT;
+      int step = 1;
+      if (resident) {
+        step = 100 - count % 100;
+        if (step > left) step = left;
+      }
+      int rc = resident ? resident_chunk(step) : outer();
       if (rc) { primed = false; return rc; }
+      left -= step;
+      count += step;
+      int64_t most_m = 0, most_p = 0;
       for (int c = 0; c < n; ++c) {
         if (!live(c)) continue;
-        const Status& st = host_st.get()[c];
-        iters[c] = count;
+        const Status& st = host_st[c];
+        const int did = resident ? host_rec[c].iters : step;
+        if (resident) {
+          for (int k = 0; k < 3; ++k) last_sweeps[3 * c + k] = host_rec[c].last[k];
+          if (host_rec[c].mom > most_m) most_m = host_rec[c].mom;
+          if (host_rec[c].prs > most_p) most_p = host_rec[c].prs;
+        }
+        iters[c] = count - step + did;
         state[c] = st.state;   // a diverged case is frozen on the device already; the others go on
         for (int k = 0; k < 3; ++k) rms[3 * c + k] = st.rms[k];
-        if (count % 100 == 0 && n_hist[c] < history_len) {   // residual_history (PyCFD_ML_accelerated.py:418-421), at the case's own iterations 100, 200, ...
+        if (did == step && count % 100 == 0 && n_hist[c] < history_len) {   // residual_history (PyCFD_ML_accelerated.py:418-421), at the case's own iterations 100, 200, ...
           for (int k = 0; k < 3; ++k) history[((size_t)c * history_len + n_hist[c]) * 3 + k] = st.rms[k];
           ++n_hist[c];
         }
       }
+      n_mom += most_m;
+      n_p += most_p;
     }
     for (int c = 0; c < n; ++c) {
       if (iterations) iterations[c] = iters[c];
@@ -854,14 +1136,30 @@ int srcfd_fine_solver_counters(const srcfd_fine_solver* s, int64_t counters[4], 
   });
 }
 
+int srcfd_fine_solver_set_mode(srcfd_fine_solver* s, int mode) {
+  return srcfd::abi_guard("srcfd_fine_solver_set_mode", [&]() -> int {
+    if (!s) { set_error("srcfd_fine_solver_set_mode: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(s)->set_mode("srcfd_fine_solver_set_mode", mode);
+  });
+}
+
 // ---------------------------------------------------------------- batches
+int srcfd_fine_resident_supported(int nx, int ny) { return srcfd::resident_mesh_ok(nx, ny) ? 1 : 0; }
+
+int srcfd_fine_batch_set_mode(srcfd_fine_batch* b, int mode) {
+  return srcfd::abi_guard("srcfd_fine_batch_set_mode", [&]() -> int {
+    if (!b) { set_error("srcfd_fine_batch_set_mode: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(b)->set_mode("srcfd_fine_batch_set_mode", mode);
+  });
+}
+
 int srcfd_fine_batch_footprint(int nx, int ny, int n_cases, int64_t* device_bytes) {
   return srcfd::abi_guard("srcfd_fine_batch_footprint", [&]() -> int {
     if (!device_bytes || nx < 3 || ny < 3 || nx > 4096 || ny > 4096 || n_cases < 1 || n_cases > srcfd::MAX_CASES) {
       set_error("srcfd_fine_batch_footprint: bad arguments");
       return SRCFD_EINVAL;
     }
-    *device_bytes = (int64_t)n_cases * (int64_t)(srcfd::case_doubles(nx, ny) * sizeof(double) + sizeof(srcfd::Status) + sizeof(srcfd::CaseP));
+    *device_bytes = (int64_t)n_cases * (int64_t)(srcfd::case_doubles(nx, ny) * sizeof(double) + sizeof(srcfd::Status) + sizeof(srcfd::ResRec) + sizeof(srcfd::CaseP));
     return SRCFD_OK;
   });
 }

@@ -222,25 +222,29 @@ def generate_simulation_file(path, reynolds_numbers: Iterable[int] = range(100, 
                              bc=LDC_DOUBLE_LID, bc_type: str = "double_lid(u_top=1,u_bottom=1)",
                              case_name: str = "double lid driven cavity", dt: float = 0.001, scheme: str = "QUICK",
                              convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
-                             max_batch: int = 8, device: int = 0, solve: Optional[Callable] = None) -> List[Tuple[int, int, int, int]]:
+                             max_batch: int = 8, device: int = 0, solve: Optional[Callable] = None,
+                             resident=False) -> List[Tuple[int, int, int, int]]:
     """The data-creation notebook's sweep (sr-simulation-data-creation.ipynb cell 2): every Reynolds number on every n x n mesh
     from zero fields, one `Re{Re}_mesh{n}x{n}` group each in `path`, which `load_paired_reynolds_multi` reads.  Per mesh size
     the Reynolds numbers are solved `max_batch` at a time by `fine.run_normal_simulations` (or by `solve`, a callable of that
     signature), and the file is saved after every batch.  Groups already in the file are kept (the notebook appends); a group
     of the same name is replaced.  A diverged case is reported and not written; one that only reached `max_iterations` is
-    written, like the notebook's.  -> [(Re, n, iterations, status)] with fine.FineSolverBatch's status codes."""
+    written, like the notebook's.  `resident` (False, True or "auto", as fine.FineSolverBatch.set_resident) is handed to the
+    solve as a keyword unless it is False; "auto" runs the small meshes of the sweep resident and the others as before.
+    -> [(Re, n, iterations, status)] with fine.FineSolverBatch's status codes."""
     if max_batch < 1:
         raise ValueError("max_batch must be at least 1")
     if solve is None:
         from .fine import run_normal_simulations as solve
     reynolds_numbers = list(reynolds_numbers)
+    mode = {} if resident is False else {"resident": resident}
     done: Dict[str, tuple] = {}           # group -> (Re, n, fields) of this call, in the order the file gets them
     record = []
     for n in mesh_sizes:
         for a in range(0, len(reynolds_numbers), max_batch):
             res = reynolds_numbers[a:a + max_batch]
             results = solve(res, n, n, dt=dt, scheme=scheme, convergence_criteria=convergence_criteria, max_iterations=max_iterations,
-                            bc=bc, max_batch=max_batch, device=device)
+                            bc=bc, max_batch=max_batch, device=device, **mode)
             for Re, (fields, iterations, status) in zip(res, results):
                 record.append((Re, n, int(iterations), int(status)))
                 if status != 2:

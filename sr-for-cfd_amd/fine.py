@@ -14,6 +14,10 @@ is a batch of one), each with the bits of a `FineSolver` of its own; `run_normal
 `FineSolverBatch.init_from_prediction` warm-starts any subset of a batch from one SR call (srcfd_fine_batch_init_from_prediction);
 `run_ml_accelerated_fine_simulations` / `run_bfs_ml_accelerated_fine_simulations` are the warm-started drop-ins for a sweep, and
 `compare_ml_and_normal_simulations` / `compare_bfs_ml_and_normal_simulations` run each Reynolds number warm and cold in one batch.
+
+`resident=` (False, True or "auto") on the solver classes and the sweep functions selects the resident mode for meshes of at most
+64 x 64 cells (`resident_supported`): one workgroup per case runs many outer iterations per launch, with the same bits.
+`run_coarse_simulations` / `run_bfs_coarse_simulations` solve the coarse fields of a whole sweep as one resident batch.
 """
 from __future__ import annotations
 
@@ -69,10 +73,26 @@ def problem(Re: float, nx: int, ny: int, lx: float = 1.0, ly: float = 1.0, dt: f
     return pb
 
 
-class FineSolver:
-    """Device-resident float64 solver state for one problem (srcfd_fine_solver_*).  Starts from `_initialize_fields`."""
+def resident_supported(nx: int, ny: int) -> bool:
+    """Whether an nx x ny mesh can run in the resident mode (srcfd_fine_resident_supported; needs no device)."""
+    return bool(L.lib.srcfd_fine_resident_supported(int(nx), int(ny)))
 
-    def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0):
+
+def _resident_mode(resident, nx: int, ny: int) -> int:
+    """The srcfd mode of a `resident=` keyword: False launches, True resident (the library refuses an unsupported mesh),
+    "auto" resident where `resident_supported` holds."""
+    if resident == "auto":
+        return L.FINE_MODE_RESIDENT if resident_supported(nx, ny) else L.FINE_MODE_LAUNCHES
+    if resident is True or resident is False:
+        return L.FINE_MODE_RESIDENT if resident else L.FINE_MODE_LAUNCHES
+    raise ValueError(f"resident must be False, True or 'auto', not {resident!r}")
+
+
+class FineSolver:
+    """Device-resident float64 solver state for one problem (srcfd_fine_solver_*).  Starts from `_initialize_fields`.
+    `resident`: see `set_resident`."""
+
+    def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0, resident=False):
         self.problem = pb
         self.max_iterations = int(max_iterations)
         self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
@@ -81,6 +101,12 @@ class FineSolver:
         self.rms = np.zeros(3)
         self._h = C.c_void_p()
         L.check(L.lib.srcfd_fine_solver_create(C.byref(pb), int(device), C.byref(self._h)))
+        self.resident = False
+        try:
+            self.set_resident(resident)
+        except ValueError:
+            self.close()
+            raise
         self.init()
 
     def close(self) -> None:
@@ -90,6 +116,16 @@ class FineSolver:
 
     def __del__(self):
         self.close()
+
+    def set_resident(self, resident) -> bool:
+        """False: one launch per inner sweep (the default).  True: the resident mode, one workgroup for the case and up to 100
+        outer iterations per launch; ValueError on a mesh that `resident_supported` refuses, and the solver keeps its mode.
+        "auto": resident where supported.  The bits are the same, and the mode may change between any two `run` calls.
+        Returns whether the solver is now resident."""
+        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny)
+        L.check(L.lib.srcfd_fine_solver_set_mode(self._h, mode))
+        self.resident = mode == L.FINE_MODE_RESIDENT
+        return self.resident
 
     @property
     def shape(self):
@@ -177,9 +213,9 @@ class FineSolver:
 class FineSolverBatch:
     """B cases of one mesh, scheme and case type in one set of launches (srcfd_fine_batch_*): each case computes what a
     `FineSolver` of its own computes, bit for bit.  `status[i]` is 0 while case i runs (or only the iteration budget ended),
-    1 converged, 2 diverged (non-finite residuals; the other cases go on, nothing is raised)."""
+    1 converged, 2 diverged (non-finite residuals; the other cases go on, nothing is raised).  `resident`: see `set_resident`."""
 
-    def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0):
+    def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0, resident=False):
         self.problems = list(problems)
         self.n_cases = len(self.problems)
         self.max_iterations = int(max_iterations)
@@ -188,7 +224,23 @@ class FineSolverBatch:
         L.check(L.lib.srcfd_fine_batch_create(arr, self.n_cases, int(device), C.byref(self._h)))
         pb = self.problems[0]
         self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
+        self.resident = False
+        try:
+            self.set_resident(resident)
+        except ValueError:
+            self.close()
+            raise
         self.init()
+
+    def set_resident(self, resident) -> bool:
+        """False: every case shares one launch per inner sweep (the default).  True: the resident mode, one workgroup per case
+        and up to 100 outer iterations per launch, so that no case waits for another's inner solves; ValueError on a mesh that
+        `resident_supported` refuses, and the batch keeps its mode.  "auto": resident where supported.  The bits are the same,
+        and the mode may change between any two `run` calls.  Returns whether the batch is now resident."""
+        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny)
+        L.check(L.lib.srcfd_fine_batch_set_mode(self._h, mode))
+        self.resident = mode == L.FINE_MODE_RESIDENT
+        return self.resident
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -335,13 +387,13 @@ def _per_case(bc, n):
     return [bc] * n
 
 
-def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=None):
+def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=None, resident=False):
     """warm_start(batch, a): starts the batch of problems[a : a + batch.n_cases] (default: from zero fields, as created)."""
     if max_batch < 1:
         raise ValueError("max_batch must be at least 1")
     out = []
     for a in range(0, len(problems), max_batch):
-        b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device)
+        b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device, resident=resident)
         try:
             if warm_start is not None:
                 warm_start(b, a)
@@ -354,14 +406,59 @@ def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=No
 
 def run_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: float = 0.001, scheme: str = "QUICK",
                            convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
-                           max_batch: int = 8, device: int = 0) -> list:
+                           max_batch: int = 8, device: int = 0, resident=False) -> list:
     """`run_normal_simulation` for a list of Reynolds numbers, `max_batch` cases at a time on the batched device solver:
     a list of (fields, iterations, status) in input order; fields are the (ny, nx) u, v, p, status as FineSolverBatch's.
-    `bc`: one boundary-condition set or a list with one per Reynolds number."""
+    `bc`: one boundary-condition set or a list with one per Reynolds number.  `resident`: as FineSolverBatch.set_resident."""
     reynolds = list(reynolds)
     bcs = _per_case(bc, len(reynolds))
     pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs)]
-    return _solve_in_batches(pbs, max_iterations, max_batch, device)
+    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident)
+
+
+def _coarse_sweep(problems, reynolds, max_iterations, max_batch, device, output_dir, name_of, bfs_step_height=None):
+    out = _solve_in_batches(problems, max_iterations, max_batch, device, resident=True)
+    fields_list = []
+    for pb, Re, (fields, _, status) in zip(problems, reynolds, out):
+        if status == L.CASE_DIVERGED:
+            raise ValueError(f"Solver failed: NaN/Inf in residuals (Re {Re})")
+        if output_dir is not None:
+            os.makedirs(output_dir, exist_ok=True)
+            save_coarse_fields(os.path.join(output_dir, name_of(Re)), fields, Re, pb.lx, pb.ly, bfs_step_height=bfs_step_height)
+        fields_list.append(fields)
+    return fields_list
+
+
+def run_coarse_simulations(reynolds: Sequence[float], lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
+                           convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
+                           output_dir: Optional[str] = None, bc=None, max_batch: int = 64, device: int = 0) -> List[Dict[str, np.ndarray]]:
+    """`coarse.run_coarse_simulation` (same arguments and defaults) for a list of Reynolds numbers on the device: one resident
+    batch serves up to `max_batch` (at most 64) of them, each case in a workgroup of its own.  Returns the {'u','v','p'} dicts
+    of (lr_dim, lr_dim) fields in input order: the `coarse_fields_list` of the warm-started sweeps.  `bc`: one set or one per
+    Reynolds number.  These solves follow the device's sweep order (Jacobi momentum, red-black pressure;
+    tests/fine_solver_spec.py), not the host's serial sweeps of `srcfd_coarse_solve`: the same fixed point -- the reference's
+    stored coarse fields pin both to 6e-8 -- reached along another trajectory, so iteration counts and the last bits differ
+    from `coarse.run_coarse_simulation`.  A diverged case raises ValueError, as the host function does."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [problem(Re, lr_dim, lr_dim, 1.0, 1.0, dt, scheme, convergence_criteria, b) for Re, b in zip(reynolds, bcs)]
+    return _coarse_sweep(pbs, reynolds, max_iterations, max_batch, device, output_dir,
+                         lambda Re: f"coarse_Re{Re}_{lr_dim}x{lr_dim}_{max_iterations}_coarse_iterations.h5")
+
+
+def run_bfs_coarse_simulations(reynolds: Sequence[float], lr_dim: int = 10, dt: float = 0.002, scheme: str = "UPWIND",
+                               convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
+                               output_dir: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0,
+                               lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None,
+                               max_batch: int = 64, device: int = 0) -> List[Dict[str, np.ndarray]]:
+    """`coarse.run_bfs_coarse_simulation` for a list of Reynolds numbers, as `run_coarse_simulations` (the device's sweep order:
+    the host solver's fixed point, not its trajectory)."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [problem(Re, lr_dim, lr_dim, lx, ly, dt, scheme, convergence_criteria, b, bfs={"step_height": step_height, "h": h, "Ub": Ub},
+                   relaxation_factors=relaxation_factors) for Re, b in zip(reynolds, bcs)]
+    return _coarse_sweep(pbs, reynolds, max_iterations, max_batch, device, output_dir,
+                         lambda Re: f"bfs_coarse_Re{Re}_{lr_dim}x{lr_dim}_{max_iterations}_coarse_iterations.h5", bfs_step_height=step_height)
 
 
 def _model_files(stats_file, encoder_file, decoder_file):
@@ -374,9 +471,9 @@ def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re:
                                        dt: float = 0.001, scheme: str = "QUICK", convergence_criteria: Optional[Dict[str, float]] = None,
                                        max_iterations_fine: int = 100000, output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                        encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                       precision: Optional[str] = None) -> tuple:
+                                       precision: Optional[str] = None, resident=False) -> tuple:
     """PyCFD_ML_accelerated.py:1024-1123: coarse fields -> SR straight into the device solver state -> fine solve.  The only
-    400x400 field that crosses to the host is the result (`solver.Var`, on demand)."""
+    400x400 field that crosses to the host is the result (`solver.Var`, on demand).  `resident`: as FineSolver.set_resident."""
     from . import pipeline
     stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}.txt"
     encoder_file = encoder_file or f"vanilla_encoder{lr_dim}_to_{nx}.h5"
@@ -385,13 +482,14 @@ def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re:
     _model_files(stats_file, encoder_file, decoder_file)
     model, x, ain, aout, back, _ = pipeline._prepare(coarse_fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0,
                                                      False, 0.3, precision, pipeline._quiet)
-    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations_fine, model.device)
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations_fine, model.device,
+                   resident=resident)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated")
 
 
 def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch, output_name, suffix_of, bfs_step_height=None,
-                every=1):
+                every=1, resident=False):
     """The batched warm-started solve behind the sweep drop-ins.  `problems` holds `every` consecutive cases per coarse field,
     of which the first is warm-started from it and the others start from zero; prepare(fields) is pipeline._prepare_batch for
     a list of coarse fields.  The prediction of a batch holds the fields of that batch's warm cases only."""
@@ -406,7 +504,7 @@ def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch
         cases = None if every == 1 else [every * i for i in range(n_warm)]
         pipeline._warn_nonfinite(b.init_from_prediction(model, x, ain, aout, back, cases=cases))
 
-    out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start)
+    out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start, resident=resident)
     if output_name is not None:
         for i, (fields, _, _) in enumerate(out):
             name = f"{output_name}_Re{problems[i].reynolds:g}{suffix_of(i)}"
@@ -430,7 +528,7 @@ def _paired(out, reynolds):
 
 
 def _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
-               encoder_file, decoder_file, bc, precision, max_batch, device, every):
+               encoder_file, decoder_file, bc, precision, max_batch, device, every, resident=False):
     from . import pipeline
     reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
     if len(coarse_fields_list) != len(reynolds):
@@ -444,7 +542,7 @@ def _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, converg
     prepare = lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0, False, 0.3,
                                                      precision, device)
     return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
-                       lambda i: "_accelerated" if i % every == 0 else "_normal", every=every)
+                       lambda i: "_accelerated" if i % every == 0 else "_normal", every=every, resident=resident)
 
 
 def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -452,15 +550,17 @@ def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, n
                                         convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                                         output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                         encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                        precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+                                        precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                        device: Optional[int] = None) -> list:
     """`run_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, `max_batch` cases at a time:
     one SR call per batch straight into the batched device solver, then the batched solve.  Returns a list of (fields,
     iterations, status) in input order, as `run_normal_simulations`.  `bc`: one boundary-condition set or one per case.
     `output_name`: None writes nothing; otherwise each case's fields go to `{output_name}_Re{Re}_accelerated.h5`.  `device`:
     None lets the model loader choose.  A case's initial field has the bits of its batch's prediction (see
-    FineSolverBatch.init_from_prediction); with max_batch=1 every case equals the single-case function bit for bit."""
+    FineSolverBatch.init_from_prediction); with max_batch=1 every case equals the single-case function bit for bit.
+    `resident`: as FineSolverBatch.set_resident."""
     return _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
-                      stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 1)
+                      stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 1, resident)
 
 
 def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -468,14 +568,15 @@ def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.
                                       convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                                       output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                       encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                      precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+                                      precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                      device: Optional[int] = None) -> list:
     """The reference's headline experiment (PyCFD_ML_accelerated.py:1431-1499) for a sweep: every Reynolds number goes into the
     batch twice, case 2i warm-started from its coarse field and case 2i + 1 from zero fields, under the same iteration cap.
     Returns one dict per Reynolds number: Re, ml_iterations, normal_iterations, ml_status, normal_status, iterations_saved
     (normal - ml), ratio (normal / ml) and both results' fields.  Whether iterations are saved depends on the decoder's
     weights; the function only reports the counts."""
     out = _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
-                     stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 2)
+                     stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 2, resident)
     return _paired(out, list(reynolds))
 
 
@@ -510,13 +611,14 @@ def run_bfs_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.002, sc
 def run_bfs_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: float = 0.002, scheme: str = "UPWIND",
                                convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
                                step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
-                               relaxation_factors: Optional[Dict[str, float]] = None, max_batch: int = 8, device: int = 0) -> list:
+                               relaxation_factors: Optional[Dict[str, float]] = None, max_batch: int = 8, device: int = 0,
+                               resident=False) -> list:
     """`run_bfs_normal_simulation` for a list of Reynolds numbers, batched as `run_normal_simulations`."""
     reynolds = list(reynolds)
     bcs = _per_case(bc, len(reynolds))
     pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
            for Re, b in zip(reynolds, bcs)]
-    return _solve_in_batches(pbs, max_iterations, max_batch, device)
+    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident)
 
 
 def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re: float, nx: int, ny: int, lr_dim: int = 10,
@@ -527,7 +629,7 @@ def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray],
                                            Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                            relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                            use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                           precision: Optional[str] = None) -> tuple:
+                                           precision: Optional[str] = None, resident=False) -> tuple:
     """bfs_ml_accelerated.py:1384-1518 (the BFS `ml_super_resolution`: adaptive normalisation, optional aspect-ratio resampling)."""
     from . import pipeline
     stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}_swish_trained_upto_700_multiBC.txt"
@@ -539,14 +641,14 @@ def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray],
                                                      use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor, precision,
                                                      pipeline._quiet)
     s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
-                   max_iterations_fine, model.device)
+                   max_iterations_fine, model.device, resident=resident)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
 
 
 def _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
                encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-               use_adaptive_normalization, blend_factor, precision, max_batch, device, every):
+               use_adaptive_normalization, blend_factor, precision, max_batch, device, every, resident=False):
     from . import pipeline
     reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
     if len(coarse_fields_list) != len(reynolds):
@@ -561,7 +663,8 @@ def _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, converg
     prepare = lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, stats_file, encoder_file, decoder_file, use_aspect_ratio_correction,
                                                      lx, ly, use_adaptive_normalization, blend_factor, precision, device)
     return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
-                       lambda i: "_accelerated" if i % every == 0 else "_normal", bfs_step_height=step_height, every=every)
+                       lambda i: "_accelerated" if i % every == 0 else "_normal", bfs_step_height=step_height, every=every,
+                       resident=resident)
 
 
 def run_bfs_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -572,12 +675,13 @@ def run_bfs_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[st
                                             step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                             relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                             use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                            precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+                                            precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                            device: Optional[int] = None) -> list:
     """`run_bfs_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, batched as
     `run_ml_accelerated_fine_simulations`."""
     return _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
                       stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 1)
+                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 1, resident)
 
 
 def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -588,9 +692,10 @@ def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str,
                                           step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                           relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                           use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                          precision: Optional[str] = None, max_batch: int = 8, device: Optional[int] = None) -> list:
+                                          precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                          device: Optional[int] = None) -> list:
     """`compare_ml_and_normal_simulations` for the backward-facing step (bfs_ml_accelerated.py main)."""
     out = _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
                      stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-                     use_adaptive_normalization, blend_factor, precision, max_batch, device, 2)
+                     use_adaptive_normalization, blend_factor, precision, max_batch, device, 2, resident)
     return _paired(out, list(reynolds))

@@ -23,6 +23,15 @@ limit of its own and chain them, e.g.
 
     timeout -k 10 120 python tools/fine_solver_bench.py --handoff 1,8,16 --repeats 7 > handoff.json &&
     timeout -k 10 120 python tools/fine_solver_bench.py --handoff 1,8,16 --repeats 7 --single-only > handoff_single.json
+
+With --resident it times the resident mode (srcfd_fine_batch_set_mode, one workgroup per case) against the launch-per-sweep mode
+on small meshes instead: per configuration (LDC QUICK double lid with Re spread over 100..800, BFS UPWIND Re 400), mesh of
+--mesh and batch size of --batch, --repeats times each mode on a fresh handle, the two modes alternating, --warmup untimed
+iterations and then --iters timed ones.  One JSON line: every repeat's ms per outer iteration of the batch, the medians and
+ranges, and whether the resident median lies below the whole range of the launch mode.  --pinned adds the wall seconds of the
+59 765-iteration 10x10 Re 800 run of tests/test_gpu_fine_solver.py in both modes.
+
+    python tools/fine_solver_bench.py --resident --mesh 10,20,30,40,50,64 --batch 1,8 --iters 10 --warmup 2 [--pinned]
 """
 import argparse
 import importlib
@@ -78,6 +87,51 @@ def batch_bench(a, fine, coarse):
                 "host_syncs": c["host_syncs"],
             })
         out["batch"][str(B)] = {"reynolds": res, "repeats": rows}
+    print(json.dumps(out))
+
+
+def resident_bench(a, fine, coarse):
+    bfs = {"step_height": 1.0, "h": 2.0, "Ub": 1.0}
+    configs = {
+        "ldc_quick_double_lid": lambda n, B: [fine.problem(float(Re), n, n, 1.0, 1.0, 0.001, "QUICK", None, coarse.LDC_DOUBLE_LID)
+                                              for Re in np.linspace(100.0, 800.0, B)],
+        "bfs_upwind_re400": lambda n, B: [fine.problem(400.0, n, n, 10.0, 3.0, 0.002, "UPWIND", None, None, bfs=bfs) for _ in range(B)],
+    }
+    out = {"iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "unit": "ms per outer iteration of the batch", "resident": {}}
+    for name, make in configs.items():
+        out["resident"][name] = {}
+        for n in [int(m) for m in a.mesh.split(",")]:
+            if not fine.resident_supported(n, n):
+                out["resident"][name][f"{n}x{n}"] = {"supported": False}
+                continue
+            for B in [int(b) for b in (a.batch or "1").split(",")]:
+                pbs = make(n, B)
+                ms = {False: [], True: []}
+                sweeps = {}
+                for _ in range(a.repeats):
+                    for resident in (False, True):
+                        b = fine.FineSolverBatch(pbs, resident=resident)
+                        dt_s, c = _timed(b, a.warmup, a.iters)
+                        b.close()
+                        ms[resident].append(round(1e3 * dt_s / a.iters, 4))
+                        sweeps[resident] = c
+                row = {"launches_ms": ms[False], "resident_ms": ms[True],
+                       "launches_median": float(np.median(ms[False])), "launches_range": [min(ms[False]), max(ms[False])],
+                       "resident_median": float(np.median(ms[True])), "resident_range": [min(ms[True]), max(ms[True])],
+                       "resident_median_below_launches_range": bool(np.median(ms[True]) < min(ms[False])),
+                       "launches_over_resident": round(float(np.median(ms[False]) / np.median(ms[True])), 2),
+                       "pressure_sweeps": sweeps[True]["pressure_sweeps"], "momentum_sweeps": sweeps[True]["momentum_sweeps"],
+                       "resident_launches": sweeps[True]["launches"], "launch_mode_launches": sweeps[False]["launches"]}
+                out["resident"][name].setdefault(f"{n}x{n}", {})[str(B)] = row
+    if a.pinned:
+        out["pinned_10x10_re800_59765_iterations_s"] = {}
+        for resident in (False, True):
+            s = fine.FineSolver(fine.problem(800.0, 10, 10, bc=coarse.LDC_DOUBLE_LID, convergence_criteria={"u": 0.0, "v": 0.0, "p": 0.0}),
+                                resident=resident)
+            t0 = time.perf_counter()
+            s.run(59765)
+            out["pinned_10x10_re800_59765_iterations_s"]["resident" if resident else "launches"] = round(time.perf_counter() - t0, 3)
+            s.close()
     print(json.dumps(out))
 
 
@@ -150,11 +204,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--handoff", default=None, help="comma-separated batch sizes: time the SR hand-off, batched against single-case calls")
     ap.add_argument("--single-only", action="store_true", help="with --handoff: only the single-case calls")
+    ap.add_argument("--resident", action="store_true", help="time the resident mode against the launch mode on the meshes of --mesh")
+    ap.add_argument("--mesh", default="10,20,30,40,50,64", help="with --resident: comma-separated square mesh sizes")
+    ap.add_argument("--pinned", action="store_true", help="with --resident: also the 59 765-iteration 10x10 run in both modes")
     ap.add_argument("--golden", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"),
                     help="directory of the encoder, statistics and coarse-field files --handoff reads")
     a = ap.parse_args()
     fine = importlib.import_module("sr-for-cfd_amd.fine")
     coarse = importlib.import_module("sr-for-cfd_amd.coarse")
+    if a.resident:
+        return resident_bench(a, fine, coarse)
     if a.batch:
         return batch_bench(a, fine, coarse)
     if a.handoff:

@@ -3,6 +3,7 @@ batched across Reynolds numbers (datasets.generate_simulation_file).  Prints one
 
     python tools/generate_dataset.py simulation_result_double_lid.h5 [--reynolds 100,200,...] [--mesh-sizes 10,50,400]
         [--bc double_lid|single_lid] [--dt 0.001] [--scheme QUICK] [--tolerance 1e-6] [--max-iterations 100000] [--max-batch 8]
+        [--resident no|yes|auto]
 """
 import argparse
 import importlib
@@ -28,6 +29,9 @@ def main():
     ap.add_argument("--max-iterations", type=int, default=100000)
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--resident", choices=("no", "yes", "auto"), nargs="?", const="auto", default="no",
+                    help="resident mode for the small meshes (at most 64 x 64): 'yes' refuses larger ones, 'auto' (also the bare flag) "
+                         "runs them launch per sweep")
     a = ap.parse_args()
     datasets = importlib.import_module("sr-for-cfd_amd.datasets")
     coarse = importlib.import_module("sr-for-cfd_amd.coarse")
@@ -39,7 +43,8 @@ def main():
     record = datasets.generate_simulation_file(
         a.path, [int(r) for r in a.reynolds.split(",")], [int(n) for n in a.mesh_sizes.split(",")], bc=bc, bc_type=bc_type,
         case_name=case_name, dt=a.dt, scheme=a.scheme, convergence_criteria={c: a.tolerance for c in "uvp"},
-        max_iterations=a.max_iterations, max_batch=a.max_batch, device=a.device)
+        max_iterations=a.max_iterations, max_batch=a.max_batch, device=a.device,
+        resident={"no": False, "yes": True, "auto": "auto"}[a.resident])
     for Re, n, iterations, status in record:
         print(f"Re {Re} mesh {n}x{n}: {iterations} iterations, {STATUS[status]}")
     print(json.dumps({"path": a.path, "runs": len(record), "written": sum(s != 2 for *_, s in record), "seconds": round(time.time() - t0, 1)}))
