@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <functional>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -36,8 +37,8 @@ struct ProfEvent {
   std::string name;
 };
 
-struct FusedState;  // bf16/f16 path (fused_bf16.hip)
-struct Any16State;  // bf16/f16 path of the other family graphs (fused_bf16.hip, any16_forward)
+struct Lowp16State;  // bf16/f16 path of this handle's graph: the fused encoder_10 + decoder_400 kernels or any16 (fused_bf16.hip)
+void lowp16_free(Lowp16State* st);
 
 // Functional A/B switches: every one selects a COMPLETE alternative implementation of a stage (no work is skipped), for the parity
 // tests and the tools.  They are read from the environment once per srcfd_predict* call (Switches::from_env), are part of the hipGraph
@@ -70,7 +71,7 @@ struct Plan {
   int tail_seg = 0;   // 16-bit tail: segments per sample actually launched (last chunk)
   int graph = 0;      // 0 plain launches, 1 captured now and launched as a graph, 2 replay of an earlier capture
   bool fused = false;
-  bool any16 = false;  // the 16-bit forward was any16_forward (decoder=any16)
+  bool any16 = false;  // the 16-bit forward ran the any16 graph (decoder=any16)
 };
 
 struct Model {
@@ -122,9 +123,8 @@ struct Model {
   std::vector<ProfEvent> prof_events;
   size_t prof_used = 0;
 
-  FusedState* fused = nullptr;
-  Any16State* any16 = nullptr;   // non-null: the graph is eligible for any16_forward (host-only handles included)
-  bool lowp_ok() const { return has_fused || any16 != nullptr; }
+  std::unique_ptr<Lowp16State, void (*)(Lowp16State*)> lowp16{nullptr, lowp16_free};   // non-null: the graph runs in bf16 / f16 (host-only handles included)
+  bool lowp_ok() const { return lowp16 != nullptr; }
 
   // hipGraph replay of the fused 16-bit pipeline: a call whose arguments equal the previous call's is
   // captured once on a private stream and replayed afterwards (removes ~8 launch gaps per batch)
@@ -161,22 +161,15 @@ struct Model {
                    const std::function<int(const float* y_dev, int first, int count)>& sink = nullptr);
 };
 
-// bf16 / f16 fused path for the encoder_10 + decoder_400 graph.
-int fused_init(Model& m);
-void fused_free(Model& m);
-int fused_debug_read(Model& m, int index, void* dst, size_t bytes);
-int fused_reserve(Model& m, int n);
-int fused_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
-                  int flags, unsigned long long* nonfinite, hipStream_t s);
-
-// bf16 / f16 for encoder_10 + any decoder of supported layers that ends in a 3x3 C -> 1 convolution (operand_pack.h, Any16Pack)
-void any16_create(Model& m);   // host only: plans the graph; leaves m.any16 null when it is not eligible
-void any16_free(Model& m);
-int any16_init(Model& m);      // device side of a planned graph
-int any16_reserve(Model& m, int n);
-size_t any16_workspace_bytes(const Model& m, int n);
-int any16_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
-                  int flags, unsigned long long* nonfinite, hipStream_t s);
+// The bf16 / f16 path of a handle (fused_bf16.hip): the fused kernels of the encoder_10 + decoder_400 graph (Model::has_fused), or
+// encoder_10 + any decoder of supported layers that ends in a 3x3 C -> 1 convolution (operand_pack.h, Any16Pack).
+void lowp16_plan(Model& m);   // host only: plans the graph; leaves m.lowp16 null when no 16-bit path takes it
+int lowp16_init(Model& m);    // device side of a planned graph
+int lowp16_reserve(Model& m, int n);
+size_t lowp16_workspace_bytes(const Model& m, int n);   // what lowp16_reserve(n) allocates for activations and split-K slabs
+int lowp16_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
+                   int flags, unsigned long long* nonfinite, hipStream_t s);
+int fused_debug_read(Model& m, int index, void* dst, size_t bytes);   // the fused graph only
 
 // The prediction behind the hand-offs into a solver state (resample.hip): `write` takes the n_samples predicted [and
 // resampled] planes (ny, nx) on the device, float or double, on the default stream.

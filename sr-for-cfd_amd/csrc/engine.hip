@@ -112,11 +112,7 @@ static void plan_enc32(Model& m) {
 // model
 // ---------------------------------------------------------------------------
 Model::~Model() {
-  if (device >= 0) {
-    (void)hipSetDevice(device);   // for the members' destructors (device_mem.h)
-    fused_free(*this);
-  }
-  any16_free(*this);   // a host-only handle holds the plan only
+  if (device >= 0) (void)hipSetDevice(device);   // for the members' destructors (device_mem.h; lowp16's state is one of them)
 }
 
 Switches Switches::from_env() {
@@ -157,7 +153,7 @@ int Model::init_device() {
   return rc ? rc : d_pack_x3.upload(pack_x3);
 }
 
-// bf16 / f16 need 16-bit kernels for every layer: the fused encoder_10 + decoder_400 kernels, or any16_forward's layer loop
+// bf16 / f16 need 16-bit kernels for every layer: the fused encoder_10 + decoder_400 kernels, or any16's layer loop (fused_bf16.hip)
 static const char* const LOWP_REFUSAL =
     "bf16/f16 precision needs encoder_10 in front, Dense / 2x2 or 3x3 stride-2 Conv2DTranspose layers with input channels a multiple of 16 behind it and a "
     "3x3 'same' Conv2D to one channel at the end (the encoder_10+decoder_400 layer graph is one); use SRCFD_PREC_FP32 for other graphs";
@@ -409,7 +405,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   sw = Switches::from_env();
   const bool use_fused = (precision == SRCFD_PREC_BF16 || precision == SRCFD_PREC_F16);
   plan = Plan();
-  const bool use_any16 = use_fused && !has_fused && any16;
+  const bool use_any16 = use_fused && !has_fused && lowp16;
   plan.sw = sw; plan.precision = precision; plan.fused = use_fused && !use_any16; plan.any16 = use_any16;
   if (use_fused && !lowp_ok()) { set_error(LOWP_REFUSAL); return SRCFD_EINVAL; }
   if (!use_fused) {
@@ -421,8 +417,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   const size_t out_elems = (size_t)os[0] * os[1] * os[2];
   const size_t osz = out_dtype == SRCFD_F32 ? 4 : 2;
   auto run = [&](hipStream_t st) -> int {
-    if (use_any16) return any16_forward(*this, (const float*)x_dev, n, aff_in, aff_out, y_dev, out_dtype, flags, nonfinite, st);
-    if (use_fused) return fused_forward(*this, (const float*)x_dev, n, aff_in, aff_out, y_dev, out_dtype, flags, nonfinite, st);
+    if (use_fused) return lowp16_forward(*this, (const float*)x_dev, n, aff_in, aff_out, y_dev, out_dtype, flags, nonfinite, st);
     for (int i = 0; i < n; i += ws_chunk) {
       int c = std::min(ws_chunk, n - i);
       int rc = forward_generic((const float*)x_dev + (size_t)i * in_elems, c, aff_in ? aff_in + 2 * (size_t)i : nullptr,
@@ -574,15 +569,11 @@ static int finish_create(std::unique_ptr<Model>& m, srcfd_model** out) {
     return SRCFD_EINVAL;
   }
   m->has_fused = m->desc.is_sr_10_400();
-  if (!m->has_fused) any16_create(*m);   // host only: which other graphs run in bf16 / f16 (srcfd_model_supports_precision)
+  lowp16_plan(*m);   // host only: which graphs run in bf16 / f16 (srcfd_model_supports_precision)
   int rc = m->init_device();
   if (rc) return rc;
-  if (m->device >= 0 && m->has_fused) {
-    rc = fused_init(*m);
-    if (rc) return rc;
-  }
-  if (m->device >= 0 && m->any16) {
-    rc = any16_init(*m);
+  if (m->device >= 0 && m->lowp16) {
+    rc = lowp16_init(*m);
     if (rc) return rc;
   }
   *out = reinterpret_cast<srcfd_model*>(m.release());
@@ -785,7 +776,7 @@ int srcfd_model_reserve(srcfd_model* m, int n) {
     HIPCHECK(hipSetDevice(mm.device));
     if (mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) {
       if (!mm.lowp_ok()) { set_error(srcfd::LOWP_REFUSAL); return SRCFD_EINVAL; }
-      return mm.has_fused ? srcfd::fused_reserve(mm, n) : srcfd::any16_reserve(mm, n);
+      return srcfd::lowp16_reserve(mm, n);
     }
     return mm.ensure_workspace(n);
   });
@@ -816,9 +807,10 @@ int srcfd_model_workspace(srcfd_model* m, int n, size_t* bytes) {
   return srcfd::abi_guard("srcfd_model_workspace", [&]() -> int {
     if (!m) { set_error("null model"); return SRCFD_EINVAL; }
     const Model& mm = *M(m);
-    if ((mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) && !mm.has_fused && mm.any16) {   // any16_forward: chunks of up to 1024 samples
+    // the 16-bit path's chunks of up to 1024 samples; the fused graph answers with the f32 figures below, as it always has
+    if ((mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) && !mm.has_fused && mm.lowp16) {
       const int chunk16 = std::min(std::max(n, 1), 1024);
-      if (bytes) *bytes = srcfd::any16_workspace_bytes(mm, chunk16);
+      if (bytes) *bytes = srcfd::lowp16_workspace_bytes(mm, chunk16);
       return chunk16;
     }
     int chunk = std::min(std::max(n, 1), M(m)->chunk_cap());
@@ -839,12 +831,8 @@ int srcfd_model_footprint(const srcfd_model* m, int n, int precision, size_t byt
     const size_t in_elems = (size_t)shp_in[0] * shp_in[1] * shp_in[2], out_elems = (size_t)shp_out[0] * shp_out[1] * shp_out[2];
     size_t params = 0;
     for (const auto& L : mm.desc.layers) params += L.kernel.size() + L.bias.size();
-    if (lowp && !mm.has_fused) {
-      bytes[0] = srcfd::any16_workspace_bytes(mm, n);   // any16_reserve: two activation buffers + the dense split-K slabs
-      bytes[1] = params * (sizeof(float) + 2 * sizeof(uint16_t));
-    } else if (lowp) {
-      const size_t want = (size_t)std::min(n, 1024);
-      bytes[0] = want ? 2 * want * 160000 * sizeof(uint16_t) + 16 * want * 128 * sizeof(float) : 0;   // fused_reserve: two activation buffers + the dense split-K slabs
+    if (lowp) {
+      bytes[0] = srcfd::lowp16_workspace_bytes(mm, n);   // lowp16_reserve: two activation buffers + the dense split-K slabs
       bytes[1] = params * (sizeof(float) + 2 * sizeof(uint16_t));   // f32 weights + the 16-bit GEMM layout + fragment re-orderings (upper bound: every layer twice)
     } else {
       const int chunk = n ? std::min(n, mm.chunk_cap()) : 0;

@@ -347,11 +347,11 @@ static double scale_w(const ModelDesc& md, const std::vector<int>& cl, int i) {
   double si = scale_in(md, cl, i), so = scale_out(md, cl, i);
   return (si != 1.0 && so != 1.0) ? 1.0 : si * so;  // swish -> swish: the factors cancel exactly
 }
-// compute-layer ordinal of a GEMM op the 16-bit path takes (1..6: conv2d_1, dense, latent_vector, dense_1, conv2d_transpose, conv2d_transpose_1), else -1
-static int op16_layer(const std::vector<int>& cl, const Op& op) {
-  int ci = -1;
-  for (size_t k = 0; k < cl.size(); ++k) if (cl[k] == op.layer) ci = (int)k;
-  return ci < 1 || ci > 6 ? -1 : ci;
+static std::vector<int> compute_layers(const ModelDesc& md) {
+  std::vector<int> cl;
+  for (size_t i = 0; i < md.layers.size(); ++i)
+    if (md.layers[i].kind != SRCFD_LAYER_FLATTEN && md.layers[i].kind != SRCFD_LAYER_RESHAPE) cl.push_back((int)i);
+  return cl;
 }
 
 // A operands of v_mfma 32x32x16 (R = 32) / 16x16x32 (R = 16), one 16-byte load per lane, from W(row, k):
@@ -371,65 +371,66 @@ template <class F> static void acc_bias(float* out, int tiles, F b) {
       for (int r = 0; r < 16; ++r) out[(t * 2 + hh) * 16 + r] = b(32 * t + rowof(r, hh));
 }
 
-void pack_fused_f32(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs) {
-  for (size_t i = 0; i < md.layers.size(); ++i)
-    if (md.layers[i].kind != SRCFD_LAYER_FLATTEN && md.layers[i].kind != SRCFD_LAYER_RESHAPE) fs.cl.push_back((int)i);
+void plan16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, int last, bool narrow_ok, Plan16& P) {
+  P.cl = compute_layers(md);
   {  // conv1 (VALU kernel): f32 weights, scaled
-    const Layer& L = md.layers[fs.cl[0]];
-    double sw = scale_w(md, fs.cl, 0), so = scale_out(md, fs.cl, 0);
-    fs.c1w_off = fs.f32.size();
-    for (float v : L.kernel) fs.f32.push_back((float)(v * sw));
-    fs.c1b_off = fs.f32.size();
-    for (float v : L.bias) fs.f32.push_back((float)(v * so));
+    const Layer& L = md.layers[P.cl[0]];
+    const double sw = scale_w(md, P.cl, 0), so = scale_out(md, P.cl, 0);
+    P.c1w_off = P.f32.size();
+    for (float v : L.kernel) P.f32.push_back((float)(v * sw));
+    P.c1b_off = P.f32.size();
+    for (float v : L.bias) P.f32.push_back((float)(v * so));
   }
-  for (const Op& op : ops) {
-    const int ci = op16_layer(fs.cl, op);
-    if (ci < 0) continue;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    const Op& op = ops[i];
+    int ci = -1;
+    for (size_t k = 0; k < P.cl.size(); ++k) if (P.cl[k] == op.layer) ci = (int)k;
+    if (ci < 1 || ci > last) continue;
     Op16 o;
-    o.d = op.d;
-    o.name = op.name;
-    o.layer = ci;
-    if (ci == 3) { o.d.N = 64; o.d.CO = 64; o.d.OC = 64; }   // latent 50 -> 64 zero-padded channels
-    if (ci == 4) { o.d.CI = 64; o.d.K = 64; }                // dense_1 reads the padded latent
-    o.d.Npad = (o.d.N + 63) / 64 * 64;
-    o.Kpad = (o.d.K + 63) / 64 * 64;
-    const double so = scale_out(md, fs.cl, ci);
-    while (fs.f32.size() % 4) fs.f32.push_back(0.f);
-    o.b_off = fs.f32.size();
-    for (int n = 0; n < o.d.Npad; ++n) fs.f32.push_back(n < op.d.N ? (float)(pack[op.b_off + n] * so) : 0.f);
-    fs.ops.push_back(o);
+    o.d = op.d; o.name = op.name; o.layer = ci; o.src = (int)i;
+    if (ci == 3) { o.d.N = 64; o.d.CO = 64; o.d.OC = 64; }   // latent -> 64 zero-padded channels
+    if (ci == 4) { o.d.CI = 64; o.d.K = 64; }                // the dense layer behind it reads the padded latent
+    const bool narrow = narrow_ok && any16_narrow(o.d);
+    o.d.Npad = round_up(o.d.N, narrow ? 32 : 64);
+    o.Kpad = narrow ? o.d.K : round_up(o.d.K, 64);
+    const double so = scale_out(md, P.cl, ci);
+    while (P.f32.size() % 4) P.f32.push_back(0.f);
+    o.b_off = P.f32.size();
+    for (int n = 0; n < o.d.Npad; ++n) P.f32.push_back(n < op.d.N ? (float)(pack[op.b_off + n] * so) : 0.f);
+    P.ops.push_back(o);
   }
 }
 
-void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs, bool enc, bool f16, Pack16Host& P) {
-  // ---- GEMM weights, transposed: Wt[Npad][Kpad] ----
-  std::vector<uint16_t>& w = P.w;
-  size_t oi = 0;
-  for (const Op& op : ops) {
-    const int ci = op16_layer(fs.cl, op);
-    if (ci < 0) continue;
-    Op16& o = fs.ops[oi++];
-    const double sw = scale_w(md, fs.cl, ci);
+void pack_wt16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& P, bool f16, std::vector<uint16_t>& w) {
+  for (Op16& o : P.ops) {
+    const Op& op = ops[o.src];
+    const double sw = scale_w(md, P.cl, o.layer);
     while (w.size() % 8) w.push_back(0);
     o.w_off = w.size();
     w.resize(w.size() + (size_t)o.d.Npad * o.Kpad, 0);
     for (int n = 0; n < op.d.N; ++n)
-      for (int k = 0; k < op.d.K; ++k)
-        w[o.w_off + (size_t)n * o.Kpad + k] = to16((float)(pack[op.w_off + (size_t)k * op.d.Npad + n] * sw), f16);
+      for (int k = 0; k < op.d.K; ++k) w[o.w_off + (size_t)n * o.Kpad + k] = to16((float)(pack[op.w_off + (size_t)k * op.d.Npad + n] * sw), f16);
   }
-  if (enc) {
-    // ---- enc16 operands: the same 16-bit values, re-ordered so that one lane's MFMA A operand is one 16-byte load ----
-    const uint16_t* W2 = w.data() + fs.ops[0].w_off;   // [128][576]
-    const uint16_t* WD = w.data() + fs.ops[1].w_off;   // [128][3200]
-    const uint16_t* WL = w.data() + fs.ops[2].w_off;   // [64][128]
-    P.enc_wd_off = (size_t)4 * 36 * 1024; P.enc_wl_off = P.enc_wd_off + (size_t)8 * 100 * 1024;
-    P.encf.resize((size_t)(4 * 36 + 8 * 100 + 4 * 4) * 512);
-    a_frags(P.encf.data(), 32, 4, 36, [&](int r, int k) { return W2[(size_t)r * 576 + k]; });
-    a_frags(P.encf.data() + P.enc_wd_off / 2, 16, 8, 100, [&](int r, int k) { return WD[(size_t)r * 3200 + k]; });
-    a_frags(P.encf.data() + P.enc_wl_off / 2, 16, 4, 4, [&](int r, int k) { return WL[(size_t)r * 128 + k]; });
-    P.encb.resize(128);
-    acc_bias(P.encb.data(), 4, [&](int row) { return fs.f32[fs.ops[0].b_off + row]; });
-  }
+}
+
+// the same 16-bit values as Wt, re-ordered so that one lane's MFMA A operand is one 16-byte load
+void pack_enc16(const Plan16& P, const std::vector<uint16_t>& w, Enc16Host& E) {
+  const uint16_t* W2 = w.data() + P.ops[0].w_off;   // [128][576]
+  const uint16_t* WD = w.data() + P.ops[1].w_off;   // [128][3200]
+  const uint16_t* WL = w.data() + P.ops[2].w_off;   // [64][128]
+  E.enc_wd_off = (size_t)4 * 36 * 1024; E.enc_wl_off = E.enc_wd_off + (size_t)8 * 100 * 1024;
+  E.encf.resize((size_t)(4 * 36 + 8 * 100 + 4 * 4) * 512);
+  a_frags(E.encf.data(), 32, 4, 36, [&](int r, int k) { return W2[(size_t)r * 576 + k]; });
+  a_frags(E.encf.data() + E.enc_wd_off / 2, 16, 8, 100, [&](int r, int k) { return WD[(size_t)r * 3200 + k]; });
+  a_frags(E.encf.data() + E.enc_wl_off / 2, 16, 4, 4, [&](int r, int k) { return WL[(size_t)r * 128 + k]; });
+  E.encb.resize(128);
+  acc_bias(E.encb.data(), 4, [&](int row) { return P.f32[P.ops[0].b_off + row]; });
+}
+
+void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& fs, bool enc, bool f16, Pack16Host& P) {
+  std::vector<uint16_t>& w = P.w;
+  pack_wt16(md, ops, pack, fs, f16, w);
+  if (enc) pack_enc16(fs, w, P);
 
   // ---- tail constants ----
   const Layer& L2 = md.layers[fs.cl[7]];   // ConvT 64->32, kernel (2,2,32,64)
@@ -505,14 +506,14 @@ static float from16(uint16_t v, bool f16) {
   return f;
 }
 
-void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A) {
+void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& P, Any16Pack& A) {
+  P = Plan16();
   A = Any16Pack();
-  auto no = [&](const std::string& w) { A.why = w; };
-  for (size_t i = 0; i < md.layers.size(); ++i)
-    if (md.layers[i].kind != SRCFD_LAYER_FLATTEN && md.layers[i].kind != SRCFD_LAYER_RESHAPE) A.cl.push_back((int)i);
-  const int n = (int)A.cl.size();
+  auto no = [&](const std::string& w) { P = Plan16(); A = Any16Pack(); A.why = w; };   // a refused graph has no plan
+  const std::vector<int> cl = compute_layers(md);
+  const int n = (int)cl.size();
   if (n < 6) return no("fewer layers than encoder_10 + a dense layer + an output convolution");
-  auto L = [&](int i) -> const Layer& { return md.layers[A.cl[i]]; };
+  auto L = [&](int i) -> const Layer& { return md.layers[cl[i]]; };
   auto act_ok = [](int a) { return a == SRCFD_ACT_SWISH || a == SRCFD_ACT_LINEAR; };
   // 1. the first four compute layers are encoder_10's (enc16 is written for exactly these)
   if (md.in_shape[0] != 10 || md.in_shape[1] != 10 || md.in_shape[2] != 1) return no("input is not (10, 10, 1)");
@@ -540,69 +541,23 @@ void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vect
     } else return no("layer '" + l.name + "': no 16-bit kernel for this layer kind");
   }
   if (L(4).kind != SRCFD_LAYER_DENSE) return no("the layer behind latent_vector is not Dense");
-  // conv1 (VALU kernel): f32 weights, scaled
-  {
-    const double sw = scale_w(md, A.cl, 0), so = scale_out(md, A.cl, 0);
-    A.c1w_off = A.f32.size();
-    for (float v : c1.kernel) A.f32.push_back((float)(v * sw));
-    A.c1b_off = A.f32.size();
-    for (float v : c1.bias) A.f32.push_back((float)(v * so));
-  }
+  plan16(md, ops, pack, n - 2, true, P);
   A.max_act = 3200;   // conv2d_1's output when the encoder runs layer by layer
-  for (const Op& op : ops) {
-    int ci = -1;
-    for (int k = 0; k < n; ++k) if (A.cl[k] == op.layer) ci = k;
-    if (ci < 1 || ci >= n - 1) continue;
-    Op16 o;
-    o.d = op.d; o.name = op.name; o.layer = ci;
-    if (ci == 3) { o.d.N = 64; o.d.CO = 64; o.d.OC = 64; }   // latent -> 64 zero-padded channels
-    if (ci == 4) { o.d.CI = 64; o.d.K = 64; }                // the dense layer behind it reads the padded latent
-    const bool narrow = any16_narrow(o.d);
-    o.d.Npad = round_up(o.d.N, narrow ? 32 : 64);
-    o.Kpad = narrow ? o.d.K : round_up(o.d.K, 64);
-    if (o.d.K <= 0 || o.d.N % 4 != 0 || o.d.CO % 4 != 0 || o.d.OC % 4 != 0 || o.d.CI % 16 != 0 || (!narrow && o.d.K % 64 != 0)) {
-      A.ops.clear();
-      return no("layer '" + md.layers[op.layer].name + "': GEMM shape");
-    }
-    const double so = scale_out(md, A.cl, ci);
-    while (A.f32.size() % 4) A.f32.push_back(0.f);
-    o.b_off = A.f32.size();
-    for (int q = 0; q < o.d.Npad; ++q) A.f32.push_back(q < op.d.N ? (float)(pack[op.b_off + q] * so) : 0.f);
-    A.ops.push_back(o);
-    const Layer& l = md.layers[op.layer];
-    A.max_act = std::max(A.max_act, (size_t)l.out_shape[0] * l.out_shape[1] * (ci == 3 ? 64 : l.out_shape[2]));
+  for (const Op16& o : P.ops) {
+    const Layer& l = md.layers[cl[o.layer]];
+    if (o.d.K <= 0 || o.d.N % 4 != 0 || o.d.CO % 4 != 0 || o.d.OC % 4 != 0 || o.d.CI % 16 != 0 || (!any16_narrow(o.d) && o.d.K % 64 != 0))
+      return no("layer '" + l.name + "': GEMM shape");
+    A.max_act = std::max(A.max_act, (size_t)l.out_shape[0] * l.out_shape[1] * (o.layer == 3 ? 64 : l.out_shape[2]));
   }
-  if (A.ops.size() < 4 || A.ops[0].layer != 1 || A.ops[1].layer != 2 || A.ops[2].layer != 3) { A.ops.clear(); return no("unexpected plan shape"); }
+  if (P.ops.size() < 4 || P.ops[0].layer != 1 || P.ops[1].layer != 2 || P.ops[2].layer != 3) return no("unexpected plan shape");
   A.out_C = lo.cin; A.out_H = lo.in_shape[0]; A.out_W = lo.in_shape[1]; A.out_bias = lo.bias[0];
   A.ok = true;
 }
 
-void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A, bool f16, Any16Host& P) {
+void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& A, bool f16, Any16Host& P) {
   const int n = (int)A.cl.size();
-  size_t oi = 0;
-  for (const Op& op : ops) {
-    int ci = -1;
-    for (int k = 0; k < n; ++k) if (A.cl[k] == op.layer) ci = k;
-    if (ci < 1 || ci >= n - 1) continue;
-    Op16& o = A.ops[oi++];
-    const double sw = scale_w(md, A.cl, ci);
-    while (P.w.size() % 8) P.w.push_back(0);
-    o.w_off = P.w.size();
-    P.w.resize(P.w.size() + (size_t)o.d.Npad * o.Kpad, 0);
-    for (int q = 0; q < op.d.N; ++q)
-      for (int k = 0; k < op.d.K; ++k) P.w[o.w_off + (size_t)q * o.Kpad + k] = to16((float)(pack[op.w_off + (size_t)k * op.d.Npad + q] * sw), f16);
-  }
-  // enc16 operands: as pack_fused16
-  const uint16_t* W2 = P.w.data() + A.ops[0].w_off;   // [128][576]
-  const uint16_t* WD = P.w.data() + A.ops[1].w_off;   // [128][3200]
-  const uint16_t* WL = P.w.data() + A.ops[2].w_off;   // [64][128]
-  P.enc_wd_off = (size_t)4 * 36 * 1024; P.enc_wl_off = P.enc_wd_off + (size_t)8 * 100 * 1024;
-  P.encf.resize((size_t)(4 * 36 + 8 * 100 + 4 * 4) * 512);
-  a_frags(P.encf.data(), 32, 4, 36, [&](int r, int k) { return W2[(size_t)r * 576 + k]; });
-  a_frags(P.encf.data() + P.enc_wd_off / 2, 16, 8, 100, [&](int r, int k) { return WD[(size_t)r * 3200 + k]; });
-  a_frags(P.encf.data() + P.enc_wl_off / 2, 16, 4, 4, [&](int r, int k) { return WL[(size_t)r * 128 + k]; });
-  P.encb.resize(128);
-  acc_bias(P.encb.data(), 4, [&](int row) { return A.f32[A.ops[0].b_off + row]; });
+  pack_wt16(md, ops, pack, A, f16, P.w);
+  pack_enc16(A, P.w, P);
   // output convolution: Keras kernel (3, 3, C, 1) = (ty, tx, ci)
   const Layer& lo = md.layers[A.cl[n - 1]];
   const double si = scale_in(md, A.cl, n - 1);

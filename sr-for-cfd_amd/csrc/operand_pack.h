@@ -1,8 +1,8 @@
 // Host-side operand packing: every layout a kernel reads its weights in, as pure functions from the layer graph to host vectors
 // and offsets.  These layouts are the contract between host and kernel.  No HIP runtime calls in this unit: engine.hip (plan_*),
-// fused_bf16.hip (fused_init, build_pack), train_tail.hip (train_tail_plan) and train.hip (trainer_build) decide what qualifies and
-// upload what these functions return; tools/pack_digest.cpp links the same functions on a CPU and tests/test_operand_pack.py pins
-// their bytes.
+// fused_bf16.hip (lowp16_plan, build_pack: both 16-bit graphs through plan16 / pack_wt16 / pack_enc16), train_tail.hip
+// (train_tail_plan) and train.hip (trainer_build) decide what qualifies and upload what these functions return;
+// tools/pack_digest.cpp links the same functions on a CPU and tests/test_operand_pack.py pins their bytes.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -55,55 +55,62 @@ Tail32Pack tail32_slots(std::vector<Slot>& s);
 // map / scale / offsets of TrainTailPlan for a tail whose first parameter has flat index param_off
 void train_tail_slots(size_t param_off, TrainTailPlan& plan);
 
-// ---- bf16 / f16 path (fused_bf16.hip) ----
+// ---- bf16 / f16 path (fused_bf16.hip): two graphs, one front end ----
+// fused: encoder_10 + decoder_400 (enc16 -> dense1_16 -> mid16 -> tail16).  any16: encoder_10 + the other family decoders
+// (enc16 -> per layer gemm16, or the narrow-channel GEMM of kernels_any16.hip for CI 16 / 32 -> outconv16).  Both store swish
+// outputs scaled by log2e and fold 1 / log2e into the consumer's weights; both share plan16 / pack_wt16 / pack_enc16 below.
 struct Op16 {
   GemmDesc d;
-  size_t w_off = 0, b_off = 0;  // elements into Pack16Host::w, floats into Fused32Pack::f32
-  int Kpad = 0, layer = 0;
+  size_t w_off = 0, b_off = 0;  // elements into the Wt vector of pack_wt16, floats into Plan16::f32
+  int Kpad = 0;                 // row pitch of Wt
+  int layer = 0, src = 0;       // compute-layer ordinal; index of the f32 op it was made from
   std::string name;
 };
-struct Fused32Pack {
-  std::vector<int> cl;  // indices of the 11 compute layers in ModelDesc::layers
-  std::vector<Op16> ops;
-  std::vector<float> f32;  // conv1 weights [9][64], conv1 bias [64], per-op biases
+struct Plan16 {             // what both graphs plan once, for both operand types (plan16)
+  std::vector<int> cl;      // indices of the compute layers in ModelDesc::layers
+  std::vector<Op16> ops;    // GEMM ops of compute layers 1 .. last
+  std::vector<float> f32;   // conv1 weights [9][64] + bias [64] (scaled), per-op biases [Npad] (scaled)
   size_t c1w_off = 0, c1b_off = 0;
 };
-void pack_fused_f32(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs);
-struct Pack16Host {  // one per operand type (bf16, f16); the device copies are fused_bf16.hip's Pack16
-  std::vector<uint16_t> w;                    // GEMM weights, transposed: Wt[Npad][Kpad] per op
-  std::vector<uint16_t> encf, w2f, w0t, w1f;  // enc16 fragments (one blob); tail ConvT#2; mid16 ConvT#0 LDS images per phase, ConvT#1
-  size_t enc_wd_off = 0, enc_wl_off = 0;      // byte offsets of the dense / latent fragments in encf
-  size_t w0t_off[4] = {0, 0, 0, 0};
-  std::vector<uint8_t> consts;                // tail constants (kernels16.h, TC_OFF_*)
-  std::vector<float> encb, midb;              // enc16 conv2d_1 bias fragments [128]; mid16 bias fragments b0f [128] | b1f [64]
+struct Enc16Host {          // enc16's operands of one type (pack_enc16)
+  std::vector<uint16_t> encf;               // conv2d_1, dense, latent_vector fragments (one blob)
+  size_t enc_wd_off = 0, enc_wl_off = 0;    // byte offsets of the dense / latent fragments in encf
+  std::vector<float> encb;                  // conv2d_1 bias fragments [128]
 };
-// sets fs.ops[].w_off; the enc16 fragments only when `enc` (FusedState::enc_ok)
-void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Fused32Pack& fs, bool enc, bool f16, Pack16Host& P);
+// cl, the scaled conv1 and the Op16 list of compute layers 1 .. last: latent padded to 64 channels, biases scaled and 4-float
+// aligned, Npad / Kpad = multiples of 64, or 32 / K for a narrow op (any16_narrow) where `narrow_ok`
+void plan16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, int last, bool narrow_ok, Plan16& P);
+// GEMM weights of every op, transposed and scaled: Wt[Npad][Kpad], 8-element aligned; sets P.ops[].w_off (the same for both types)
+void pack_wt16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& P, bool f16, std::vector<uint16_t>& w);
+// ops 0..2 of w (conv2d_1, dense, latent_vector) in MFMA fragment order + conv2d_1's bias as accumulator init
+void pack_enc16(const Plan16& P, const std::vector<uint16_t>& w, Enc16Host& E);
+inline bool any16_narrow(const GemmDesc& d) { return d.CI % 64 != 0; }
 
-// ---- bf16 / f16 path of the other family graphs (fused_bf16.hip, any16_forward) ----
-// encoder_10 (enc16) -> per layer gemm16 (CI % 64 == 0) or the narrow-channel GEMM (CI 16 / 32, kernels_any16.hip) -> outconv16.
-// Same log2(e) folding as the fused path: swish outputs are stored scaled by log2e, consumers fold 1 / log2e into their weights.
-struct Any16Pack {
-  bool ok = false;           // the graph is eligible (any16_plan); `why` says what is not
+// the fused graph (plan16 with last = 6, no narrow ops), one per operand type; the device copies are fused_bf16.hip's Dev16 (w and
+// the enc16 part) and FusedState::Dev (the rest)
+struct Pack16Host : Enc16Host {
+  std::vector<uint16_t> w;              // pack_wt16
+  std::vector<uint16_t> w2f, w0t, w1f;  // tail ConvT#2; mid16 ConvT#0 LDS images per phase, ConvT#1
+  size_t w0t_off[4] = {0, 0, 0, 0};
+  std::vector<uint8_t> consts;          // tail constants (kernels16.h, TC_OFF_*)
+  std::vector<float> midb;              // mid16 bias fragments b0f [128] | b1f [64]
+};
+// the enc16 fragments only when `enc` (FusedState::enc_ok)
+void pack_fused16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& fs, bool enc, bool f16, Pack16Host& P);
+
+struct Any16Pack {           // what any16_plan finds besides the Plan16
+  bool ok = false;           // the graph is eligible; `why` says what is not (the Plan16 is then empty)
   std::string why;
-  std::vector<int> cl;       // indices of the compute layers in ModelDesc::layers
-  std::vector<Op16> ops;     // GEMM ops of compute layers 1 .. last - 1 (Op16::layer = compute-layer ordinal); Kpad: row pitch of Wt
-  std::vector<float> f32;    // conv1 weights [9][64] + bias [64] (scaled), per-op biases [Npad] (scaled)
-  size_t c1w_off = 0, c1b_off = 0;
   int out_C = 0, out_H = 0, out_W = 0;   // the output convolution: 3x3 SAME, C -> 1
   float out_bias = 0.f;
   size_t max_act = 0;        // largest 16-bit activation per sample, elements
 };
-struct Any16Host {           // one per operand type
-  std::vector<uint16_t> w;       // Wt[Npad][Kpad] per op
-  std::vector<uint16_t> encf;    // enc16 fragments, as Pack16Host
-  size_t enc_wd_off = 0, enc_wl_off = 0;
-  std::vector<float> encb;
+struct Any16Host : Enc16Host {   // one per operand type
+  std::vector<uint16_t> w;       // pack_wt16
   std::vector<float> wout;       // output convolution (ty, tx, ci): the 16-bit-rounded weights (x 1 / log2e behind a swish) as f32
 };
-inline bool any16_narrow(const GemmDesc& d) { return d.CI % 64 != 0; }
-void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A);
-void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Any16Pack& A, bool f16, Any16Host& P);   // sets A.ops[].w_off
+void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& P, Any16Pack& A);
+void pack_any16(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack, Plan16& A, bool f16, Any16Host& P);
 
 // ---- trainer (train.hip) ----
 // a compute layer: its index in ModelDesc::layers, elements per sample, flat parameter offsets

@@ -209,7 +209,7 @@ def test_keras_surface_runs_a_family_decoder_file(srcfd, enc_weights, fields, tm
 
 
 # ---------------------------------------------------------------------------
-# the same five models in bf16 and f16 (any16_forward: enc16 -> gemm16 / gemm16n per layer -> outconv16)
+# the same five models in bf16 and f16 (any16: enc16 -> gemm16 / gemm16n per layer -> outconv16)
 # ---------------------------------------------------------------------------
 _EMU = {}
 

@@ -102,11 +102,11 @@ static void f32_sections(const std::string& tag, const ModelDesc& md, std::vecto
   if (w2x >= 0) section(tag + "pack_x3.t32_w2x", px.data() + w2x, 6144, (size_t)w2x);
 }
 
-// fused_init() + build_pack() of fused_bf16.hip for both operand types
+// lowp16_plan() + build_pack() of fused_bf16.hip for the fused graph, both operand types
 static void fused_sections(const ModelDesc& md, const std::vector<Op>& ops, const std::vector<float>& pack) {
-  Fused32Pack fs;
-  pack_fused_f32(md, ops, pack, fs);
-  const bool enc_ok = true;   // encoder_10: fused_init's shape test
+  Plan16 fs;
+  plan16(md, ops, pack, 6, false, fs);   // compute layers 1..6: conv2d_1 .. conv2d_transpose_1
+  const bool enc_ok = true;   // encoder_10: fused_init's shape test (fused_bf16.hip)
   whole("fused.f32", fs.f32);
   std::vector<int64_t> bo;
   for (const Op16& o : fs.ops) bo.push_back((int64_t)o.b_off);
@@ -182,22 +182,23 @@ static void family_sections(const ModelDesc& md) {
   std::vector<int64_t> geo;   // per op: the row grid and the origins a cropped ('same') transposed convolution moves
   for (const Op& o : ops) for (int v : {o.layer, o.d.MH, o.d.MW, o.d.TY, o.d.TX, o.d.cy, o.d.cx, o.d.oy0, o.d.ox0, o.d.os, o.d.K, o.d.N}) geo.push_back(v);
   ints("family.ops_geometry", geo);
-  {  // the 16-bit path of the family graphs: any16_create() + any16_build_pack() of fused_bf16.hip for both operand types
+  {  // the 16-bit path of the family graphs: lowp16_plan() + build_pack() of fused_bf16.hip for both operand types
+    Plan16 P16;
     Any16Pack A;
-    any16_plan(md, ops, pack, A);
-    ints("family.any16.plan", {(int64_t)A.ok, (int64_t)A.ops.size(), A.out_C, A.out_H, A.out_W, (int64_t)A.max_act, (int64_t)A.c1w_off, (int64_t)A.c1b_off});
+    any16_plan(md, ops, pack, P16, A);
+    ints("family.any16.plan", {(int64_t)A.ok, (int64_t)P16.ops.size(), A.out_C, A.out_H, A.out_W, (int64_t)A.max_act, (int64_t)P16.c1w_off, (int64_t)P16.c1b_off});
     if (A.ok) {
-      whole("family.any16.f32", A.f32);
+      whole("family.any16.f32", P16.f32);
       for (int f16 = 0; f16 < 2; ++f16) {
         const std::string px = f16 ? "family.any16.f16." : "family.any16.bf16.";
         Any16Host P;
-        pack_any16(md, ops, pack, A, f16 != 0, P);
+        pack_any16(md, ops, pack, P16, f16 != 0, P);
         whole(px + "Wt", P.w);
         whole(px + "encf", P.encf);
         whole(px + "encb", P.encb);
         whole(px + "wout", P.wout, true);
         std::vector<int64_t> wo;
-        for (const Op16& o : A.ops) { wo.push_back((int64_t)o.w_off); wo.push_back(o.Kpad); wo.push_back(o.d.Npad); wo.push_back(any16_narrow(o.d)); }
+        for (const Op16& o : P16.ops) { wo.push_back((int64_t)o.w_off); wo.push_back(o.Kpad); wo.push_back(o.d.Npad); wo.push_back(any16_narrow(o.d)); }
         ints(px + "w_off", wo);
       }
     }
