@@ -355,21 +355,23 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   // simply drains what the older waves leave): SIMD 0,1 get 4 BC + 2 A + 2 D, SIMD 2,3 get 3 BC + 2 A + 6 D.
   //   A : waves 0-7, item = wave; weights resident, activations prefetched one round ahead
   //   BC: waves 0,1,4,5,8,9,12,13 -> items 0-7; waves 2,3,6,7,10,11 -> items 8-13
-  //   D : waves 8,9,12,13 and 2,3,6,7 -> one item each (0-7); waves 10,11,14,15 -> two each (8-15)
-  const bool hasA = wave < 8;
+  //   D : waves 8,9,12,13 -> one item each (0-3); waves 10,11 -> two each (8-11); waves 14,15 -> four each (12-15 and 4-7)
+  // Two wave roles, each with a round loop of its own (`rounds`, below): P = waves 0-7 (BC + A, no D state), Q = waves 8-15
+  // (D + BC, no ConvT#2 operands).  ConvT#2's resident weights and prefetched input (32 registers) and D's lane constants are
+  // then live only in the role that uses them, which is what leaves room for two interleaved D chains in role Q.
   const int a_mt = wave & 3, a_ct = (wave >> 2) & 1;
   const int sq = wave >> 2, sl = wave & 3;       // wave = 4 * sq + sl, SIMD = sl
-  int bc_item = -1, d_first = 0, d_cnt = 0;
+  int bc_item = -1, d_first = 0, d_cnt = 0, d_second = 0;   // D items d_first .. + min(d_cnt, 2) - 1, and d_second, d_second + 1 when d_cnt == 4
   if (sl < 2) {                                   // SIMD 0,1
     bc_item = 2 * sq + sl;                        // 0..7
     if (sq >= 2) { d_first = 2 * (sq - 2) + sl; d_cnt = 1; }        // waves 8,9,12,13 -> 0..3
   } else {                                        // SIMD 2,3
     if (sq < 3) bc_item = 8 + 2 * sq + (sl - 2);  // waves 2,3,6,7,10,11 -> 8..13
-    if (sq < 2) { d_first = 4 + 2 * sq + (sl - 2); d_cnt = 1; }      // waves 2,3,6,7 -> 4..7
-    else { d_first = 8 + 4 * (sq - 2) + 2 * (sl - 2); d_cnt = 2; }   // waves 10,11,14,15 -> 8..15
+    if (sq >= 2) { d_first = 8 + 4 * (sq - 2) + 2 * (sl - 2); d_cnt = 2; }   // waves 10,11,14,15 -> 8..15
+    if (sq == 3) { d_second = 4 + 2 * (sl - 2); d_cnt = 4; }                 // waves 14,15 -> also 4..7 (same tiles, row pair 1 instead of 3)
   }
 
-  int d_b0[2], d_b1[2];   // per D item of this wave: within-row byte offsets of window column pair 0 (pair 4 = + 16) and 1 (pairs 2, 3 = + 2, 4 planes)
+  int d_b0[2], d_b1[2];   // per D item of a pair of this wave: within-row byte offsets of window column pair 0 (pair 4 = + 16) and 1 (pairs 2, 3 = + 2, 4 planes); (d_second + i) & 3 == (d_first + i) & 3
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     int tx = 16 * ((d_first + i) & 3) + d_tsel;
@@ -392,13 +394,6 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   const int a_pxc = a_valid ? a_px : 49;
   const unsigned a_lane = (unsigned)(a_pxc * 64 + 8 * h);                       // element offset of this lane's 16-byte pieces inside a 50-level row
   const int a_dst = l100_off(a_mt >> 1, 2 * (a_valid ? a_px : 0) + (a_mt & 1), 0) + 8 * h;   // L100 granule of chunk 0; chunk q is q * 212 granules further
-  uint4 wa[4], xb[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) { wa[kk] = make_uint4(0, 0, 0, 0); xb[kk] = make_uint4(0, 0, 0, 0); }
-  if (hasA) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) wa[kk] = w2_f[(a_mt * 4 + kk) * 64 + lane];
-  }
 
   const bool ab_sw = TAIL_ABL(1);
   // This workgroup's samples k = 0..K-1 (ids blockIdx.x + k*gridDim.x) are treated as one tall image of
@@ -422,7 +417,22 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
     sidx = S > 1 ? seg * L + sl - 1 : sl;
     seg_out = seg; sl_out = sl;
   };
-  if (hasA && K > 0) {
+  float o_mean = 0.f, o_std = 1.f, o_mean_prev = 0.f, o_std_prev = 1.f;  // de-standardisation of D's sample / the one before
+  unsigned bad_count = 0;
+
+  unsigned long long tD = 0, tBC = 0, tA = 0, tBar = 0, tStart = 0, ts[6];
+  if (PROF) tStart = __builtin_amdgcn_s_memtime();
+  // The round loop, instantiated once per wave role (ROLE 0 = P: BC -> A; ROLE 1 = Q: D -> BC).  Every wave of the workgroup runs
+  // exactly `last + 1` rounds with one lds_barrier() each, whichever instantiation it is in: the bound is computed once, in front
+  // of the (wave-uniform) role branch, and nothing inside a round leaves it early.
+  auto rounds = [&](auto role, const int last) {
+  constexpr bool ROLE_P = decltype(role)::value == 0, ROLE_Q = !ROLE_P;
+  uint4 wa[4], xb[4];   // role P only: ConvT#2's weights, resident, and the input of the next strip
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) { wa[kk] = make_uint4(0, 0, 0, 0); xb[kk] = make_uint4(0, 0, 0, 0); }
+  if (ROLE_P) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) wa[kk] = w2_f[(a_mt * 4 + kk) * 64 + lane];
     int smp0, s0, sg0, sl0;
     strip_of(0, smp0, s0, sg0, sl0);
     if (s0 >= 0) {
@@ -431,24 +441,16 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       for (int kk = 0; kk < 4; ++kk) xb[kk] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4nt*>(src + 16 * kk)));
     }
   }
-  float o_mean = 0.f, o_std = 1.f, o_mean_prev = 0.f, o_std_prev = 1.f;  // de-standardisation of D's sample / the one before
-  unsigned bad_count = 0;
-
-  unsigned long long tD = 0, tBC = 0, tA = 0, tBar = 0, tStart = 0, ts[6];
-  if (PROF) tStart = __builtin_amdgcn_s_memtime();
-  for (int r = 0; r <= G + 2 && K > 0; ++r) {
+#pragma nounroll   // also keeps hipcc from peeling round 0: one loop and one s_barrier per role in the listing
+  for (int r = 0; r <= last; ++r) {
     // ---------------- A: ConvT#2 for strip g = r (input prefetched last round), then prefetch g+1 ----------------
-    // Runs BEFORE this wave's D items (waves 0-7: BC -> A -> D).  vmcnt is one in-order counter for loads and stores: waiting
-    // for the prefetched input right after D's global stores (the old order BC -> D -> A) made the wave sit out the completion
-    // of stores it had issued a few hundred cycles earlier, at the end of every round, in front of the barrier.  With A first
-    // the youngest operations ahead of the wait are last round's stores -- long done -- and this round's stores have until
-    // the next round's A.
-    unsigned long long a_span = 0;   // diagnostic build: cycles of this round's A stage (it runs inside the D section for waves 0-7)
+    // Role P runs it after its BC item.  (vmcnt is one in-order counter for loads and stores: a wave that waits for the prefetched
+    // input right after D's global stores sits out the completion of those stores in front of the barrier; with the roles split,
+    // no wave has both.)
     auto run_a = [&]() {
-      const unsigned long long a_t0 = PROF ? __builtin_amdgcn_s_memtime() : 0;
       int a_smp = 0, a_s = -1, a_sg = 0, a_sl = 0;
       if (r < G) strip_of(r, a_smp, a_s, a_sg, a_sl);
-      if (hasA && r < G && !TAIL_ABL(4)) {
+      if (r < G && !TAIL_ABL(4)) {
         int n_smp = 0, n_s = -1, n_sg = 0, n_sl = 0;
         if (r + 1 < G) strip_of(r + 1, n_smp, n_s, n_sg, n_sl);
         if (a_s < 0) {        // warm-up strip above the image: nothing to compute, only fetch the next strip's input
@@ -475,7 +477,6 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
         }
         }
       }
-      if (PROF) a_span = __builtin_amdgcn_s_memtime() - a_t0;
     };
     // ---------------- BC: ConvT#3 + ConvT#4 on 32 pixels of the 100-level ----------------
     auto do_bc = [&]() {
@@ -547,7 +548,7 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       prev_smp = pv / S;
       prev_ends = pv - prev_smp * S == S - 1;
     }
-    if (d_on && sd == 0 && p.aff_out) {  // entering a virtual sample: rotate the de-standardisation scalars (SGPRs)
+    if (ROLE_Q && d_on && sd == 0 && p.aff_out) {  // entering a virtual sample: rotate the de-standardisation scalars (SGPRs)
       o_mean_prev = o_mean; o_std_prev = o_std;
       if (gd < G) {
         o_mean = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.aff_out[2 * sample_d])));
@@ -558,21 +559,27 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
     const bool d_top = !d_warm && s_d == 0;              // first strip of a real sample: row pair 0 = (nothing | row 0)
     {
       // fast path: row pair rp of strip gd, all four window rows inside one sample
-      auto d_fast = [&](const int it, const int rowoff0, const int rowoff1) {
-        const int item = d_first + it, rp = item >> 2, j4 = item & 3;
-        if (TAIL_ABL(64) && j4 == 3) return;   // diagnostic: what the 2-of-16-tile items at the end of every row pair cost
-        f32x4 acc = {conv_bias, conv_bias, conv_bias, conv_bias};
+      // NI = 1: item `item0`; NI = 2: items item0 and item0 + 1 (same row pair) as two independent accumulator chains, interleaved:
+      // each keeps its own ten-MFMA k order, and the Toeplitz fragments -- the same for every item -- are read once for the pair
+      auto d_fast = [&](auto ni, const int item0, const int rowoff0, const int rowoff1) {
+        constexpr int NI = decltype(ni)::value;
+        f32x4 accs[NI];
+#pragma unroll
+        for (int it = 0; it < NI; ++it) accs[it] = f32x4{conv_bias, conv_bias, conv_bias, conv_bias};
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           const int rb = half ? rowoff1 : rowoff0;
-          const char* p0 = smem + rb + d_b0[it];
-          const char* p1 = smem + rb + d_b1[it];
-          uint4 av[5], wv[5];
-          av[0] = *reinterpret_cast<const uint4*>(p0);
-          av[4] = *reinterpret_cast<const uint4*>(p0 + 16);
-          av[1] = *reinterpret_cast<const uint4*>(p1);
-          av[2] = *reinterpret_cast<const uint4*>(p1 + 2 * T_PLANE * 16);
-          av[3] = *reinterpret_cast<const uint4*>(p1 + 4 * T_PLANE * 16);
+          uint4 av[NI][5], wv[5];
+#pragma unroll
+          for (int it = 0; it < NI; ++it) {
+            const char* p0 = smem + rb + d_b0[it];
+            const char* p1 = smem + rb + d_b1[it];
+            av[it][0] = *reinterpret_cast<const uint4*>(p0);
+            av[it][4] = *reinterpret_cast<const uint4*>(p0 + 16);
+            av[it][1] = *reinterpret_cast<const uint4*>(p1);
+            av[it][2] = *reinterpret_cast<const uint4*>(p1 + 2 * T_PLANE * 16);
+            av[it][3] = *reinterpret_cast<const uint4*>(p1 + 4 * T_PLANE * 16);
+          }
 #pragma unroll
           for (int cp = 0; cp < 5; ++cp) wv[cp] = wc_f[(half * 5 + cp) * 64 + lane];
           // Operands SWAPPED against the seam path (round 3): the Toeplitz weights are the A operand (rows = the tile's 16 pixels),
@@ -581,16 +588,24 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
           // is now pixel 4 kg + rr of tile (lane & 15) -- four CONSECUTIVE pixels of one output row, one 16-byte store per lane
           // instead of four 4-byte stores 32 pixels apart.  Same products, same k order per output: bit-identical to the seam path.
 #pragma unroll
-          for (int cp = 0; cp < 5; ++cp) acc = mfma16<F16>(wv[cp], av[cp], acc);
+          for (int cp = 0; cp < 5; ++cp)
+#pragma unroll
+            for (int it = 0; it < NI; ++it) accs[it] = mfma16<F16>(wv[cp], av[it][cp], accs[it]);
           __builtin_amdgcn_sched_barrier(0);
         }
+#pragma unroll
+        for (int it = 0; it < NI; ++it) {
+        const f32x4 acc = accs[it];
+        const int item = item0 + it, rp = item >> 2, j4 = item & 3;
         // lane (n = lane & 15, kg): tile 16 j4 + d_tsel(n), output row oy = kg >> 1 of the pair, pixels 4 (kg & 1) .. + 3 of the tile
         char* orow = reinterpret_cast<char*>(p.out) + (((size_t)sample_d * 400 + (8 * s_d - 1 + 2 * rp)) * 400 + 128 * j4) * OUTSZ;
         float v[4];
+        float mean_v = o_mean;
+        asm volatile("" : "+v"(mean_v));   // a vector instruction takes one scalar operand: the second one goes through a vector register, by hand (left to hipcc, the diagnostic build ends in an illegal two-scalar fma)
         // de-standardise with ONE fma per value on this 16-bit path (the f32 parity path keeps numpy's two roundings, kernels_tail32.hip):
         // <= 1 ulp from y * std + mean, four instructions instead of two packed multiplies + two packed adds + four selects
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) v[rr] = __builtin_fmaf(acc[rr], o_std, o_mean);   // without aff_out: std = 1, mean = 0 -> v exactly
+        for (int rr = 0; rr < 4; ++rr) v[rr] = __builtin_fmaf(acc[rr], o_std, mean_v);   // without aff_out: std = 1, mean = 0 -> v exactly
         const bool lane_on = j4 < 3 || d_last_on;   // item 3 of a row pair holds tiles 48, 49 only
         if (p.nan_guard) {
           // ONE question of the four values first (0 * v summed is NaN iff one of them is not finite: 3 fma + 1 multiply + 1 compare);
@@ -618,6 +633,7 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
           if (OUT == 0) __builtin_nontemporal_store(f32x4nt{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4nt*>(o));
           else if (OUT == 1) __builtin_nontemporal_store(u32x2nt{pack2<false>(v[0], v[1]), pack2<false>(v[2], v[3])}, reinterpret_cast<u32x2nt*>(o));
           else __builtin_nontemporal_store(u32x2nt{pack2<true>(v[0], v[1]), pack2<true>(v[2], v[3])}, reinterpret_cast<u32x2nt*>(o));
+        }
         }
       };
       auto do_d = [&](const int item) {  // seam rows (sample / segment boundaries): called (not looped) so no conservative vmcnt(0) lands in front of it
@@ -694,17 +710,9 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
           }
         }
       };
-      auto run_d = [&]() {
-        if (!d_on || d_cnt < 1) return;
-        const int rp = d_first >> 2;    // both items of a wave sit in the same row pair
-        // wave-uniform: no regular rows at all (flush round / a segment's warm-up strip), or row pair 0 of a strip whose row
-        // above belongs to another sample or lies above the image (first strip of a virtual sample; strip 0 of a real one)
-        const bool seam_round = d_warm || (rp == 0 && (sd == 0 || s_d == 0));
-        if (seam_round) {
-          do_d(d_first);
-          if (d_cnt >= 2) do_d(d_first + 1);
-          return;
-        }
+      // the one or two items item0 (, item0 + 1) of one row pair, away from every seam
+      auto run_d_fast = [&](const int item0, const int cnt) {
+        const int rp = item0 >> 2;
         // ring byte offsets of window rows (d_dy) and (d_dy + 2) of the row pair: uniform slot + lane row, wrapped at 18 rows
         // (unsigned min: v - 18 rows wraps around to a huge value unless v is past the end)
         const int sa = (8 * gd + 16 + 2 * rp) % T_RING_ROWS;
@@ -712,14 +720,29 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
         v0 = min(v0, v0 - (unsigned)(T_RING_ROWS * T_ROWP));
         unsigned v1 = v0 + 2u * T_ROWP;
         v1 = min(v1, v1 - (unsigned)(T_RING_ROWS * T_ROWP));
-        d_fast(0, (int)v0, (int)v1);
-        if (d_cnt >= 2) d_fast(1, (int)v0, (int)v1);
+        const bool skip_last = TAIL_ABL(64);   // diagnostic: what the 2-of-16-tile items at the end of every row pair cost
+        if (cnt >= 2 && !(skip_last && ((item0 + 1) & 3) == 3)) d_fast(ic<2>(), item0, (int)v0, (int)v1);
+        else if (!(skip_last && (item0 & 3) == 3)) d_fast(ic<1>(), item0, (int)v0, (int)v1);
       };
-      // stagger: the BC-only-plus-D waves do their latency-bound D items first, so their VALU-heavy
-      // BC items overlap the tail (A items) of the waves that started with BC
+      auto run_d = [&]() {
+        if (!d_on || d_cnt < 1) return;
+        const int rp = d_first >> 2;
+        // wave-uniform: no regular rows at all (flush round / a segment's warm-up strip), or row pair 0 of a strip whose row
+        // above belongs to another sample or lies above the image (first strip of a virtual sample; strip 0 of a real one)
+        const bool seam_round = d_warm || (rp == 0 && (sd == 0 || s_d == 0));
+        if (seam_round) {
+          do_d(d_first);
+          if (d_cnt >= 2) do_d(d_first + 1);
+        } else {
+          run_d_fast(d_first, d_cnt);
+        }
+        // the second pair of waves 14, 15 lies in row pair 1: never at a seam, and without rows in a flush / warm-up round
+        if (d_cnt == 4 && !d_warm) run_d_fast(d_second, 2);
+      };
+      // Role Q does its latency-bound D items first, so that its VALU-heavy BC item overlaps the tail (A items) of the role-P
+      // waves, which start with BC
       if (PROF) ts[0] = __builtin_amdgcn_s_memtime();
-      const bool d_first_order = TAIL_ABL(16) ? false : (TAIL_ABL(32) ? true : wave >= 8);
-      if (d_first_order) {
+      if (ROLE_Q) {
         if (!TAIL_ABL(128)) __builtin_amdgcn_s_setprio(3);  // D is a latency chain with few instructions: let it through
         run_d();
         __builtin_amdgcn_s_setprio(0);
@@ -727,23 +750,22 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       if (PROF) ts[1] = __builtin_amdgcn_s_memtime();
       do_bc();
       if (PROF) ts[2] = __builtin_amdgcn_s_memtime();
-      if (!d_first_order) {
-        run_a();
-        if (!TAIL_ABL(128)) __builtin_amdgcn_s_setprio(3);
-        run_d();
-        __builtin_amdgcn_s_setprio(0);
-      }
+      if (ROLE_P) run_a();
       if (PROF) ts[3] = __builtin_amdgcn_s_memtime();
-      if (d_first_order) run_a();   // (waves 8-15 have no A items; the diagnostic orders keep the call)
     }
 
     if (PROF) ts[4] = __builtin_amdgcn_s_memtime();
     lds_barrier();
     if (PROF) {
       ts[5] = __builtin_amdgcn_s_memtime();
-      const bool a_in_d = !(TAIL_ABL(16) ? false : (TAIL_ABL(32) ? true : wave >= 8));   // A ran between BC and D (inside ts[2]..ts[3])
-      tD += (ts[1] - ts[0]) + (ts[3] - ts[2]) - (a_in_d ? a_span : 0); tBC += ts[2] - ts[1]; tA += a_span; tBar += ts[5] - ts[4];
+      tD += ts[1] - ts[0]; tBC += ts[2] - ts[1]; tA += ts[3] - ts[2]; tBar += ts[5] - ts[4];
     }
+  }
+  };
+  if (K > 0) {
+    const int last = G + 2;
+    if (wave < 8) rounds(ic<0>(), last);
+    else rounds(ic<1>(), last);
   }
   if (PROF && p.prof && blockIdx.x == 0 && lane == 0) {
     unsigned long long* o = p.prof + wave * 5;
