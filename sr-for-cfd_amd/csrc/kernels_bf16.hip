@@ -333,12 +333,12 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   const uint4* w3_f = reinterpret_cast<const uint4*>(cst + TC_OFF_W3);
   const uint4* w2_f = reinterpret_cast<const uint4*>(p.w2frags);
   const float conv_bias = *reinterpret_cast<const float*>(cst + TC_OFF_BC);
-  const uint4* const w4_f = reinterpret_cast<const uint4*>(cst + TC_OFF_W4);   // ConvT#4 A operand: read per item (one ds_read_b128)
+  const uint4* const w4_f = reinterpret_cast<const uint4*>(cst + TC_OFF_W4);   // ConvT#4 A operand: read once per launch, in front of the round loop
   // D-item lane constants: tile within the item, window sub-pixel (dy,dx) of this lane's k-group,
   // byte offsets of the five window column pairs relative to granule (plane 0, tx)
   const int d_tsel = 4 * (lane & 3) + ((lane & 15) >> 2);
   // (window sub-pixel (dy, dx) of a lane's k-group and the five window column offsets of the seam path are recomputed inside do_d:
-  // the hot loop has no register to spare for constants of a path that runs once per sample)
+  // the registers the role split freed hold the BC item's constants (`rounds`, below), not those of a path that runs once per sample)
 
   // D fast path (every row pair that is not at a sample / segment seam): everything that depends on the lane only is
   // computed here, once; a round adds wave-uniform terms.  (These address and epilogue instructions were 65 of a D item's
@@ -358,7 +358,9 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   //   D : waves 8,9,12,13 -> one item each (0-3); waves 10,11 -> two each (8-11); waves 14,15 -> four each (12-15 and 4-7)
   // Two wave roles, each with a round loop of its own (`rounds`, below): P = waves 0-7 (BC + A, no D state), Q = waves 8-15
   // (D + BC, no ConvT#2 operands).  ConvT#2's resident weights and prefetched input (32 registers) and D's lane constants are
-  // then live only in the role that uses them, which is what leaves room for two interleaved D chains in role Q.
+  // then live only in the role that uses them, which is what leaves room for two interleaved D chains in role Q -- and, at 96
+  // registers of the 128 a wave may have, for the constants of a wave's BC item (its ConvT#3 and ConvT#4 weight fragments and b4),
+  // which both roles read once per launch: a BC item is 6 ds_read_b128 (2 data + b3), not 17.
   const int a_mt = wave & 3, a_ct = (wave >> 2) & 1;
   const int sq = wave >> 2, sl = wave & 3;       // wave = 4 * sq + sl, SIMD = sl
   int bc_item = -1, d_first = 0, d_cnt = 0, d_second = 0;   // D items d_first .. + min(d_cnt, 2) - 1, and d_second, d_second + 1 when d_cnt == 4
@@ -441,6 +443,14 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       for (int kk = 0; kk < 4; ++kk) xb[kk] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4nt*>(src + 16 * kk)));
     }
   }
+  // A BC item's constants, resident for the whole launch (28 registers; the role split left ~30 unallocated under the 128 a wave
+  // of a 1024-thread workgroup may have): the two ConvT#3 weight fragments of the item's row tile, ConvT#4's fragment, and b4,
+  // which is the C operand of both ConvT#4 MFMAs (each result goes to an accumulator of its own: no copy).  hipcc cannot hoist
+  // these reads itself: the loop writes LDS.  b3 (16 more) does not fit beside b4 and stays in LDS, as does role P's b2.  Waves
+  // 14 and 15 have no BC item and never use theirs.  (121-122 registers, no scratch: tests/test_tail16_listing.py.)
+  const int m3 = bc_item & 1;
+  const uint4 w3r0 = w3_f[(m3 * 2 + 0) * 64 + lane], w3r1 = w3_f[(m3 * 2 + 1) * 64 + lane], w4r = w4_f[lane];
+  const f32x16 b4r = load_bias16(cst + TC_OFF_B4 + h * 64);
 #pragma nounroll   // also keeps hipcc from peeling round 0: one loop and one s_barrier per role in the listing
   for (int r = 0; r <= last; ++r) {
     // ---------------- A: ConvT#2 for strip g = r (input prefetched last round), then prefetch g+1 ----------------
@@ -483,14 +493,13 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       const int g = r - 1;
       if (!(bc_item >= 0 && g >= 0 && g < G && !TAIL_ABL(8))) return;
       { int sm, sx, sg, sl; strip_of(g, sm, sx, sg, sl); if (sx < 0) return; }  // warm-up strip of a top segment: nothing above the image
-      const int m3 = bc_item & 1;
       const char* src = l100 + (g & 1) * T_L100_BUF;
       uint4 b0 = *reinterpret_cast<const uint4*>(src + bc_l0), b1 = *reinterpret_cast<const uint4*>(src + bc_l0 + 2 * 212 * 16);
       f32x16 acc3 = load_bias16(cst + TC_OFF_B3 + h * 64);
-      acc3 = mfma32<F16>(w3_f[(m3 * 2 + 0) * 64 + lane], b0, acc3);
-      acc3 = mfma32<F16>(w3_f[(m3 * 2 + 1) * 64 + lane], b1, acc3);
+      acc3 = mfma32<F16>(w3r0, b0, acc3);
+      acc3 = mfma32<F16>(w3r1, b1, acc3);
       uint32_t f3[8];
-      const uint4 w4 = w4_f[lane];
+      const uint4 w4 = w4r;
       // the item writes ring rows 8g + 4a + 2 m3 + {0, 1} (a = 100-level row of the lane's pixel; the ConvT#3 tap row is m3
       // for both taps tt): two wave-uniform row offsets per value of a, picked per lane, + the lane's constant granule
       const int rbase = (8 * g) % T_RING_ROWS;
@@ -507,16 +516,16 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       f32x16 acc4a, acc4b;
       if (ab_sw) {       // diagnostic (no swish): the round-2 order
         swish_pack16<F16>(acc3, f3, true);
-        acc4a = mfma32<F16>(w4, make_uint4(f3[0], f3[1], f3[2], f3[3]), load_bias16(cst + TC_OFF_B4 + h * 64));
-        acc4b = mfma32<F16>(w4, make_uint4(f3[4], f3[5], f3[6], f3[7]), load_bias16(cst + TC_OFF_B4 + h * 64));
+        acc4a = mfma32<F16>(w4, make_uint4(f3[0], f3[1], f3[2], f3[3]), b4r);
+        acc4b = mfma32<F16>(w4, make_uint4(f3[4], f3[5], f3[6], f3[7]), b4r);
       } else {
         swish_pack_h<F16, 0, 8>(acc3, f3);
         pin();
-        acc4a = mfma32<F16>(w4, make_uint4(f3[0], f3[1], f3[2], f3[3]), load_bias16(cst + TC_OFF_B4 + h * 64));
+        acc4a = mfma32<F16>(w4, make_uint4(f3[0], f3[1], f3[2], f3[3]), b4r);
         pin();
         swish_pack_h<F16, 8, 8>(acc3, f3 + 4);
         pin();
-        acc4b = mfma32<F16>(w4, make_uint4(f3[4], f3[5], f3[6], f3[7]), load_bias16(cst + TC_OFF_B4 + h * 64));
+        acc4b = mfma32<F16>(w4, make_uint4(f3[4], f3[5], f3[6], f3[7]), b4r);
         pin();
       }
       auto ring_store = [&](const uint32_t (&f4)[8], const int tt) {
