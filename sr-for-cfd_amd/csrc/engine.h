@@ -55,11 +55,19 @@ struct Switches {
   int mid_waves = 0;     // SRCFD_MID_WAVES: other workgroup shapes of mid16 (4, 16: waves per workgroup at 32 pixels per wave); 0 = the shape mid_shape selects
   int mid_order = 0;     // SRCFD_MID_ORDER=1: mid16's workgroups dispatched with output phases 0 / 3 and 1 / 2 alternating instead of phase by phase
   int tail_seg = 0;      // SRCFD_TAIL_SEG: segments per sample of the 16-bit tail (1, 2, 5, 10, 25); 0 = chosen per batch
+  bool tail32 = true;    // SRCFD_NO_TAIL32=1: the f32 tail layer by layer (convt_triple + the output conv) instead of the streaming tail32
+  bool triple = true;    // SRCFD_NO_TRIPLE=1: ConvT#2 on its own and convt_pair instead of convt_triple
+  bool pair = true;      // SRCFD_NO_PAIR=1: neither convt_triple nor convt_pair: every layer materialised
+  bool gemm32_big = true;   // SRCFD_NO_GEMM32_BIG=1: large launches of the wide decoder layers on the generic f32 GEMM too
   unsigned bits() const {
     return (enc16 ? 1u : 0u) | (mid16 ? 2u : 0u) | (dense1_16 ? 4u : 0u) | (enc32 ? 8u : 0u) | (skinny32 ? 16u : 0u) | (tail16s ? 32u : 0u) |
-           ((unsigned)mid_shape << 6) | ((unsigned)tail_seg << 8) | ((unsigned)mid_waves << 16) | ((unsigned)mid_order << 24);
+           ((unsigned)mid_shape << 6) | ((unsigned)tail_seg << 8) | ((unsigned)mid_waves << 16) | ((unsigned)mid_order << 24) |
+           (tail32 ? 1u << 25 : 0u) | (triple ? 1u << 26 : 0u) | (pair ? 1u << 27 : 0u) | (gemm32_big ? 1u << 28 : 0u);
   }
-  bool all_default() const { return enc16 && mid16 && mid_shape == Switches().mid_shape && dense1_16 && enc32 && skinny32 && !tail16s && tail_seg == 0 && mid_waves == 0 && mid_order == Switches().mid_order; }
+  bool all_default() const {
+    return enc16 && mid16 && mid_shape == Switches().mid_shape && dense1_16 && enc32 && skinny32 && !tail16s && tail_seg == 0 && mid_waves == 0 &&
+           mid_order == Switches().mid_order && tail32 && triple && pair && gemm32_big;
+  }
   static Switches from_env();
 };
 
@@ -72,6 +80,20 @@ struct Plan {
   int graph = 0;      // 0 plain launches, 1 captured now and launched as a graph, 2 replay of an earlier capture
   bool fused = false;
   bool any16 = false;  // the 16-bit forward ran the any16 graph (decoder=any16)
+};
+
+// One step of the f32-grade forward (Model::f32_step): the kernel that takes ops [i, i + count) at a given batch, precision and switches.
+enum class F32Kernel { Tail32, Triple, Pair, X3Group, Big, Group, Skinny, Finalize, Mfma, Naive };
+struct F32Step {
+  F32Kernel k;
+  int count;
+  bool x3_tail;   // Tail32: its first two layers on the split-bf16 MFMAs
+};
+// Device operands of up to four ops (the output phases of one layer): f32 weights, split-bf16 planes (or null), biases
+struct F32Operands {
+  const float* B[4];
+  const uint16_t* Bx[4];
+  const float* bias[4];
 };
 
 struct Model {
@@ -146,9 +168,14 @@ struct Model {
 
   ~Model();
   int init_device();
-  size_t max_act_elems() const;
-  int chunk_cap() const;
-  int ensure_workspace(int n);
+  // The f32-grade forward's kernel choice (engine.hip): the loop of forward_generic and the sizes of its buffers all ask f32_step
+  size_t f32_first(int precision, const Switches& sw) const;   // 4: enc32 takes ops [0, 4) in front of the loop; else 0
+  F32Step f32_step(size_t i, int n, int precision, const Switches& sw) const;
+  void f32_span(size_t i, int count, int n, GemmDesc ds[4], F32Operands* w = nullptr) const;
+  size_t max_act_elems(int precision, const Switches& sw) const;
+  int chunk_cap(int precision, const Switches& sw) const;
+  size_t splitk_need(int n, int precision, const Switches& sw) const;
+  int ensure_workspace(int n, const Switches& sw);
   int launch(const char* name, hipStream_t s, const std::function<hipError_t()>& fn);
   int forward_generic(const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
                       unsigned long long* nonfinite, hipStream_t s);

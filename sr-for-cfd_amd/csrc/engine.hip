@@ -124,6 +124,10 @@ Switches Switches::from_env() {
   w.dense1_16 = on("SRCFD_DENSE1", true);
   w.enc32 = !on("SRCFD_NO_ENC32", false);
   w.skinny32 = !on("SRCFD_NO_DENSE_SKINNY", false);
+  w.tail32 = !on("SRCFD_NO_TAIL32", false);
+  w.triple = !on("SRCFD_NO_TRIPLE", false);
+  w.pair = !on("SRCFD_NO_PAIR", false);
+  w.gemm32_big = !on("SRCFD_NO_GEMM32_BIG", false);
   { const char* t = getenv("SRCFD_TAIL"); w.tail16s = t && t[0] == 's'; }
   { const char* e = getenv("SRCFD_MID_ORDER"); if (e) w.mid_order = atoi(e) == 1 ? 1 : 0; }
   { const char* e = getenv("SRCFD_MID_WAVES"); const int v = e ? atoi(e) : 0; w.mid_waves = (v == 4 || v == 16) ? v : 0; }
@@ -158,17 +162,60 @@ static const char* const LOWP_REFUSAL =
     "bf16/f16 precision needs encoder_10 in front, Dense / 2x2 or 3x3 stride-2 Conv2DTranspose layers with input channels a multiple of 16 behind it and a "
     "3x3 'same' Conv2D to one channel at the end (the encoder_10+decoder_400 layer graph is one); use SRCFD_PREC_FP32 for other graphs";
 
-static bool tail32_disabled() {
-  static const bool off = [] { const char* e = getenv("SRCFD_NO_TAIL32"); return e && atoi(e) != 0; }();
-  return off;
+// ---------------------------------------------------------------------------
+// The f32-grade forward's kernel choice.  f32_step answers "which kernel takes op i at batch n" for the launch loop
+// (forward_generic) and for everything that sizes its buffers (max_act_elems, splitk_need): no HIP calls, nothing allocated.
+// ---------------------------------------------------------------------------
+// Descriptors of ops [i, i + count) at batch n and, with `w`, their device operands
+void Model::f32_span(size_t i, int count, int n, GemmDesc ds[4], F32Operands* w) const {
+  for (int q = 0; q < count; ++q) {
+    const Op& op = ops[i + q];
+    ds[q] = op.d;
+    ds[q].M = n * ds[q].MH * ds[q].MW;
+    if (!w) continue;
+    w->B[q] = d_pack.get() + op.w_off;
+    w->Bx[q] = x3_off[i + q] >= 0 ? d_pack_x3.get() + x3_off[i + q] : nullptr;
+    w->bias[q] = d_pack.get() + op.b_off;
+  }
+}
+
+// enc32: standardise + the encoder's four layers as one launch in front of the loop
+size_t Model::f32_first(int precision, const Switches& sw) const { return enc32_ok && sw.enc32 && precision != SRCFD_PREC_FP32_NAIVE ? 4 : 0; }
+
+F32Step Model::f32_step(size_t i, int n, int precision, const Switches& sw) const {
+  if (precision == SRCFD_PREC_FP32_NAIVE) return {F32Kernel::Naive, 1, false};   // the bring-up path: every op on its own
+  // SRCFD_PREC_FP32X3: the split-bf16 kernels from 64 samples on: below that their serial k loops lose to the generic f32 kernels'
+  // split-K launches (tools/precision_sweep.py: 0.26 vs 0.13 ms at 3 samples, break-even between 48 and 96), so small calls run
+  // exactly the SRCFD_PREC_FP32 path.
+  const bool x3 = precision == SRCFD_PREC_FP32X3 && !pack_x3.empty() && n >= 64;
+  int cnt = 1;   // the ops of one layer (ConvT output phases) are launched together
+  while (i + cnt < ops.size() && ops[i + cnt].layer == ops[i].layer && cnt < 4) ++cnt;
+  GemmDesc ds[4];
+  f32_span(i, cnt, n, ds);
+  if (i + 1 == ops.size() && gemm_fuses_finalize(ds[0])) return {F32Kernel::Finalize, 1, false};   // last layer: epilogue writes the caller's buffer directly
+  if (sw.tail32 && (int)i == tail32_op) return {F32Kernel::Tail32, 4, x3 && t32_w1x >= 0 && t32_w2x >= 0};   // ConvT#2 -> #3 -> #4 -> output conv + finalize
+  if (sw.pair && sw.triple && (int)i == triple_op && i + 3 < ops.size()) return {F32Kernel::Triple, 3, false};   // ConvT#2 -> #3 -> #4
+  if (sw.pair && (int)i == pair_op && i + 2 < ops.size()) return {F32Kernel::Pair, 2, false};   // ConvT#3 -> ConvT#4 (kernels.h, PairDesc)
+  if (x3) {   // every GEMM of the layer on the split-bf16 kernel, or none
+    bool all = true;
+    for (int q = 0; q < cnt && all; ++q) all = x3_off[i + q] >= 0 && gemm_x3_qualifies(ds[q]);
+    if (all) return {F32Kernel::X3Group, cnt, false};
+  }
+  if (cnt == 1 && sw.skinny32 && dense_skinny32_qualifies(ds[0])) return {F32Kernel::Skinny, 1, false};
+  if (sw.gemm32_big && gemm32_big_qualifies(ds, cnt)) return {F32Kernel::Big, cnt, false};   // sums its K slabs in registers: no slab workspace
+  return {cnt > 1 ? F32Kernel::Group : F32Kernel::Mfma, cnt, false};
 }
 
 // Largest activation that sits in a ping-pong buffer.  With the streaming tail (tail32) the layers from its first one on
 // never materialise: the largest tensor of the f32 path is then ConvT#1's output (640 KB per sample, not 5.12 MB).
-size_t Model::max_act_elems() const {
+size_t Model::max_act_elems(int precision, const Switches& sw) const {
   size_t m = (size_t)desc.in_shape[0] * desc.in_shape[1] * desc.in_shape[2];
-  const bool streaming = tail32_op >= 0 && !tail32_disabled() && precision != SRCFD_PREC_FP32_NAIVE;   // the bring-up path runs layer by layer
-  const int stop = streaming ? ops[tail32_op].layer : (int)desc.layers.size();
+  int stop = (int)desc.layers.size();
+  F32Step st;
+  for (size_t i = 0; i < ops.size() && stop == (int)desc.layers.size(); i += st.count) {
+    st = f32_step(i, 1, precision, sw);
+    if (st.k == F32Kernel::Tail32) stop = ops[i].layer;
+  }
   for (int i = 0; i < stop; ++i) {
     const Layer& L = desc.layers[i];
     m = std::max(m, (size_t)L.out_shape[0] * L.out_shape[1] * L.out_shape[2]);
@@ -178,34 +225,44 @@ size_t Model::max_act_elems() const {
 
 // Samples per pass of the layer-by-layer path: two buffers of the largest activation within 3 GB, at most 1024 samples
 // (batch 256 = 768 samples runs as one pass with the streaming tail, as three without it).
-int Model::chunk_cap() const {
-  size_t per = 2 * max_act_elems() * sizeof(float);
+int Model::chunk_cap(int precision, const Switches& sw) const {
+  size_t per = 2 * max_act_elems(precision, sw) * sizeof(float);
   size_t cap = ((size_t)3 << 30) / std::max<size_t>(per, 1);
   return (int)std::max<size_t>(1, std::min<size_t>(cap, 1024));
 }
 
-int Model::ensure_workspace(int n) {
-  int chunk = std::min(n, chunk_cap());
-  const size_t per = max_act_elems();   // depends on the precision: the bring-up path materialises every layer
-  if (chunk <= ws_chunk && per <= ws_per_sample) return SRCFD_OK;
-  drop_graph();  // a captured forward holds the old buffers' addresses
-  ws_chunk = 0;
-  for (auto& b : buf) { int rc = b.alloc((size_t)chunk * per); if (rc) return rc; }
+// Split-K slab floats of an n-sample chunk: what the generic GEMM launches that f32_step returns FOR THAT n ask for.  Not
+// monotonic in n: a layer that gemm32_big takes at a large batch needs slabs at a small one.
+size_t Model::splitk_need(int n, int precision, const Switches& sw) const {
   size_t need = 0;
-  for (size_t i = 0; i < ops.size();) {  // the ops of one layer (ConvT output phases) are launched together: their slabs coexist
-    size_t j = i;
+  F32Step st;
+  for (size_t i = f32_first(precision, sw); i < ops.size(); i += st.count) {
+    st = f32_step(i, n, precision, sw);
+    if (st.k != F32Kernel::Group && st.k != F32Kernel::Mfma) continue;
     GemmDesc ds[4];
-    int cnt = 0;
-    for (; j < ops.size() && ops[j].layer == ops[i].layer && cnt < 4; ++j) { ds[cnt] = ops[j].d; ds[cnt].M = chunk * ds[cnt].MH * ds[cnt].MW; ++cnt; }
-    static const bool no_big = [] { const char* e = getenv("SRCFD_NO_GEMM32_BIG"); return e && atoi(e) != 0; }();
-    if (no_big || !gemm32_big_qualifies(ds, cnt))   // gemm32_big sums its K slabs in registers: no slab workspace for those launches
-      need = std::max(need, gemm_group_ws_floats(ds, cnt));
-    i = j;
+    f32_span(i, st.count, n, ds);
+    need = std::max(need, st.k == F32Kernel::Group ? gemm_group_ws_floats(ds, st.count) : gemm_splitk_ws_floats(ds[0]));
   }
-  int rc = need ? d_splitk.alloc(need) : d_splitk.release();
-  if (rc) return rc;
-  ws_per_sample = per;
-  ws_chunk = chunk;
+  return need;
+}
+
+// Buffers of an n-sample forward: the two activation buffers grow to the call's chunk, the slabs to what its chunks (whole ones
+// and the remainder) ask for; neither shrinks on a smaller call.
+int Model::ensure_workspace(int n, const Switches& sw) {
+  const int chunk = std::min(n, chunk_cap(precision, sw));
+  const size_t per = max_act_elems(precision, sw);   // depends on the precision: the bring-up path materialises every layer
+  const bool grow = chunk > ws_chunk || per > ws_per_sample;
+  const int step = grow ? chunk : ws_chunk;   // predict_device's chunks: min(n, step) samples, then n % step
+  const size_t need = std::max(splitk_need(std::min(n, step), precision, sw), n > step && n % step ? splitk_need(n % step, precision, sw) : 0);
+  if (!grow && need <= d_splitk.size()) return SRCFD_OK;
+  drop_graph();  // a captured forward holds the old buffers' addresses
+  if (need > d_splitk.size()) { int rc = d_splitk.alloc(need); if (rc) return rc; }
+  if (grow) {
+    ws_chunk = 0;
+    for (auto& b : buf) { int rc = b.alloc((size_t)chunk * per); if (rc) return rc; }
+    ws_per_sample = per;
+    ws_chunk = chunk;
+  }
   return SRCFD_OK;
 }
 
@@ -228,23 +285,18 @@ int Model::launch(const char* name, hipStream_t s, const std::function<hipError_
   return SRCFD_OK;
 }
 
-// Generic layer-by-layer f32 forward of one chunk (<= ws_chunk samples).
+// f32-grade forward of one chunk (<= ws_chunk samples): the steps of f32_step, one launch each.
 int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
                            int flags, unsigned long long* nonfinite, hipStream_t s) {
   const int in_elems = desc.in_shape[0] * desc.in_shape[1] * desc.in_shape[2];
   const int* os = desc.out_shape();
   const int out_elems = os[0] * os[1] * os[2];
-  const bool naive = precision == SRCFD_PREC_FP32_NAIVE;
-  const bool x3 = precision == SRCFD_PREC_FP32X3;
-  int cur = 0;
-  int rc = SRCFD_OK;
-  int prev_layer = -1;
-  size_t first = 0;
-  const bool no_enc32 = !sw.enc32;   // functional A/B switch of the tests (Switches, engine.h)
+  const int guard = flags & SRCFD_FLAG_NAN_GUARD;
   const float* const d_pack = this->d_pack.get();
-  const uint16_t* const d_pack_x3 = this->d_pack_x3.get();
   float* const buf[2] = {this->buf[0].get(), this->buf[1].get()};
-  if (enc32_ok && !naive && !no_enc32) {   // standardise + the encoder's four layers: one launch, latent vectors into buf[0]
+  int rc = SRCFD_OK;
+  const size_t first = f32_first(precision, sw);
+  if (first) {   // standardise + the encoder's four layers: one launch, latent vectors into buf[0]
     Enc32Params ep;
     ep.x = x_dev; ep.affine = aff_in; ep.n = n;
     ep.w1 = d_pack + ops[0].w_off; ep.b1 = d_pack + ops[0].b_off;
@@ -255,143 +307,86 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
     ep.nl = ops[3].d.N; ep.nl_pad = ops[3].d.Npad;
     ep.act1 = ops[0].d.act; ep.act2 = ops[1].d.act; ep.act3 = ops[2].d.act; ep.act4 = ops[3].d.act;
     rc = launch("encoder(standardize..latent_vector)", s, [&] { return launch_enc32(ep, s); });
-    if (rc) return rc;
-    first = 4;
-    prev_layer = ops[3].layer;
-    cur = 1;          // the next op is a new layer: it flips to buf[0], where the latent vectors are
   } else {
     rc = launch("standardize", s, [&] { return launch_standardize(x_dev, buf[0], aff_in, in_elems, (int64_t)n * in_elems, s); });
-    if (rc) return rc;
   }
-  for (size_t i = first; i < ops.size(); ++i) {
+  int cur = 0;   // buf[cur]: the input of the next step
+  F32Step st;
+  for (size_t i = first; i < ops.size() && !rc; i += st.count) {
+    st = f32_step(i, n, precision, sw);
     const Op& op = ops[i];
-    if (op.layer != prev_layer && prev_layer >= 0) cur ^= 1;
-    prev_layer = op.layer;
-    GemmDesc d = op.d;
-    d.M = n * d.MH * d.MW;
+    GemmDesc ds[4];
+    F32Operands w;
+    f32_span(i, st.count, n, ds, &w);
+    const GemmDesc& d = ds[0];
     const float* X = buf[cur];
     float* Y = buf[cur ^ 1];
-    const float* B = d_pack + op.w_off;
-    const float* bias = d_pack + op.b_off;
-    if (!naive && i + 1 == ops.size() && gemm_fuses_finalize(d)) {  // last layer: epilogue writes the caller's buffer directly
-      return launch(op.name.c_str(), s, [&] {
-        return launch_gemm_finalize(d, X, B, bias, y_dev, out_dtype, aff_out, flags & SRCFD_FLAG_NAN_GUARD, nonfinite, s);
-      });
-    }
-    if (!naive && !tail32_disabled() && (int)i == tail32_op) {  // ConvT#2 -> #3 -> #4 -> output conv + finalize: one streaming kernel
-      Tail32Params tp;
-      tp.in = X; tp.out = y_dev; tp.n = n; tp.H = d.MH; tp.W = d.MW;
-      tp.w1f = d_pack + t32.w1; tp.b1 = d_pack + t32.b1; tp.w2f = d_pack + t32.w2; tp.b2 = d_pack + t32.b2;
-      tp.w3f = d_pack + t32.w3; tp.b3 = d_pack + t32.b3; tp.wc = d_pack + t32.wc;
-      tp.aff_out = aff_out; tp.nan_guard = flags & SRCFD_FLAG_NAN_GUARD; tp.nonfinite = nonfinite; tp.out_dtype = out_dtype;
-      tp.seg = tail32_segments(n, d.MH, num_cus);
-      if (x3 && d_pack_x3 && t32_w1x >= 0 && t32_w2x >= 0 && n >= 64) {   // SRCFD_PREC_FP32X3: the first two layers on the bf16 matrix cores
-        tp.w1x = d_pack_x3 + t32_w1x;
-        tp.w2x = d_pack_x3 + t32_w2x;
-      }
-#ifdef SRCFD_DIAG
-      { static const int abl = [] { const char* e = getenv("SRCFD_TAIL32_ABLATE"); return e ? atoi(e) : 0; }(); tp.ablate = abl; }
-#endif
-      const std::string nm = op.name + "+" + ops[i + 1].name + "+" + ops[i + 2].name + "+" + ops[i + 3].name + (tp.w1x ? "(x3)" : "");
-      return launch(nm.c_str(), s, [&] { return launch_tail32(tp, num_cus, s); });
-    }
-    static const bool no_pair = [] { const char* e = getenv("SRCFD_NO_PAIR"); return e && atoi(e) != 0; }();
-    static const bool no_triple = [] { const char* e = getenv("SRCFD_NO_TRIPLE"); return e && atoi(e) != 0; }();
-    if (!naive && !no_pair && !no_triple && (int)i == triple_op && i + 3 < ops.size()) {  // ConvT#2 -> #3 -> #4 in one kernel
-      TripleDesc td;
-      td.n = n; td.H = d.MH; td.W = d.MW; td.act1 = d.act; td.act2 = ops[i + 1].d.act; td.act3 = ops[i + 2].d.act;
-      const std::string nm = op.name + "+" + ops[i + 1].name + "+" + ops[i + 2].name;
-      rc = launch(nm.c_str(), s, [&] {
-        return launch_convt_triple_f32(td, X, d_pack + tri.w1, d_pack + tri.b1, d_pack + tri.w2, d_pack + tri.b2, d_pack + tri.w3,
-                                       d_pack + tri.b3, Y, s);
-      });
-      if (rc) return rc;
-      prev_layer = ops[i + 2].layer;
-      i += 2;
-      continue;
-    }
-    if (!naive && !no_pair && (int)i == pair_op && i + 2 < ops.size()) {  // ConvT#3 -> ConvT#4 in one kernel (kernels.h, PairDesc)
-      PairDesc pd;
-      pd.n = n; pd.H = d.MH; pd.W = d.MW; pd.act_a = d.act; pd.act_b = ops[i + 1].d.act;
-      const std::string nm = op.name + "+" + ops[i + 1].name;
-      rc = launch(nm.c_str(), s, [&] {
-        return launch_convt_pair_f32(pd, X, d_pack + pair.wa, d_pack + pair.ba, d_pack + pair.wb, d_pack + pair.bb, Y, s);
-      });
-      if (rc) return rc;
-      prev_layer = ops[i + 1].layer;  // the pair's output sits where the first layer's would: the next layer toggles once
-      ++i;
-      continue;
-    }
-    size_t j = i + 1;
-    while (j < ops.size() && ops[j].layer == op.layer && j - i < 4) ++j;
-    // SRCFD_PREC_FP32X3: every GEMM of the layer on the split-bf16 kernel (one launch per output phase) -- from 64 samples on: below
-    // that its serial k loops lose to the generic f32 kernels' split-K launches (tools/precision_sweep.py: 0.26 vs 0.13 ms at 3
-    // samples, break-even between 48 and 96), so small calls run exactly the SRCFD_PREC_FP32 path.
-    if (x3 && d_pack_x3 && n >= 64) {
-      bool all = true;
-      for (size_t q = i; q < j && all; ++q) {
-        GemmDesc dq = ops[q].d;
-        dq.M = n * dq.MH * dq.MW;
-        all = x3_off[q] >= 0 && gemm_x3_qualifies(dq);
-      }
-      if (all) {
-        GemmDesc dsx[4];
-        const uint16_t* wx[4];
-        const float* bx[4];
-        const int cnt = (int)(j - i);
-        for (int q = 0; q < cnt; ++q) {
-          dsx[q] = ops[i + q].d;
-          dsx[q].M = n * dsx[q].MH * dsx[q].MW;
-          wx[q] = d_pack_x3 + x3_off[i + q];
-          bx[q] = d_pack + ops[i + q].b_off;
+    const size_t next = i + st.count;
+    if (next == ops.size() || ops[next].layer != ops[next - 1].layer) cur ^= 1;   // the next step starts a new layer: it reads what this one writes
+    const char* name = (st.count > 1 ? desc.layers[op.layer].name : op.name).c_str();   // the output phases of one layer go by the layer's name
+    std::string nm;   // of a launch that spans layers
+    switch (st.k) {
+      case F32Kernel::Finalize:
+        return launch(name, s, [&] { return launch_gemm_finalize(d, X, w.B[0], w.bias[0], y_dev, out_dtype, aff_out, guard, nonfinite, s); });
+      case F32Kernel::Tail32: {   // one streaming kernel up to the caller's buffer
+        Tail32Params tp;
+        tp.in = X; tp.out = y_dev; tp.n = n; tp.H = d.MH; tp.W = d.MW;
+        tp.w1f = d_pack + t32.w1; tp.b1 = d_pack + t32.b1; tp.w2f = d_pack + t32.w2; tp.b2 = d_pack + t32.b2;
+        tp.w3f = d_pack + t32.w3; tp.b3 = d_pack + t32.b3; tp.wc = d_pack + t32.wc;
+        tp.aff_out = aff_out; tp.nan_guard = guard; tp.nonfinite = nonfinite; tp.out_dtype = out_dtype;
+        tp.seg = tail32_segments(n, d.MH, num_cus);
+        if (st.x3_tail) {   // SRCFD_PREC_FP32X3: the first two layers on the bf16 matrix cores
+          tp.w1x = d_pack_x3.get() + t32_w1x;
+          tp.w2x = d_pack_x3.get() + t32_w2x;
         }
-        // the layer's output phases: one launch (kernels_x3.hip, X3Group); a single-op layer: its own kernel
-        std::string nm = ops[i].name;
-        if (cnt > 1) { const size_t dot = nm.rfind(".ph"); if (dot != std::string::npos) nm.resize(dot); }
-        nm += "(x3)";
-        rc = launch(nm.c_str(), s, [&] { return launch_gemm_x3_group(dsx, cnt, X, wx, bx, Y, s, num_cus); });
-        if (rc) return rc;
-        i = j - 1;
-        continue;
+#ifdef SRCFD_DIAG
+        { static const int abl = [] { const char* e = getenv("SRCFD_TAIL32_ABLATE"); return e ? atoi(e) : 0; }(); tp.ablate = abl; }
+#endif
+        name = (nm = op.name + "+" + ops[i + 1].name + "+" + ops[i + 2].name + "+" + ops[i + 3].name + (st.x3_tail ? "(x3)" : "")).c_str();
+        return launch(name, s, [&] { return launch_tail32(tp, num_cus, s); });
       }
-    }
-    if (!naive && j - i > 1) {  // the output phases of one transposed convolution: one launch (kernels_fp32.hip, GemmGroup)
-      GemmDesc ds[4];
-      const float* Bs[4];
-      const float* biases[4];
-      const int cnt = (int)(j - i);
-      for (int q = 0; q < cnt; ++q) {
-        ds[q] = ops[i + q].d; ds[q].M = n * ds[q].MH * ds[q].MW;
-        Bs[q] = d_pack + ops[i + q].w_off; biases[q] = d_pack + ops[i + q].b_off;
+      case F32Kernel::Triple: {
+        TripleDesc td;
+        td.n = n; td.H = d.MH; td.W = d.MW; td.act1 = d.act; td.act2 = ds[1].act; td.act3 = ds[2].act;
+        name = (nm = op.name + "+" + ops[i + 1].name + "+" + ops[i + 2].name).c_str();
+        rc = launch(name, s, [&] {
+          return launch_convt_triple_f32(td, X, d_pack + tri.w1, d_pack + tri.b1, d_pack + tri.w2, d_pack + tri.b2, d_pack + tri.w3,
+                                         d_pack + tri.b3, Y, s);
+        });
+        break;
       }
-      static const bool no_big = [] { const char* e = getenv("SRCFD_NO_GEMM32_BIG"); return e && atoi(e) != 0; }();
-      const bool big = !no_big && gemm32_big_qualifies(ds, cnt);
-      rc = launch(desc.layers[op.layer].name.c_str(), s, [&] {
-        return big ? launch_gemm32_big(ds, cnt, X, Bs, biases, Y, s) : launch_gemm_mfma_group(ds, cnt, X, Bs, biases, Y, s, d_splitk.get(), d_splitk.size());
-      });
-      if (rc) return rc;
-      i = j - 1;
-      continue;
+      case F32Kernel::Pair: {
+        PairDesc pd;
+        pd.n = n; pd.H = d.MH; pd.W = d.MW; pd.act_a = d.act; pd.act_b = ds[1].act;
+        name = (nm = op.name + "+" + ops[i + 1].name).c_str();
+        rc = launch(name, s, [&] { return launch_convt_pair_f32(pd, X, d_pack + pair.wa, d_pack + pair.ba, d_pack + pair.wb, d_pack + pair.bb, Y, s); });
+        break;
+      }
+      case F32Kernel::X3Group:   // the layer's output phases: one launch (kernels_x3.hip, X3Group); a single-op layer: its own kernel
+        nm = op.name;
+        if (st.count > 1) { const size_t dot = nm.rfind(".ph"); if (dot != std::string::npos) nm.resize(dot); }
+        name = (nm += "(x3)").c_str();
+        rc = launch(name, s, [&] { return launch_gemm_x3_group(ds, st.count, X, w.Bx, w.bias, Y, s, num_cus); });
+        break;
+      case F32Kernel::Big:
+        rc = launch(name, s, [&] { return launch_gemm32_big(ds, st.count, X, w.B, w.bias, Y, s); });
+        break;
+      case F32Kernel::Group:   // the output phases of one transposed convolution: one launch (kernels_fp32.hip, GemmGroup)
+        rc = launch(name, s, [&] { return launch_gemm_mfma_group(ds, st.count, X, w.B, w.bias, Y, s, d_splitk.get(), d_splitk.size()); });
+        break;
+      case F32Kernel::Skinny:
+        rc = launch(name, s, [&] { return launch_dense_skinny32(d, X, w.B[0], w.bias[0], Y, s); });
+        break;
+      case F32Kernel::Mfma:
+        rc = launch(name, s, [&] { return launch_gemm_mfma(d, X, w.B[0], w.bias[0], Y, s, d_splitk.get(), d_splitk.size()); });
+        break;
+      case F32Kernel::Naive:
+        rc = launch(name, s, [&] { return launch_gemm_naive(d, X, w.B[0], w.bias[0], Y, s); });
+        break;
     }
-    static const bool no_big1 = [] { const char* e = getenv("SRCFD_NO_GEMM32_BIG"); return e && atoi(e) != 0; }();
-    const bool no_skinny = !sw.skinny32;
-    if (!naive && !no_skinny && dense_skinny32_qualifies(d)) {
-      rc = launch(op.name.c_str(), s, [&] { return launch_dense_skinny32(d, X, B, bias, Y, s); });
-      if (rc) return rc;
-      continue;
-    }
-    if (!naive && !no_big1 && gemm32_big_qualifies(&d, 1)) {
-      rc = launch(op.name.c_str(), s, [&] { return launch_gemm32_big(&d, 1, X, &B, &bias, Y, s); });
-      if (rc) return rc;
-      continue;
-    }
-    rc = launch(op.name.c_str(), s, [&] { return naive ? launch_gemm_naive(d, X, B, bias, Y, s) : launch_gemm_mfma(d, X, B, bias, Y, s, d_splitk.get(), d_splitk.size()); });
-    if (rc) return rc;
   }
-  cur ^= 1;
-  return launch("finalize", s, [&] {
-    return launch_finalize(buf[cur], y_dev, out_dtype, aff_out, out_elems, (int64_t)n * out_elems, flags & SRCFD_FLAG_NAN_GUARD, nonfinite, s);
-  });
+  if (rc) return rc;
+  return launch("finalize", s, [&] { return launch_finalize(buf[cur], y_dev, out_dtype, aff_out, out_elems, (int64_t)n * out_elems, guard, nonfinite, s); });
 }
 
 int Model::predict_device(const void* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
@@ -409,7 +404,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   plan.sw = sw; plan.precision = precision; plan.fused = use_fused && !use_any16; plan.any16 = use_any16;
   if (use_fused && !lowp_ok()) { set_error(LOWP_REFUSAL); return SRCFD_EINVAL; }
   if (!use_fused) {
-    int rc = ensure_workspace(n);  // (re)allocates before anything is captured; drops a stale graph when it does
+    int rc = ensure_workspace(n, sw);  // (re)allocates before anything is captured; drops a stale graph when it does
     if (rc) return rc;
   }
   const int in_elems = desc.in_shape[0] * desc.in_shape[1] * desc.in_shape[2];
@@ -778,7 +773,7 @@ int srcfd_model_reserve(srcfd_model* m, int n) {
       if (!mm.lowp_ok()) { set_error(srcfd::LOWP_REFUSAL); return SRCFD_EINVAL; }
       return srcfd::lowp16_reserve(mm, n);
     }
-    return mm.ensure_workspace(n);
+    return mm.ensure_workspace(n, srcfd::Switches::from_env());
   });
 }
 
@@ -813,8 +808,9 @@ int srcfd_model_workspace(srcfd_model* m, int n, size_t* bytes) {
       if (bytes) *bytes = srcfd::lowp16_workspace_bytes(mm, chunk16);
       return chunk16;
     }
-    int chunk = std::min(std::max(n, 1), M(m)->chunk_cap());
-    if (bytes) *bytes = 2 * (size_t)chunk * M(m)->max_act_elems() * sizeof(float);
+    const srcfd::Switches sw = srcfd::Switches::from_env();
+    int chunk = std::min(std::max(n, 1), mm.chunk_cap(mm.precision, sw));
+    if (bytes) *bytes = 2 * (size_t)chunk * mm.max_act_elems(mm.precision, sw) * sizeof(float);
     return chunk;
   });
 }
@@ -835,8 +831,9 @@ int srcfd_model_footprint(const srcfd_model* m, int n, int precision, size_t byt
       bytes[0] = srcfd::lowp16_workspace_bytes(mm, n);   // lowp16_reserve: two activation buffers + the dense split-K slabs
       bytes[1] = params * (sizeof(float) + 2 * sizeof(uint16_t));   // f32 weights + the 16-bit GEMM layout + fragment re-orderings (upper bound: every layer twice)
     } else {
-      const int chunk = n ? std::min(n, mm.chunk_cap()) : 0;
-      bytes[0] = 2 * (size_t)chunk * mm.max_act_elems() * sizeof(float);
+      const srcfd::Switches sw = srcfd::Switches::from_env();
+      const int chunk = n ? std::min(n, mm.chunk_cap(precision, sw)) : 0;
+      bytes[0] = 2 * (size_t)chunk * mm.max_act_elems(precision, sw) * sizeof(float);
       bytes[1] = params * sizeof(float) * 2 + mm.pack_x3.size() * sizeof(uint16_t);   // packed weights + the per-layer operand orders of the fused f32 kernels (upper bound) + the split-bf16 planes
     }
     const size_t stage = (size_t)std::min(n, Model::STAGE_SAMPLES);
