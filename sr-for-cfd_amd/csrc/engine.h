@@ -194,6 +194,7 @@ void lowp16_plan(Model& m);   // host only: plans the graph; leaves m.lowp16 nul
 int lowp16_init(Model& m);    // device side of a planned graph
 int lowp16_reserve(Model& m, int n);
 size_t lowp16_workspace_bytes(const Model& m, int n);   // what lowp16_reserve(n) allocates for activations and split-K slabs
+int lowp16_chunk_cap(const Model& m);                   // samples per chunk of the 16-bit forward: 1024, fewer where gemm16's 32-bit offsets ask for it
 int lowp16_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype,
                    int flags, unsigned long long* nonfinite, hipStream_t s);
 int fused_debug_read(Model& m, int index, void* dst, size_t bytes);   // the fused graph only

@@ -802,9 +802,9 @@ int srcfd_model_workspace(srcfd_model* m, int n, size_t* bytes) {
   return srcfd::abi_guard("srcfd_model_workspace", [&]() -> int {
     if (!m) { set_error("null model"); return SRCFD_EINVAL; }
     const Model& mm = *M(m);
-    // the 16-bit path's chunks of up to 1024 samples; the fused graph answers with the f32 figures below, as it always has
+    // the 16-bit path's chunks of up to 1024 samples (lowp16_chunk_cap); the fused graph answers with the f32 figures below, as it always has
     if ((mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) && !mm.has_fused && mm.lowp16) {
-      const int chunk16 = std::min(std::max(n, 1), 1024);
+      const int chunk16 = std::min(std::max(n, 1), srcfd::lowp16_chunk_cap(mm));
       if (bytes) *bytes = srcfd::lowp16_workspace_bytes(mm, chunk16);
       return chunk16;
     }

@@ -147,11 +147,14 @@ int fused_debug_read(Model& m, int index, void* dst, size_t bytes) {
 }
 
 // A forward runs chunks of up to 1024 samples through two activation buffers of the graph's largest activation and the split-K
-// slabs of dense (3200 -> 128): up to 16 K-slice slabs of (rows x 128) f32.
-static size_t chunk_of(int n) { return (size_t)std::min(std::max(n, 0), 1024); }
+// slabs of dense (3200 -> 128): up to 16 K-slice slabs of (rows x 128) f32.  gemm16 forms its element offsets into a chunk's
+// activations in 32-bit int, so a chunk holds fewer samples where 1024 of the graph's largest activation would pass 2^31 elements
+// (any16_plan refuses a single activation of that size; the fused graph's 1024 x 160000 is far below).
+int lowp16_chunk_cap(const Model& m) { return (int)std::min<size_t>(1024, (((size_t)1 << 31) - 1) / act_elems(m)); }
+static size_t chunk_of(const Model& m, int n) { return (size_t)std::min(std::max(n, 0), lowp16_chunk_cap(m)); }
 static size_t slab_elems(size_t want) { return 16 * want * 128; }
 size_t lowp16_workspace_bytes(const Model& m, int n) {
-  const size_t want = chunk_of(n);
+  const size_t want = chunk_of(m, n);
   return want ? 2 * want * act_elems(m) * sizeof(uint16_t) + slab_elems(want) * sizeof(float) : 0;
 }
 
@@ -162,7 +165,7 @@ int lowp16_reserve(Model& m, int n) {
   if (!st) { set_error(m.has_fused ? "fused path not initialised" : "any16 path not initialised"); return SRCFD_EINVAL; }
   int rc = build_pack(m, st, m.precision == SRCFD_PREC_F16);
   if (rc) return rc;
-  const int want = (int)chunk_of(n);
+  const int want = (int)chunk_of(m, n);
   if (want > st->cap) {
     m.drop_graph();  // a captured forward holds the old buffers' addresses
     st->cap = 0;
@@ -310,9 +313,11 @@ static int run_gemm(Chunk16& k, const Op16& o, bool use_d1) {
     return k.m.launch(o.name.c_str(), k.s, [&] { return launch_dense1_16(k.f16, d, X, W, bias, Y, k.s); });
   // a narrow op (CI 16 / 32) exists on the any16 graphs only: fused_init refuses CI % 64 != 0
   if (any16_narrow(d)) return k.m.launch(o.name.c_str(), k.s, [&] { return launch_gemm16n(k.f16, d, X, W, o.Kpad, bias, Y, k.s); });
-  // dense layers with few rows and a long K: split K over workgroups (f32 slabs + finish kernel)
+  // dense layers with few rows and a long K: split K over workgroups (f32 slabs + finish kernel).  The finish kernel stores row m
+  // at Y + m OC: a layer with a 1x1 OUTPUT.  One row per sample alone does not say that -- the phase ops of a transposed
+  // convolution on a one-pixel image have it too, and their rows go to (oy0, ox0) of a 2x2 image.
   int splits = 1;
-  if (d.MH == 1 && d.MW == 1 && d.K >= 1024) splits = std::max(1, std::min(16, d.K / 256));
+  if (d.OH == 1 && d.OW == 1 && d.MH == 1 && d.MW == 1 && d.K >= 1024) splits = std::max(1, std::min(16, d.K / 256));
   if (splits > 1 && (size_t)splits * d.M * d.Npad > k.st.d_part.size()) splits = 1;
   return k.m.launch(o.name.c_str(), k.s, [&] { return launch_gemm16(k.f16, d, X, W, o.Kpad, bias, Y, k.st.d_part.get(), splits, k.s); });
 }

@@ -549,6 +549,9 @@ void any16_plan(const ModelDesc& md, const std::vector<Op>& ops, const std::vect
       return no("layer '" + l.name + "': GEMM shape");
     A.max_act = std::max(A.max_act, (size_t)l.out_shape[0] * l.out_shape[1] * (o.layer == 3 ? 64 : l.out_shape[2]));
   }
+  // gemm16 addresses a chunk's activations with 32-bit element offsets: the chunk shrinks with the largest activation
+  // (lowp16_chunk_cap, fused_bf16.hip) and one sample has to fit
+  if (A.max_act >= ((size_t)1 << 31)) return no("an activation of 2^31 elements or more per sample");
   if (P.ops.size() < 4 || P.ops[0].layer != 1 || P.ops[1].layer != 2 || P.ops[2].layer != 3) return no("unexpected plan shape");
   A.out_C = lo.cin; A.out_H = lo.in_shape[0]; A.out_W = lo.in_shape[1]; A.out_bias = lo.bias[0];
   A.ok = true;

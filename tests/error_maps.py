@@ -259,6 +259,39 @@ def output_classes(seg: int = 1, pool_rows: int = 1) -> dict:
     return cl
 
 
+def grid_classes(n: int, H: int, W: int, stacked: int = 1, pool: int = 1, sample_group: int = 1) -> dict:
+    """`output_classes` for any output size, with the batch as an axis: name -> boolean mask over (n, H, W) [sample, row, col], for
+    the graphs of tests/any16_cases.py (`class_rms` / `class_check` then take the error field as d[None]).  No class knows a
+    kernel's tiling; they follow what every stride-2 transposed convolution + 3x3 'same' output convolution has:
+      border/   the two outermost rows and columns on each side (the zero padding of the output convolution, the crop);
+      corner/   the four corners as one class;
+      lattice/  row % 2 x col % 2, the output phases of the last transposed convolution, and % 4 where `stacked` = 2 of them;
+      single/   every row and column, pooled in groups of `pool`;
+      sample/   groups of `sample_group` consecutive samples: the last one rides in the GEMMs' last, partial 128-row tile."""
+    r = np.arange(H)[:, None] * np.ones((1, W), int)
+    c = np.arange(W)[None, :] * np.ones((H, 1), int)
+    cl = {}
+    for k in range(min(2, H // 2)):
+        cl[f"border/row_{k}"], cl[f"border/row_{H - 1 - k}"] = r == k, r == H - 1 - k
+    for k in range(min(2, W // 2)):
+        cl[f"border/col_{k}"], cl[f"border/col_{W - 1 - k}"] = c == k, c == W - 1 - k
+    cl["corner/all_four"] = ((r == 0) | (r == H - 1)) & ((c == 0) | (c == W - 1))
+    for mod in (2, 4)[:stacked]:
+        for a in range(mod):
+            for b in range(mod):
+                cl[f"lattice/row%{mod}=={a},col%{mod}=={b}"] = (r % mod == a) & (c % mod == b)
+    for k in range(0, H, pool):
+        cl[f"single/row_{k}" if pool == 1 else f"single/row_{k}-{min(k + pool, H) - 1}"] = (r >= k) & (r < k + pool)
+    for k in range(0, W, pool):
+        cl[f"single/col_{k}" if pool == 1 else f"single/col_{k}-{min(k + pool, W) - 1}"] = (c >= k) & (c < k + pool)
+    cl = {k: np.broadcast_to(m, (n, H, W)) for k, m in cl.items()}
+    s = np.arange(n)[:, None, None] * np.ones((1, H, W), int)
+    starts = list(range(0, n - n % sample_group, sample_group)) or [0]      # a short remainder joins the last group
+    for k, hi in zip(starts, starts[1:] + [n]):
+        cl[f"sample/{k}" if hi - k == 1 else f"sample/{k}-{hi - 1}"] = (s >= k) & (s < hi)
+    return cl
+
+
 def activation_classes(h: int, w: int, ch: int) -> dict:
     """name -> boolean mask over (h, w, ch) for an intermediate activation (ConvT#1: 50x50x64; ConvT#0: 25x25x128)."""
     r = np.arange(h)[:, None, None] * np.ones((1, w, ch), int)

@@ -228,3 +228,85 @@ def forward_specs_lowp(specs, x, kind="bf16"):
             h = rs(h) if swish else r(h)
         prev_swish = swish
     return h
+
+
+def forward_specs_lowp2(specs, x, kind="bf16"):
+    """The second emulation of a spec graph (error_maps.second_emulation, which is written for encoder_10 + decoder_400, on any
+    graph `forward_specs_lowp` takes): the same roundings of weights and of the activations handed from layer to layer, and only
+    what the device is allowed to differ in differs -- float32 accumulation one product at a time in a permuted channel order
+    (error_maps._mm_seq), taps in reverse order, bias first, exp2 / reciprocal a few ulp off (error_maps._swish).  As on the
+    device, a swish layer's sum arrives scaled by log2(e) (its weights and bias carry the factor) and its stored output keeps it."""
+    import error_maps as em
+    from oracle import sr_oracle_lowp as lp
+    f32 = np.float32
+    LOG2E = lp.LOG2E
+    rnd = lp.round_bf16 if kind == "bf16" else lp.round_f16
+    rng = np.random.default_rng(77)
+    q = lambda w: rnd(np.asarray(w, f32))
+    q_div = lambda w: rnd((np.asarray(w, np.float64) / LOG2E).astype(f32))
+    q_mul = lambda w: rnd((np.asarray(w, np.float64) * LOG2E).astype(f32))
+
+    def conv_same(a, w, b, stride, same):
+        n, h, wd, _ = a.shape
+        kh, kw, _, cout = w.shape
+        if same:
+            oh, pt, pb = oracle.same_padding(h, kh, stride)
+            ow, pl, pr = oracle.same_padding(wd, kw, stride)
+            a = np.pad(np.asarray(a, f32), ((0, 0), (pt, pb), (pl, pr), (0, 0)))
+        else:
+            oh, ow = (h - kh) // stride + 1, (wd - kw) // stride + 1
+        out = np.zeros((n, oh, ow, cout), f32) + b
+        for ky in reversed(range(kh)):
+            for kx in reversed(range(kw)):
+                out += em._mm_seq(a[:, ky:ky + (oh - 1) * stride + 1:stride, kx:kx + (ow - 1) * stride + 1:stride], w[ky, kx])
+        return out
+
+    def conv_t(a, w, b, stride, same):
+        n, h, wd, _ = a.shape
+        kh, kw, cout, _ = w.shape
+        out = np.zeros((n, (h - 1) * stride + kh, (wd - 1) * stride + kw, cout), f32) + b
+        for ky in reversed(range(kh)):
+            for kx in reversed(range(kw)):
+                out[:, ky:ky + (h - 1) * stride + 1:stride, kx:kx + (wd - 1) * stride + 1:stride] += em._mm_seq(a, w[ky, kx].T)
+        if same:
+            py, px = convt_pb(kh, stride), convt_pb(kw, stride)
+            out = out[:, py:py + h * stride, px:px + wd * stride]
+        return out
+
+    weighted = [i for i, s in enumerate(specs) if "w" in s]
+    h = np.asarray(x, f32)
+    prev_swish = False
+    for i, s in enumerate(specs):
+        kind_ = s["kind"]
+        if kind_ == "flatten":
+            h = h.reshape(h.shape[0], 1, 1, -1)
+            continue
+        if kind_ == "reshape":
+            h = h.reshape((h.shape[0],) + tuple(s["shape"]))
+            continue
+        swish = s.get("act", "linear") in ("swish", "silu")
+        first = i == weighted[0]
+        if first:
+            w = np.asarray(s["w"], f32)          # a vector kernel in f32 on unrounded weights; the factor goes onto the sum
+        elif prev_swish and not swish:
+            w = q_div(s["w"])
+        elif swish and not prev_swish:
+            w = q_mul(s["w"])
+        else:
+            w = q(s["w"])
+        b = np.asarray(s["b"], f32) * (f32(LOG2E) if swish and not first else f32(1))
+        st = int(s.get("stride", 1))
+        if kind_ == "dense":
+            pre = (em._mm_seq(h.reshape(h.shape[0], -1), w) + b).reshape(h.shape[0], 1, 1, -1)
+        elif kind_ == "conv2d":
+            pre = conv_same(h, w, b, st, bool(s.get("same")))
+        elif kind_ == "conv2d_transpose":
+            pre = conv_t(h, w, b, st, bool(s.get("same")))
+        else:
+            raise ValueError(kind_)
+        if swish:
+            h = rnd(em._swish(pre * f32(LOG2E) if first else pre, rng, True))
+        else:
+            h = pre if i == weighted[-1] else rnd(pre)
+        prev_swish = swish
+    return h.astype(np.float64) / (LOG2E if prev_swish else 1.0)
