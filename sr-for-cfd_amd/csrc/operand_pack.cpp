@@ -661,4 +661,88 @@ GatherMap gather_map(const std::vector<float>& ipack, const std::vector<float>& 
   return g;
 }
 
+std::vector<TrainOp> train_ops(const std::vector<Op>& iops, const std::vector<LayerInfo>& layers) {
+  std::vector<TrainOp> ops;
+  for (const Op& op : iops) {
+    TrainOp to{op.d, op.w_off, op.b_off, -1};
+    to.fwd.act = SRCFD_ACT_LINEAR;
+    for (size_t k = 0; k < layers.size(); ++k) if (layers[k].desc_index == op.layer) to.layer = (int)k;
+    ops.push_back(to);
+  }
+  return ops;
+}
+
+bool wgrad_is_n1_k72(const GemmDesc& d) { return d.N == 1 && d.TY == 3 && d.TX == 3 && d.CI == 8 && d.nphx == 1; }
+
+WgradPlan wgrad_plan(const GemmDesc& d) {
+  WgradPlan p;
+  if (wgrad_is_n1_k72(d)) {
+    p = WgradPlan{0, 0, 1, 1, 3, 1, 0, 0};
+    p.nslices = (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)d.M + 1023) / 1024));
+    p.rps = (d.M + p.nslices - 1) / p.nslices;
+    p.nslices = std::max(1, (d.M + p.rps - 1) / p.rps);
+    return p;
+  }
+  p.ktiles = (d.K + 1 + 31) / 32;
+  p.ntiles = d.Npad / 32;
+  p.KG = p.ktiles >= 2 ? 2 : 1;
+  p.NG = p.ntiles >= 3 ? 4 : (p.ntiles == 2 ? 2 : 1);
+  p.kblocks = (p.ktiles + p.KG - 1) / p.KG;
+  p.nblocks = (p.ntiles + p.NG - 1) / p.NG;
+  const int64_t blocks = (int64_t)p.kblocks * p.nblocks, chunks = std::max<int64_t>(1, ((int64_t)d.M + WG_RC - 1) / WG_RC);
+  int64_t want = std::max<int64_t>(1, std::min<int64_t>(chunks, 512 / blocks));
+  p.rps = (int)(((chunks + want - 1) / want) * WG_RC);
+  p.nslices = (int)std::max<int64_t>(1, ((int64_t)d.M + p.rps - 1) / p.rps);
+  return p;
+}
+
+StepPlan plan_step(const std::vector<TrainOp>& ops, int Lg, int n, int tail_slabs) {
+  StepPlan P;
+  P.part_floats.assign(ops.size(), 0);
+  auto add = [&P](int op, const WgradPlan& wp, int64_t elems, int nslices) {
+    SlabSum e{};
+    e.op = op; e.wp = wp; e.elems = elems; e.nslices = nslices;
+    e.groups = finish_groups(nslices);
+    e.block0 = P.blocks;
+    const int epb = 256 / e.groups;   // consecutive elements per workgroup
+    P.blocks += (int)((elems + epb - 1) / epb);
+    P.sums.push_back(e);
+  };
+  if (tail_slabs > 0) add(-1, WgradPlan{}, TT_PARAMS, tail_slabs);
+  for (int li = Lg - 1; li >= 0; --li) {
+    int first = -1;
+    for (size_t i = 0; i < ops.size(); ++i) {
+      if (ops[i].layer != li) continue;
+      GemmDesc d = ops[i].fwd;
+      d.M = n * d.MH * d.MW;
+      const WgradPlan wp = wgrad_plan(d);
+      const int64_t elems = (int64_t)(d.K + 1) * d.Npad;
+      const int me = (int)P.sums.size();
+      add((int)i, wp, elems, wp.nslices);
+      P.part_floats[i] = (size_t)wp.nslices * (size_t)elems;
+      if (first < 0) first = me;
+      else {
+        SlabSum& f0 = P.sums[first];
+        f0.extra[f0.nextra++] = me;
+        P.sums[me].bias_skip = 1;
+      }
+    }
+  }
+  return P;
+}
+
+SlabSpace plan_slab_space(const std::vector<TrainOp>& ops, int Lg, int max_batch) {
+  SlabSpace S;
+  S.cap.assign(ops.size(), 0);
+  for (int b = 1; b <= max_batch; ++b) {
+    const StepPlan P = plan_step(ops, Lg, b, 0);
+    for (size_t i = 0; i < ops.size(); ++i) S.cap[i] = std::max(S.cap[i], P.part_floats[i]);
+  }
+  for (size_t i = 0; i < ops.size(); ++i) {   // space of its own: the sum of one op never has to finish before the next op's slabs are written
+    S.off.push_back(S.total);
+    S.total += (S.cap[i] + 63) / 64 * 64;
+  }
+  return S;
+}
+
 }  // namespace srcfd

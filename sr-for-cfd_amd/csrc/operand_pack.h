@@ -1,8 +1,11 @@
 // Host-side operand packing: every layout a kernel reads its weights in, as pure functions from the layer graph to host vectors
 // and offsets.  These layouts are the contract between host and kernel.  No HIP runtime calls in this unit: engine.hip (plan_*),
 // fused_bf16.hip (lowp16_plan, build_pack: both 16-bit graphs through plan16 / pack_wt16 / pack_enc16), train_tail.hip
-// (train_tail_plan) and train.hip (trainer_build) decide what qualifies and upload what these functions return;
-// tools/pack_digest.cpp links the same functions on a CPU and tests/test_operand_pack.py pins their bytes.
+// (train_tail_plan) and train.hip (trainer_build) decide what qualifies and upload what these functions return.  The trainer's
+// launch arithmetic lives here too: the grid of every weight-gradient launch, the table of the step's one slab-sum launch and the
+// slab space it needs (plan_step, plan_slab_space); trainer_build sizes from it, trainer_step issues from it.
+// tools/pack_digest.cpp links the same functions on a CPU; tests/test_operand_pack.py pins the packs' bytes, tests/test_train_plan.py
+// checks the step plan against an independent statement of it.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -126,5 +129,42 @@ std::vector<int> wgrad_gmap(const Op& op, const std::vector<float>& ipack);
 // The trainer's gather map [forward operands | data-gradient operands | the fused tail's slots], every part 64-aligned
 struct GatherMap { std::vector<int> map; size_t dpack_off = 0, dpack_elems = 0, tail_off = 0; };
 GatherMap gather_map(const std::vector<float>& ipack, const std::vector<float>& dpack, const std::vector<int>* tail_map);
+
+// ---- trainer: a step's weight-gradient launches and slab sums (kernels: train.hip wgrad_f32, wgrad_n1_k72_f32, wgrad_finish_all_f32) ----
+// a forward GEMM of the step: descriptor (act forced linear, M filled per call), offsets into the packed forward buffer, compute-layer ordinal
+struct TrainOp { GemmDesc fwd; size_t w_off, b_off; int layer; };
+std::vector<TrainOp> train_ops(const std::vector<Op>& iops, const std::vector<LayerInfo>& layers);
+// end of the run of ops that share ops[i].layer: the output phases of a strided transposed convolution, at most four (trainer_build)
+template <class T> size_t layer_end(const std::vector<T>& ops, size_t i) {
+  size_t j = i;
+  while (j < ops.size() && ops[j].layer == ops[i].layer) ++j;
+  return j;
+}
+constexpr int WG_RC = 64;   // rows of one chunk of wgrad_f32
+// grid of one weight-gradient launch; KG == 0: wgrad_n1_k72_f32, one slab per workgroup.  rps: rows per slice (slab)
+struct WgradPlan { int KG, NG, kblocks, nblocks, ktiles, ntiles, nslices, rps; };
+bool wgrad_is_n1_k72(const GemmDesc& d);
+WgradPlan wgrad_plan(const GemmDesc& d);   // d.M set
+// slab groups one workgroup of wgrad_finish_all_f32 adds side by side, from the slab count
+inline int finish_groups(int nslices) { return nslices >= 256 ? 32 : (nslices >= 64 ? 8 : (nslices >= 8 ? 4 : 1)); }
+constexpr int MAX_FINISH_OPS = 24;   // slots of the slab-sum table, a kernel argument
+// One slot of the table.  The first op of a layer sums the bias rows of the others (`extra`: their slots, op order), which skip theirs.
+struct SlabSum {
+  int op;            // index into the ops; -1: the fused tail's slabs (one column of TT_PARAMS slots, no bias row)
+  WgradPlan wp;      // of that op at this batch
+  int64_t elems;     // floats of one slab: (K + 1) x Npad
+  int nslices, groups, block0;   // block0: first workgroup of this slot in the one launch
+  int bias_skip, nextra, extra[3];
+};
+// The slab sums of a step on n samples, in table order: the fused tail's `tail_slabs` slabs if any (0: no fused tail), then the
+// layers Lg - 1 .. 0 that run layer by layer, each layer's ops in op order.  block0 ascends: the kernel finds its slot by it.
+// Which stream launches a layer's weight gradients (SRCFD_TRAIN_AUX_FROM) does not enter: either way the layers are visited from
+// the last down.  trainer_build refuses graphs with more than four ops in a layer or more slots than MAX_FINISH_OPS.
+struct StepPlan { std::vector<SlabSum> sums; int blocks = 0; std::vector<size_t> part_floats; };   // workgroups in all; per op, the floats of its slabs
+StepPlan plan_step(const std::vector<TrainOp>& ops, int Lg, int n, int tail_slabs);
+// Every op's own slab space (64-float aligned offsets): the most it needs at any batch 1 .. max_batch -- the slab count is not
+// monotonic in the batch (ConvT#4 of decoder_400: 313, 417, 469, 500, 447, 469, 487, 500 slabs at 1 .. 8 samples)
+struct SlabSpace { std::vector<size_t> off, cap; size_t total = 0; };
+SlabSpace plan_slab_space(const std::vector<TrainOp>& ops, int Lg, int max_batch);
 
 }  // namespace srcfd

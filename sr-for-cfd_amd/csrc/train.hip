@@ -124,14 +124,13 @@ __global__ void __launch_bounds__(256) adam_f32(float* __restrict__ p, const flo
 // The reduction runs over the rows m (pixels), so m is the MFMA's k dimension:
 // v_mfma_f32_32x32x2_f32 with a = A[m..m+1][32 k's], b = dZ[m..m+1][32 n's].
 // A block owns KG x NG tiles of 32x32 (k x n) and one slice of the rows; it walks the slice in
-// chunks of 64 rows: the implicit-GEMM A tile [64][32 KG] and the dZ tile [64][32 NG] are gathered
+// chunks of 64 rows (WG_RC): the implicit-GEMM A tile [64][32 KG] and the dZ tile [64][32 NG] are gathered
 // with 16-byte loads into registers one chunk ahead, parked in LDS, and consumed by the 4 waves
 // (tile t -> wave t % 4; with fewer than 4 tiles the waves split the rows of the chunk instead and
 // add their accumulators through LDS in wave order).  Slabs part[slice][k][n] are summed in slab order by wgrad_finish
-// (reproducible: no float atomics), which also scatters into the flat gradient.
+// (reproducible: no float atomics), which also scatters into the flat gradient.  The grid of a launch (WgradPlan) and the table of
+// the slab sums are host arithmetic on the descriptors: operand_pack.cpp, wgrad_plan / plan_step.
 // ---------------------------------------------------------------------------
-constexpr int WG_RC = 64;
-
 template <int KG, int NG>
 __global__ void __launch_bounds__(256) wgrad_f32(GemmDesc d, const float* __restrict__ X, const float* __restrict__ dZ, float* __restrict__ part,
                                                   int rows_per_slice, int kblocks, int ktiles, int ntiles) {
@@ -333,32 +332,6 @@ __global__ void __launch_bounds__(256) wgrad_n1_k72_f32(GemmDesc d, const float*
   if (tid < 73) part[((int64_t)blockIdx.x * 73 + tid) * d.Npad] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-static bool wgrad_is_n1_k72(const GemmDesc& d) { return d.N == 1 && d.TY == 3 && d.TX == 3 && d.CI == 8 && d.nphx == 1; }
-
-struct WgradPlan { int KG, NG, kblocks, nblocks, ktiles, ntiles, nslices, rps; };
-
-static WgradPlan wgrad_plan(const GemmDesc& d) {
-  WgradPlan p;
-  if (wgrad_is_n1_k72(d)) {
-    p = WgradPlan{0, 0, 1, 1, 3, 1, 0, 0};
-    p.nslices = (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)d.M + 1023) / 1024));
-    p.rps = (d.M + p.nslices - 1) / p.nslices;
-    p.nslices = std::max(1, (d.M + p.rps - 1) / p.rps);
-    return p;
-  }
-  p.ktiles = (d.K + 1 + 31) / 32;
-  p.ntiles = d.Npad / 32;
-  p.KG = p.ktiles >= 2 ? 2 : 1;
-  p.NG = p.ntiles >= 3 ? 4 : (p.ntiles == 2 ? 2 : 1);
-  p.kblocks = (p.ktiles + p.KG - 1) / p.KG;
-  p.nblocks = (p.ntiles + p.NG - 1) / p.NG;
-  const int64_t blocks = (int64_t)p.kblocks * p.nblocks, chunks = std::max<int64_t>(1, ((int64_t)d.M + WG_RC - 1) / WG_RC);
-  int64_t want = std::max<int64_t>(1, std::min<int64_t>(chunks, 512 / blocks));
-  p.rps = (int)(((chunks + want - 1) / want) * WG_RC);
-  p.nslices = (int)std::max<int64_t>(1, ((int64_t)d.M + p.rps - 1) / p.rps);
-  return p;
-}
-
 static void launch_wgrad(const GemmDesc& d, const WgradPlan& p, const float* X, const float* dZ, float* part, hipStream_t s) {
   if (p.KG == 0) {
     hipLaunchKernelGGL(wgrad_n1_k72_f32, dim3(p.nslices), dim3(256), 0, s, d, X, dZ, part, p.rps);
@@ -379,14 +352,13 @@ static void launch_wgrad(const GemmDesc& d, const WgradPlan& p, const float* X, 
 // path.  The table travels as a kernel argument (it depends on the batch size through the slab counts).
 // Ops of one layer (the output phases of a strided transposed convolution) own disjoint kernel taps but share the layer's bias:
 // the first op of the layer sums the bias rows of the others after its own (`extra`, fixed order), the others skip theirs
-// (`bias_skip`) -- every parameter is written by exactly one thread of one launch (round 3 ran one launch per phase ordinal, the
+// (`bias_skip`; plan_step decides both) -- every parameter is written by exactly one thread of one launch (round 3 ran one launch per phase ordinal, the
 // later ones adding into the first one's biases: three more launches of 5 us at the end of every step).
 struct FinishOp {
   const float* part; const int* map; int64_t elems;
   int nslices, K, N, Npad, CO, groups, block0;   // block0: first workgroup of this op in the merged grid
   int bias_skip, nextra, extra[3];               // extra: table indices of the layer's other ops
-};
-constexpr int MAX_FINISH_OPS = 24;
+};   // a SlabSum of the step's plan + the device pointers and the columns of its op
 struct FinishTable { FinishOp op[MAX_FINISH_OPS]; int nops; int overwrite; };   // overwrite: grads = sum instead of grads += sum
 
 __global__ void __launch_bounds__(256) wgrad_finish_all_f32(const FinishTable tab, float* __restrict__ grads) {
@@ -448,21 +420,14 @@ __global__ void __launch_bounds__(256) wgrad_finish_all_f32(const FinishTable ta
 // ---------------------------------------------------------------------------
 // trainer
 // ---------------------------------------------------------------------------
-struct TrainOp {
-  GemmDesc fwd;           // forward descriptor (act forced linear)
-  size_t w_off, b_off;    // into the packed forward buffer (same layout as Model::pack)
-  int layer;              // compute-layer ordinal
-  std::vector<int> gmap;  // (K+1) x Npad -> flat param index + 1 (0: padding)
-  DevBuf<int> d_gmap;
-  size_t part_off = 0, part_cap = 0;   // this op's own slab space in Trainer::d_part (floats)
-};
-
 struct Trainer {
   int device = 0;
   int max_batch = 0;
   ModelDesc desc;                 // own copy (shapes)
   std::vector<LayerInfo> layers;  // compute layers
-  std::vector<TrainOp> ops;
+  std::vector<TrainOp> ops;          // forward GEMMs (operand_pack.h)
+  std::vector<DevBuf<int>> d_gmap;   // per op: (K+1) x Npad -> flat param index + 1 (0: padding)
+  SlabSpace slabs;                   // per op: its own slab space in d_part (floats)
   std::vector<DgradOp> dops;
   int64_t n_params = 0;
   std::vector<float> init_params;
@@ -530,6 +495,12 @@ struct Trainer {
   ~Trainer() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }   // then the members' destructors (device_mem.h)
 };
 
+// a switch of the trainer: unset or any non-zero value means on
+static bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
+
 static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   t.device = model.device;
   t.max_batch = max_batch;
@@ -546,11 +517,11 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   std::vector<Op> iops;
   std::vector<float> ipack;
   build_plan(im, iops, ipack);
-  // Refused here, before anything runs: the step groups the GEMMs of one layer four at a time and the slab sums give a layer at
+  // Refused here and nowhere else, before anything runs: the step groups the GEMMs of one layer four at a time and the slab sums give a layer at
   // most four ops (a strided transposed convolution whose kernel is not its stride plans into stride^2 output phases, e.g. 9 for
-  // stride 3), and the slab-sum table holds MAX_FINISH_OPS ops (+1 for the fused tail's slabs).
+  // stride 3; SlabSum::extra names the other three), and the slab-sum table holds MAX_FINISH_OPS ops (+1 for the fused tail's slabs).
   for (size_t i = 0, j = 0; i < iops.size(); i = j) {
-    while (j < iops.size() && iops[j].layer == iops[i].layer) ++j;
+    j = layer_end(iops, i);
     if (j - i > 4) {
       set_error("training: layer '" + im.layers[iops[i].layer].name + "' plans into " + std::to_string(j - i) + " GEMMs; at most four per layer");
       return SRCFD_EINVAL;
@@ -563,8 +534,7 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     std::vector<int> di; std::vector<size_t> ko, bo;
     for (const LayerInfo& L : t.layers) { di.push_back(L.desc_index); ko.push_back(L.kernel_off); bo.push_back(L.bias_off); }
     train_tail_plan(t.desc, di.data(), ko.data(), bo.data(), (int)t.layers.size(), t.tail);
-    const char* e = getenv("SRCFD_TRAIN_TAIL");
-    t.use_tail = t.tail.ok && !(e && atoi(e) == 0) && (uint64_t)max_batch * t.tail.H * t.tail.W * t.tail.H * t.tail.W < (1ull << 32);
+    t.use_tail = t.tail.ok && env_on("SRCFD_TRAIN_TAIL") && (uint64_t)max_batch * t.tail.H * t.tail.W * t.tail.H * t.tail.W < (1ull << 32);
   }
   if (t.use_tail) {
     std::vector<int> gm(TT_PARAMS);
@@ -574,36 +544,19 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     if (!rc) rc = t.d_tail_gmap.upload(gm);
     if (rc) return rc;
   }
-  size_t part_need = 0;   // every op has slab space of its own: the sum of one op never has to finish before the next op's slabs are written
+  t.ops = train_ops(iops, t.layers);
   for (const Op& op : iops) {
-    TrainOp to;
-    to.fwd = op.d;
-    to.fwd.act = SRCFD_ACT_LINEAR;
-    to.w_off = op.w_off; to.b_off = op.b_off;
-    int ci = -1;
-    for (size_t k = 0; k < t.layers.size(); ++k) if (t.layers[k].desc_index == op.layer) ci = (int)k;
-    to.layer = ci;
-    const GemmDesc& d = op.d;
-    to.gmap = wgrad_gmap(op, ipack);
-    int rc = to.d_gmap.upload(to.gmap);
+    t.d_gmap.emplace_back();
+    const int rc = t.d_gmap.back().upload(wgrad_gmap(op, ipack));
     if (rc) return rc;
-    size_t op_need = 1;
-    for (int b = 1; b <= max_batch; ++b) {  // the slab count is not monotonic in the batch
-      GemmDesc db = d;
-      db.M = b * d.MH * d.MW;
-      WgradPlan wp = wgrad_plan(db);
-      op_need = std::max(op_need, (size_t)wp.nslices * to.gmap.size());
-    }
-    to.part_off = part_need;
-    to.part_cap = op_need;
-    part_need += (op_need + 63) / 64 * 64;
-    t.ops.push_back(std::move(to));
   }
-  int rc = t.d_part.alloc(part_need);
+  // slab space and the step's launches come from one plan (plan_step): what is sized here is what trainer_step issues
+  const int Lg = t.use_tail ? t.tail.first_layer : (int)t.layers.size();   // layers [0, Lg) run layer by layer
+  t.slabs = plan_slab_space(t.ops, Lg, max_batch);
+  int rc = t.d_part.alloc(t.slabs.total);
   if (rc) return rc;
   {
-    const char* e = getenv("SRCFD_TRAIN_ENC");
-    bool ok = !(e && atoi(e) == 0) && t.ops.size() >= 5 && t.layers.size() >= 4;
+    bool ok = env_on("SRCFD_TRAIN_ENC") && t.ops.size() >= 5 && t.layers.size() >= 4;
     for (int i = 0; ok && i < 4; ++i) ok = t.ops[i].layer == i;                 // one op per layer, the first four layers
     ok = ok && t.ops[4].layer != 3 && train_enc_qualifies(t.ops[0].fwd, t.ops[1].fwd, t.ops[2].fwd, t.ops[3].fwd);
     t.use_enc = ok;
@@ -638,7 +591,6 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     }
   }
   {
-    const int Lg = t.use_tail ? t.tail.first_layer : (int)t.layers.size();
     t.dz.resize(Lg);
     for (int li = 0; li < Lg && !rc; ++li) rc = t.dz[li].alloc((size_t)max_batch * t.layers[li].out_elems);
     if (!rc && t.use_tail) rc = t.d_dpred.alloc((size_t)max_batch * t.layers.back().out_elems);
@@ -646,9 +598,9 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
     const char* e = getenv("SRCFD_TRAIN_AUX_FROM");
     t.aux_from = e ? std::max(atoi(e), 0) : std::max(Lg - 4, 0);
   }
-  { const char* e = getenv("SRCFD_TRAIN_OVERLAP"); t.overlap = !(e && atoi(e) == 0); }
-  { const char* e = getenv("SRCFD_TRAIN_GRAPH"); t.use_graph = !(e && atoi(e) == 0); }
-  { const char* e = getenv("SRCFD_TRAIN_FUSE"); t.fuse_epilogues = !(e && atoi(e) == 0); }
+  t.overlap = env_on("SRCFD_TRAIN_OVERLAP");
+  t.use_graph = env_on("SRCFD_TRAIN_GRAPH");
+  t.fuse_epilogues = env_on("SRCFD_TRAIN_FUSE");
   if (t.use_graph) {
     t.x_elems = t.layers.front().in_elems; t.y_elems = t.layers.back().out_elems;
     rc = t.d_xs.alloc((size_t)max_batch * t.x_elems);
@@ -665,13 +617,11 @@ static int trainer_build(Trainer& t, const Model& model, int max_batch) {
   if (rc) return rc;
   size_t sk = 0;
   for (int b = 1; b <= max_batch; ++b) {
-    for (size_t i = 0; i < t.ops.size();) {  // the forward GEMMs of one layer are launched together: their slabs coexist
+    for (size_t i = 0, j = 0; i < t.ops.size(); i = j) {  // the forward GEMMs of one layer are launched together: their slabs coexist
       GemmDesc ds[4];
-      int cnt = 0;
-      size_t j = i;
-      for (; j < t.ops.size() && t.ops[j].layer == t.ops[i].layer && cnt < 4; ++j) { ds[cnt] = t.ops[j].fwd; ds[cnt].M = b * ds[cnt].MH * ds[cnt].MW; ++cnt; }
-      sk = std::max(sk, gemm_group_ws_floats(ds, cnt, false));
-      i = j;
+      j = layer_end(t.ops, i);
+      for (size_t q = i; q < j; ++q) { ds[q - i] = t.ops[q].fwd; ds[q - i].M = b * ds[q - i].MH * ds[q - i].MW; }
+      sk = std::max(sk, gemm_group_ws_floats(ds, (int)(j - i), false));
     }
     for (const DgradOp& op : t.dops) { GemmDesc d = op.d; d.M = b * d.MH * d.MW; sk = std::max(sk, gemm_splitk_ws_floats(d, false)); }
   }
@@ -711,18 +661,17 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     HIPCHECK(launch_train_enc(q, s));
     i0 = 4;
   }
-  for (size_t i = i0; i < t.ops.size();) {
+  for (size_t i = i0, j; i < t.ops.size(); i = j) {
     const TrainOp& op = t.ops[i];
     if (op.layer >= Lg) break;
     GemmDesc ds[4];
     const float* Bs[4];
     const float* biases[4];
-    int cnt = 0;
-    size_t j = i;
-    for (; j < t.ops.size() && t.ops[j].layer == op.layer && cnt < 4; ++j) {  // ConvT output phases: one launch
-      ds[cnt] = t.ops[j].fwd; ds[cnt].M = n * ds[cnt].MH * ds[cnt].MW;
-      Bs[cnt] = t.d_pack.get() + t.ops[j].w_off; biases[cnt] = t.d_pack.get() + t.ops[j].b_off;
-      ++cnt;
+    j = layer_end(t.ops, i);
+    const int cnt = (int)(j - i);
+    for (int q = 0; q < cnt; ++q) {  // ConvT output phases: one launch
+      ds[q] = t.ops[i + q].fwd; ds[q].M = n * ds[q].MH * ds[q].MW;
+      Bs[q] = t.d_pack.get() + t.ops[i + q].w_off; biases[q] = t.d_pack.get() + t.ops[i + q].b_off;
     }
     const float* X = op.layer == 0 ? x : t.y(op.layer - 1);
     // swish layers: the GEMM epilogue stores both Z and swish(Z) (EpiAux mode 1) when every GEMM of the layer takes it
@@ -731,9 +680,7 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     EpiAux aux;
     if (fuse) { aux.mode = 1; aux.y2 = t.y(op.layer); }
     HIPCHECK(launch_gemm_mfma_group(ds, cnt, X, Bs, biases, t.Z[op.layer].get(), s, t.d_splitk.get(), t.d_splitk.size(), false, aux));
-    i = j;
-    const bool last_of_layer = i == t.ops.size() || t.ops[i].layer != op.layer;
-    if (last_of_layer && t.layers[op.layer].swish && !fuse) {
+    if (t.layers[op.layer].swish && !fuse) {
       int64_t e = (int64_t)n * t.layers[op.layer].out_elems;
       hipLaunchKernelGGL(swish_fwd_f32, grid(e), dim3(256), 0, s, t.Z[op.layer].get(), t.y(op.layer), e);
     }
@@ -759,9 +706,24 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   // 4. backward.  Main stream: [tail_bwd32 ->] swish' -> data gradient -> swish' -> ... (the dependent chain), then the weight
   //    gradients of the layers below aux_from; second stream, forked ONCE (when dZ of layer aux_from exists): the weight
   //    gradients of the layers from aux_from up, and the sum of the loss partials (nobody on the chain needs it).
+  //    The weight-gradient grids and the slab-sum table are planned here in one go (plan_step: host integer arithmetic; a replayed
+  //    graph never comes back here); trainer_build sized every op's slab space from the same plan.
+  const StepPlan plan = plan_step(t.ops, Lg, n, t.use_tail ? tail_bwd32_blocks(n, t.tail.H, t.tail.W, t.num_cus) : 0);
   FinishTable ftab;
-  ftab.nops = 0; ftab.overwrite = overwrite;
-  int fblocks = 0;                                     // workgroups of the merged slab-sum launch so far
+  ftab.nops = (int)plan.sums.size(); ftab.overwrite = overwrite;
+  for (int q = 0; q < ftab.nops; ++q) {
+    const SlabSum& e = plan.sums[q];
+    FinishOp& fo = ftab.op[q];
+    if (e.op < 0) {   // the fused tail: one column, no bias row: every slot is a parameter of its own
+      fo.part = t.d_tail_slabs.get(); fo.map = t.d_tail_gmap.get(); fo.K = 0x7fffffff; fo.N = 1; fo.Npad = 1; fo.CO = 1;
+    } else {
+      const GemmDesc& d = t.ops[e.op].fwd;
+      fo.part = t.d_part.get() + t.slabs.off[e.op]; fo.map = t.d_gmap[e.op].get(); fo.K = d.K; fo.N = d.N; fo.Npad = d.Npad; fo.CO = d.CO;
+    }
+    fo.elems = e.elems; fo.nslices = e.nslices; fo.groups = e.groups; fo.block0 = e.block0;
+    fo.bias_skip = e.bias_skip; fo.nextra = e.nextra;
+    for (int x = 0; x < e.nextra; ++x) fo.extra[x] = e.extra[x];
+  }
   bool dz_done = false;  // the data-gradient GEMM below already multiplied by swish'(Z) of the layer it feeds (EpiAux mode 2)
   const int aux_from = (t.overlap && t.aux_from < Lg) ? t.aux_from : Lg;   // Lg: everything on the caller's stream
   bool sse_pending = sse_dev != nullptr;
@@ -772,43 +734,15 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     q.n = n; q.H = t.tail.H; q.W = t.tail.W;
     HIPCHECK(launch_tail_bwd32(q, t.num_cus, s));
     dz_done = true;
-    FinishOp& fo = ftab.op[ftab.nops++];
-    fo.part = t.d_tail_slabs.get(); fo.map = t.d_tail_gmap.get(); fo.elems = TT_PARAMS; fo.nslices = tail_bwd32_blocks(n, q.H, q.W, t.num_cus);
-    fo.K = 0x7fffffff; fo.N = 1; fo.Npad = 1; fo.CO = 1;   // one column, no bias row: every slot is a parameter of its own
-    fo.groups = fo.nslices >= 256 ? 32 : (fo.nslices >= 64 ? 8 : (fo.nslices >= 8 ? 4 : 1));
-    fo.block0 = fblocks; fo.bias_skip = 0; fo.nextra = 0;
-    fblocks += (TT_PARAMS + 256 / fo.groups - 1) / (256 / fo.groups);
   }
-  // the weight gradients of layer li on stream st: one wgrad launch per op, the slab sums entered in the table
-  auto wgrad_layer = [&](const int li, hipStream_t st) -> int {
-    const float* X = li == 0 ? x : t.y(li - 1);
-    int first = -1;
-    for (const TrainOp& op : t.ops) {
-      if (op.layer != li) continue;
-      GemmDesc d = op.fwd;
+  // the weight gradients of layer li on stream st: one launch per op of the layer
+  auto wgrad_layer = [&](const int li, hipStream_t st) {
+    for (const SlabSum& e : plan.sums) {
+      if (e.op < 0 || t.ops[e.op].layer != li) continue;
+      GemmDesc d = t.ops[e.op].fwd;
       d.M = n * d.MH * d.MW;
-      const WgradPlan wp = wgrad_plan(d);
-      const int64_t elems = (int64_t)(d.K + 1) * d.Npad;
-      if ((size_t)wp.nslices * elems > op.part_cap) { set_error("training: gradient slab buffer too small"); return SRCFD_EINVAL; }
-      float* part = t.d_part.get() + op.part_off;
-      launch_wgrad(d, wp, X, t.dz[li].get(), part, st);
-      const int groups = wp.nslices >= 256 ? 32 : (wp.nslices >= 64 ? 8 : (wp.nslices >= 8 ? 4 : 1)), epb = 256 / groups;
-      if (ftab.nops >= MAX_FINISH_OPS) { set_error("training: more weight-gradient ops than the finish table holds"); return SRCFD_EINVAL; }
-      const int me = ftab.nops++;
-      FinishOp& fo = ftab.op[me];
-      fo.part = part; fo.map = op.d_gmap.get(); fo.elems = elems; fo.nslices = wp.nslices; fo.K = d.K; fo.N = d.N; fo.Npad = d.Npad; fo.CO = d.CO;
-      fo.groups = groups; fo.block0 = fblocks; fo.bias_skip = 0; fo.nextra = 0;
-      fblocks += (int)((elems + epb - 1) / epb);
-      // ops of one layer (the output phases of ConvT#0) share the layer's bias: the first one sums the others' bias rows too
-      if (first < 0) first = me;
-      else {
-        FinishOp& f0 = ftab.op[first];
-        if (f0.nextra >= 3) { set_error("training: more than four ops in one layer"); return SRCFD_EINVAL; }
-        f0.extra[f0.nextra++] = me;
-        fo.bias_skip = 1;
-      }
+      launch_wgrad(d, e.wp, li == 0 ? x : t.y(li - 1), t.dz[li].get(), t.d_part.get() + t.slabs.off[e.op], st);
     }
-    return SRCFD_OK;
   };
   for (int li = Lg - 1; li >= 0; --li) {
     float* dZ = t.dz[li].get();
@@ -818,7 +752,7 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     if (li == aux_from) {          // the one fork: dZ of the layers aux_from .. Lg - 1 exist
       HIPCHECK(hipEventRecord(t.ev_fork, s));
       HIPCHECK(hipStreamWaitEvent(t.aux, t.ev_fork, 0));
-      for (int lj = Lg - 1; lj >= aux_from; --lj) { const int rc = wgrad_layer(lj, t.aux); if (rc) return rc; }
+      for (int lj = Lg - 1; lj >= aux_from; --lj) wgrad_layer(lj, t.aux);
       if (sse_pending) { hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, t.aux, t.d_loss_partial.get(), nb, sse_dev, overwrite); sse_pending = false; }
     }
     if (li > 0) {
@@ -830,14 +764,14 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
       HIPCHECK(launch_gemm_mfma(d, dZ, t.d_dpack + dg.w_off, t.d_zero_bias.get(), t.dz[li - 1].get(), s, t.d_splitk.get(), t.d_splitk.size(), false, aux));
     }
   }
-  for (int li = std::min(aux_from, Lg) - 1; li >= 0; --li) { const int rc = wgrad_layer(li, s); if (rc) return rc; }
+  for (int li = std::min(aux_from, Lg) - 1; li >= 0; --li) wgrad_layer(li, s);
   if (sse_pending) hipLaunchKernelGGL(sum_partials_f64, dim3(1), dim3(256), 0, s, t.d_loss_partial.get(), nb, sse_dev, overwrite);
   if (aux_from < Lg) {
     HIPCHECK(hipEventRecord(t.ev_fin, t.aux));
     HIPCHECK(hipStreamWaitEvent(s, t.ev_fin, 0));  // aux is in order: this covers all of its kernels
   }
   // all slabs are written: ONE launch sums them into grads
-  if (ftab.nops > 0) hipLaunchKernelGGL(wgrad_finish_all_f32, dim3((unsigned)fblocks), dim3(256), 0, s, ftab, grads);
+  if (ftab.nops > 0) hipLaunchKernelGGL(wgrad_finish_all_f32, dim3((unsigned)plan.blocks), dim3(256), 0, s, ftab, grads);
   HIPCHECK(hipGetLastError());
   return SRCFD_OK;
 }

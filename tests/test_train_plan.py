@@ -1,0 +1,156 @@
+"""The training step's weight-gradient plan on a CPU (csrc/operand_pack.cpp: wgrad_plan, plan_step, plan_slab_space -- what
+trainer_build sizes its slab space from and trainer_step issues its launches and fills its slab-sum table from).  The
+sanitizer-built harness tools/pack_digest.cpp writes the plan of the SR network (last four layers fused and layer by layer) and of
+its own `convt3` graph (a 3x3 stride-2 ConvT: four output phases sharing one bias) for batches 1 .. 32 into its dump directory;
+the checks compare it with tests/train_plan_ref.py, the statement of the same arithmetic that tests/test_gpu_training_oracle.py
+was written with, and with what wgrad_finish_all_f32 needs of its table.
+
+Which stream launches a layer's weight gradients (SRCFD_TRAIN_AUX_FROM) is no input of the plan: the step visits the layers from
+the last down on either side of the split, so the table is the same for every split (tests/test_training.py runs the splits on the
+device)."""
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from train_plan_ref import gemm_ops, tier, wgrad_slices
+
+BATCHES = (1, 2, 3, 4, 5, 7, 8, 9, 32)
+MAX_BATCHES = (7, 8, 32)
+TT_PARAMS = 10881   # csrc/train_tail.h: parameters of the fused tail's four layers
+
+
+class Plan:
+    """The dump of one graph: ops (train.ops.txt rows joined with the reference's descriptors), entries[(tail, n)] in table
+    order, total[(tail, n)], space[(tail, max_batch)] = per op (capacity, offset)."""
+
+    def __init__(self, dump, tag, specs, in_shape):
+        rows = np.loadtxt(os.path.join(dump, tag + "train.ops.txt"), dtype=np.int64, ndmin=2)   # K N Npad layer nphx
+        ref = gemm_ops(specs, in_shape)
+        assert len(ref) == len(rows)
+        self.ops = []
+        for d, (K, N, Npad, layer, nphx) in zip(ref, rows):
+            assert (d["K"], d["N"], d["nphx"]) == (K, N, nphx) and Npad == -(-N // 32) * 32
+            self.ops.append(dict(d, Npad=int(Npad), elems=int((K + 1) * Npad), layer_index=int(layer)))
+        layer_ids = sorted({o["layer_index"] for o in self.ops})
+        for o in self.ops:
+            o["ordinal"] = layer_ids.index(o["layer_index"])   # compute-layer ordinal
+        self.n_layers = len(layer_ids)
+        self.entries, self.total, self.space = {}, {}, {}
+        for line in open(os.path.join(dump, tag + "train.plan.txt")):
+            kind, *v = line.split()
+            v = [int(x) for x in v]
+            if kind == "E":
+                keys = ("slot", "op", "nslices", "rps", "groups", "block0", "elems", "bias_skip", "nextra")
+                e = dict(zip(keys, v[2:11]), extra=[x for x in v[11:14] if x >= 0])
+                assert e["nextra"] == len(e["extra"]) and e["slot"] == len(self.entries.setdefault((v[0], v[1]), []))
+                self.entries[(v[0], v[1])].append(e)
+            elif kind == "T":
+                self.total[(v[0], v[1])] = v[2]
+            else:
+                assert kind == "S" and v[2] == len(self.space.setdefault((v[0], v[1]), []))
+                self.space[(v[0], v[1])].append((v[3], v[4]))
+        self.tails = sorted({k[0] for k in self.entries})
+
+    def planned_ops(self, tail):
+        """indices of the ops that run layer by layer, in table order: layers from the last down, a layer's ops in op order"""
+        Lg = self.n_layers - 4 if tail else self.n_layers
+        return [i for li in range(Lg - 1, -1, -1) for i, o in enumerate(self.ops) if o["ordinal"] == li]
+
+
+@pytest.fixture(scope="module")
+def plans(srcfd, enc_weights, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("train_plan")
+    h5 = str(tmp / "superres.h5")
+    dec_w = importlib.import_module("sr-for-cfd_amd.synth").synthetic_decoder_weights(1)
+    srcfd.SRModel.from_weights(enc_weights, dec_w, device=-1).save_superres_h5(h5)
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "sr-for-cfd_amd", "csrc"), "pack_digest"], stdout=subprocess.DEVNULL)
+    dump = tmp / "dump"
+    dump.mkdir()
+    out = subprocess.run([os.path.join(ROOT, "sr-for-cfd_amd", "lib", "pack_digest_asan"), h5, str(dump)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-3000:]   # ASan / UBSan clean
+    convt3 = [dict(kind="conv2d_transpose", name="ct", k=3, stride=2, same=False, act="swish", w=np.zeros((3, 3, 4, 8), np.float32), b=np.zeros(4, np.float32))]
+    return {"sr": Plan(str(dump), "", srcfd.layers_from_weights(enc_weights, dec_w), (10, 10, 1)), "convt3": Plan(str(dump), "convt3.", convt3, (4, 4, 8))}
+
+
+def test_the_dump_covers_every_batch_and_both_tails(plans):
+    sr, c3 = plans["sr"], plans["convt3"]
+    assert sr.tails == [0, 1] and c3.tails == [0]
+    assert len(sr.ops) == 14 and [o["TY"] * o["TX"] for o in c3.ops] == [4, 2, 2, 1]
+    for p in plans.values():
+        assert sorted(p.entries) == sorted(p.total) == [(t, n) for t in p.tails for n in BATCHES]
+        assert sorted(p.space) == [(t, mb) for t in p.tails for mb in MAX_BATCHES]
+
+
+def test_entries_match_the_reference_plan(plans):
+    """Every slot's slab count, rows per slab and tier are the reference's for that op and batch; the slots are the layer-by-layer
+    ops in the order the step fills the table, behind the fused tail's slot if there is one."""
+    for name, p in plans.items():
+        for (tail, n), entries in p.entries.items():
+            assert [e["op"] for e in entries] == [-1] * tail + p.planned_ops(tail), (name, tail, n)
+            for e in entries:
+                assert e["groups"] == tier(e["nslices"]), (name, tail, n, e)
+                if e["op"] < 0:
+                    assert e["elems"] == TT_PARAMS and e["nslices"] >= 1 and (e["bias_skip"], e["extra"]) == (0, [])
+                    continue
+                d = p.ops[e["op"]]
+                assert (e["nslices"], e["rps"]) == wgrad_slices(d, n)[:2], (name, tail, n, e)
+                assert e["elems"] == d["elems"]
+
+
+def test_workgroup_ranges_tile_the_launch(plans):
+    """The kernel finds its slot by ascending block0: the ranges follow each other from 0 to the launch's size, each as long as
+    its slot's elements at (256 / groups) elements per workgroup."""
+    for name, p in plans.items():
+        for key, entries in p.entries.items():
+            at = 0
+            for e in entries:
+                assert e["block0"] == at, (name, key, e)
+                at += -(-e["elems"] // (256 // e["groups"]))
+            assert at == p.total[key], (name, key)
+
+
+def test_one_slot_per_layer_owns_the_bias(plans):
+    """Per layer exactly one slot sums the bias (bias_skip == 0), and it lists the layer's other slots in op order; a single-op
+    layer lists none."""
+    for name, p in plans.items():
+        for key, entries in p.entries.items():
+            by_layer = {}
+            for e in entries:
+                if e["op"] >= 0:
+                    by_layer.setdefault(p.ops[e["op"]]["ordinal"], []).append(e)
+            for li, es in by_layer.items():
+                assert [e["op"] for e in es] == sorted(e["op"] for e in es)
+                assert [e["bias_skip"] for e in es] == [0] + [1] * (len(es) - 1), (name, key, li)
+                assert es[0]["extra"] == [e["slot"] for e in es[1:]], (name, key, li)
+                assert all(e["extra"] == [] for e in es[1:])
+    sr0 = plans["sr"].entries[(0, 5)]
+    assert sorted(len(e["extra"]) for e in sr0) == [0] * 13 + [3]   # ConvT#0's four phases
+    assert [len(e["extra"]) for e in plans["convt3"].entries[(0, 3)]] == [3, 0, 0, 0]
+
+
+def test_slab_space_holds_every_batch(plans):
+    """Every op's slab region is 64-float aligned, disjoint from the others and exactly as large as the largest need of any batch
+    up to max_batch -- which is not max_batch's own: decoder_400's ConvT#4 (K = 16, N = 32, 200 x 200 rows per sample) needs
+    313, 417, 469, 500, 447, 469, 487, 500 slabs at 1 .. 8 samples, so a trainer with max_batch = 7 is sized by batch 4."""
+    for name, p in plans.items():
+        for (tail, mb), space in p.space.items():
+            planned = set(p.planned_ops(tail))
+            end = 0
+            for i, (cap, off) in enumerate(space):
+                assert off % 64 == 0 and off >= end, (name, tail, mb, i)
+                end = off + cap
+                need = [wgrad_slices(p.ops[i], b)[0] * p.ops[i]["elems"] if i in planned else 0 for b in range(1, mb + 1)]
+                assert cap == max(need), (name, tail, mb, i, cap, max(need))
+            for n in BATCHES:   # and against the dumped entries themselves
+                if n <= mb:
+                    assert all(e["nslices"] * e["elems"] <= space[e["op"]][0] for e in p.entries[(tail, n)] if e["op"] >= 0)
+    sr = plans["sr"]
+    convt4 = next(i for i, o in enumerate(sr.ops) if (o["K"], o["N"], o["MH"]) == (16, 32, 200))
+    slabs = [wgrad_slices(sr.ops[convt4], b)[0] for b in range(1, 9)]
+    assert slabs == [313, 417, 469, 500, 447, 469, 487, 500]
+    assert int(np.argmax(slabs[:7])) + 1 == 4
+    assert sr.space[(0, 7)][convt4][0] == slabs[3] * sr.ops[convt4]["elems"] > slabs[6] * sr.ops[convt4]["elems"]

@@ -2,7 +2,8 @@
 // model.cpp) the way the engine, the 16-bit path and the trainer do, plus three small graphs built here from a seeded generator,
 // and prints JSON: per named section its offset, length (elements) and sha256.  Built by `make -C sr-for-cfd_amd/csrc pack_digest`
 // with -fsanitize=address,undefined; tests/test_operand_pack.py compares the output with tests/golden/operand_pack_digests.json.
-//   pack_digest <superres.h5> [dump-dir [family.h5]]     dump-dir: raw arrays for the test's property checks
+//   pack_digest <superres.h5> [dump-dir [family.h5]]     dump-dir: raw arrays for the test's property checks, and the training step's
+//   weight-gradient plan as text (dump_train_plan, tests/test_train_plan.py)
 //   family.h5: a whole-model file of another member of the notebook's family (family.py, e.g. encoder_10 + decoder_100, with
 //   padding='same' transposed convolutions); adds `family.*` sections: its f32 plan and the trainer's maps without the fused tail.
 // Which fused kernels a graph qualifies for is decided in engine.hip / fused_bf16.hip / train_tail.hip (HIP translation units this
@@ -132,6 +133,46 @@ static void fused_sections(const ModelDesc& md, const std::vector<Op>& ops, cons
   }
 }
 
+// The trainer's weight-gradient plan (plan_step / plan_slab_space, what trainer_build sizes from and trainer_step issues from) as a
+// text file in the dump directory, for tests/test_train_plan.py; no digest section.  Lines of integers behind a letter:
+//   E tail n slot op nslices rps groups block0 elems bias_skip nextra extra0 extra1 extra2   one slot of the slab-sum table (-1: no extra)
+//   T tail n workgroups                                                                      the whole launch
+//   S tail max_batch op capacity offset                                                      an op's slab space, floats
+// tail = 1: the last four layers fused (their slabs as one slot, op -1), as many slabs as tail_bwd32_blocks (train_tail.hip) gives
+// on 256 CUs -- restated here, the host unit takes the count as a number. 
+static void dump_train_plan(const std::string& tag, const std::vector<Op>& iops, const std::vector<LayerInfo>& layers, int tail_first, int tail_hw) {
+  if (g_dump.empty()) return;
+  const std::vector<TrainOp> ops = train_ops(iops, layers);
+  FILE* f = std::fopen((g_dump + "/" + tag + "train.plan.txt").c_str(), "w");
+  if (!f) std::exit(2);
+  for (int tail = 0; tail <= (tail_first >= 0 ? 1 : 0); ++tail) {
+    const int Lg = tail ? tail_first : (int)layers.size();
+    for (int n : {1, 2, 3, 4, 5, 7, 8, 9, 32}) {
+      const int64_t pairs = (((int64_t)n * tail_hw + 15) / 16 + 1) / 2;
+      const StepPlan P = plan_step(ops, Lg, n, tail ? (int)std::max<int64_t>(1, std::min<int64_t>(pairs, 256)) : 0);
+      for (size_t q = 0; q < P.sums.size(); ++q) {
+        const SlabSum& e = P.sums[q];
+        std::fprintf(f, "E %d %d %zu %d %d %d %d %d %lld %d %d", tail, n, q, e.op, e.nslices, e.wp.rps, e.groups, e.block0, (long long)e.elems, e.bias_skip, e.nextra);
+        for (int x = 0; x < 3; ++x) std::fprintf(f, " %d", x < e.nextra ? e.extra[x] : -1);
+        std::fprintf(f, "\n");
+      }
+      std::fprintf(f, "T %d %d %d\n", tail, n, P.blocks);
+    }
+    for (int mb : {7, 8, 32}) {
+      const SlabSpace S = plan_slab_space(ops, Lg, mb);
+      for (size_t i = 0; i < ops.size(); ++i) std::fprintf(f, "S %d %d %zu %zu %zu\n", tail, mb, i, S.cap[i], S.off[i]);
+    }
+  }
+  std::fclose(f);
+}
+static void dump_ops(const std::string& name, const std::vector<Op>& iops) {   // per op: K N Npad layer-kind, for the bijection check
+  if (g_dump.empty()) return;
+  FILE* f = std::fopen((g_dump + "/" + name).c_str(), "w");
+  if (!f) std::exit(2);
+  for (const Op& o : iops) std::fprintf(f, "%d %d %d %d %d\n", o.d.K, o.d.N, o.d.Npad, o.layer, o.d.nphx);
+  std::fclose(f);
+}
+
 // trainer_build() of train.hip with the fused tail (train_tail_plan accepts decoder_400's last four layers)
 static void train_sections(const ModelDesc& md) {
   std::vector<LayerInfo> layers;
@@ -166,12 +207,8 @@ static void train_sections(const ModelDesc& md) {
   for (const DgradOp& o : dops) doff.push_back((int64_t)o.w_off);
   ints("train.dops_off", doff);
   whole("train.map", gm.map);
-  if (!g_dump.empty()) {   // per op: K N Npad layer-kind, for the bijection check
-    FILE* f = std::fopen((g_dump + "/train.ops.txt").c_str(), "w");
-    if (!f) std::exit(2);
-    for (const Op& o : iops) std::fprintf(f, "%d %d %d %d %d\n", o.d.K, o.d.N, o.d.Npad, o.layer, o.d.nphx);
-    std::fclose(f);
-  }
+  dump_ops("train.ops.txt", iops);
+  dump_train_plan("", iops, layers, tail.first_layer, tail.H * tail.W);
 }
 
 // a family member: the f32 engine's operands + trainer_build() layer by layer (train_tail_plan declines every decoder but decoder_400)
@@ -220,12 +257,7 @@ static void family_sections(const ModelDesc& md) {
   for (const DgradOp& o : dops) for (int64_t v : {(int64_t)o.w_off, (int64_t)o.layer, (int64_t)o.d.cy, (int64_t)o.d.cx, (int64_t)o.d.ay, (int64_t)o.d.K, (int64_t)o.d.N}) dgeo.push_back(v);
   ints("family.train.dops", dgeo);
   whole("family.train.map", gm.map);
-  if (!g_dump.empty()) {
-    FILE* f = std::fopen((g_dump + "/family.train.ops.txt").c_str(), "w");
-    if (!f) std::exit(2);
-    for (const Op& o : iops) std::fprintf(f, "%d %d %d %d %d\n", o.d.K, o.d.N, o.d.Npad, o.layer, o.d.nphx);
-    std::fclose(f);
-  }
+  dump_ops("family.train.ops.txt", iops);
 }
 
 // small graphs from a seeded generator (the same sequence is easy to write in any language: a 32-bit LCG, top 24 bits - 0.5)
@@ -243,11 +275,20 @@ static Layer layer(Lcg& g, int kind, int act, int k, int stride, int same, int c
   if (kind != SRCFD_LAYER_FLATTEN) { L.kernel = g.take((size_t)k * k * cin * cout); L.bias = g.take(cout); }
   return L;
 }
-static void small_graph(const std::string& tag, ModelDesc md) {
+static void small_graph(const std::string& tag, ModelDesc md, bool train_plan = false) {
   md.infer_shapes();
   std::vector<Op> ops;
   std::vector<float> pack;
   f32_sections(tag, md, ops, pack);
+  if (train_plan) {   // trainer_build() layer by layer
+    std::vector<LayerInfo> layers;
+    int64_t n_params = 0;
+    std::vector<float> init;
+    const ModelDesc im = index_model(md, layers, n_params, init);
+    build_plan(im, ops, pack);
+    dump_ops(tag + "train.ops.txt", ops);
+    dump_train_plan(tag, ops, layers, -1, 0);
+  }
 }
 
 int main(int argc, char** argv) {
@@ -269,7 +310,7 @@ int main(int argc, char** argv) {
       Lcg g{1};
       ModelDesc m; m.in_shape[0] = 4; m.in_shape[1] = 4; m.in_shape[2] = 8;
       m.layers = {layer(g, CT, SW, 3, 2, 0, 8, 4, "ct")};
-      small_graph("convt3.", m);
+      small_graph("convt3.", m, true);
     }
     {  // 32 -> 16 -> 8 with no 64 -> 32 in front: the pair without the triple
       Lcg g{2};
