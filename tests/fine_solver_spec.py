@@ -8,6 +8,14 @@ What differs from the host solver, on purpose, is the inner sweep order, which h
 Sums of squares are reduced in the device's fixed order: per mesh row, thread t of 256 adds the row's values t, t + 256, ...
 in order, then a halving tree; the row partials are summed the same way (`_sum256`).  The inner exit rule is the host's: at
 least one sweep, stop when sqrt(sum R^2 / (nx ny)) < 1e-6, at most 1000 sweeps.
+
+This file was written together with the kernels, so equal bits cannot show a mistake both share.  What pins it to something
+independent is tests/test_fine_cross.py: this specification against the host solver itself on the cases of
+tests/solver_cross.py -- dx != dy with nx > ny and nx < ny, QUICK and UPWIND on the cavity and on the backward-facing step,
+rho != 1, relaxation factors, the step geometry and inlet rows, single lids, moving side walls, a channel with mixed boundary
+types -- along trajectories from zero fields and at the fixed point, within the noise of the 1e-6 inner exit rule (velocities
+to 2.3e-6, pressure to 9e-6; bounds 4 x the per-case measurement).  tests/test_gpu_fine_cross.py holds the device to the host
+solver at the same bounds.
 """
 from __future__ import annotations
 

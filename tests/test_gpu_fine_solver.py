@@ -1,7 +1,11 @@
 """The device fine-mesh solver (csrc/fine_solver.hip, sr-for-cfd_amd/fine.py) on an MI355X: the same bits as its numpy
 specification (tests/fine_solver_spec.py) at the meshes and controls where the kernels branch, through convergence, divergence
 and re-init; pinned to the reference's stored coarse field, the SR hand-off straight into the device state, resumable and
-deterministic runs, and the reference's drop-in functions."""
+deterministic runs, and the reference's drop-in functions.
+
+The specification shares its authors with the kernels; beyond the square double-lid cavity of test_pinned_to_the_reference_field
+the device is pinned to the host solver srcfd_coarse_solve by tests/test_gpu_fine_cross.py (rectangular cells, UPWIND, rho,
+relaxation, the backward-facing-step path, single lids, moving side walls, mixed boundary types; case table tests/solver_cross.py)."""
 import importlib
 import os
 import signal
