@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "abi_guard.h"
+#include "gemm32_plan.h"
 #include "kernels.h"
 #include "model.h"
 #include "operand_pack.h"

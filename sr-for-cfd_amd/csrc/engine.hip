@@ -241,7 +241,7 @@ size_t Model::splitk_need(int n, int precision, const Switches& sw) const {
     if (st.k != F32Kernel::Group && st.k != F32Kernel::Mfma) continue;
     GemmDesc ds[4];
     f32_span(i, st.count, n, ds);
-    need = std::max(need, st.k == F32Kernel::Group ? gemm_group_ws_floats(ds, st.count) : gemm_splitk_ws_floats(ds[0]));
+    need = std::max(need, gemm_group_ws_floats(ds, st.count));   // the plan's ws_floats: what the launcher will insist on
   }
   return need;
 }

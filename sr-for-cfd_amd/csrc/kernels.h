@@ -30,7 +30,6 @@ struct EpiAux {
   const float* zaux = nullptr;
   int mode = 0;
 };
-bool gemm_supports_epi_aux(const GemmDesc& d);
 
 // The whole encoder_10 in one launch, f32 (kernels_enc32.hip)
 constexpr int ENC32_G = 3;   // samples per workgroup
@@ -39,7 +38,7 @@ struct Enc32Params {
   const float* affine;     // (n,2) mean,std or null
   int n;
   const float* w1; const float* b1;     // conv2d: B[9][64], bias[64]
-  const float* w2f; const float* b2;    // conv2d_1: A fragments [channel tile 8][tap*4+q 36][64 lanes][4] (engine.hip, plan_enc32), bias[128]
+  const float* w2f; const float* b2;    // conv2d_1: A fragments [channel tile 8][tap*4+q 36][64 lanes][4] (operand_pack.cpp, pack_enc32), bias[128]
   const float* wd; const float* bd;     // dense: B[3200][128], bias[128]
   const float* wl; const float* bl;     // latent_vector: B[128][nl_pad], bias[nl]
   float* z;                             // (n, nl)
@@ -53,17 +52,15 @@ bool dense_skinny32_qualifies(const GemmDesc& d);
 hipError_t launch_dense_skinny32(const GemmDesc& d, const float* X, const float* B, const float* bias, float* Y, hipStream_t s);
 
 hipError_t launch_gemm_naive(const GemmDesc& d, const float* X, const float* B, const float* bias, float* Y, hipStream_t s);
-// ws: optional split-K scratch (gemm_splitk_ws_floats(d) floats); without it the launch never splits.
+// The generic f32 GEMM.  Which kernel takes d, its tile, its split-K cut and its grids are decided by plan_gemm32 (gemm32_plan.h);
+// ws: the split-K slabs, at least gemm_splitk_ws_floats(d) floats.  A smaller one is refused with hipErrorInvalidValue before
+// anything is launched (an unsplit GEMM would sum in another order); null is legal only where the plan needs no slabs.
 hipError_t launch_gemm_mfma(const GemmDesc& d, const float* X, const float* B, const float* bias, float* Y, hipStream_t s,
                             float* ws = nullptr, size_t ws_floats = 0, bool batch_invariant = true, EpiAux aux = EpiAux());
-// batch_invariant (inference): the cut depends on the layer only, never on the batch size; false (training): on the tile count too.
-int gemm_splitk_splits(const GemmDesc& d, int* kchunk_out, bool batch_invariant = true);
-size_t gemm_splitk_ws_floats(const GemmDesc& d, bool batch_invariant = true);
-// The GEMMs of one layer (the output phases of a transposed convolution with kernel != stride) as one launch + one finish;
-// ws must hold gemm_group_ws_floats() floats, otherwise (or when the GEMMs do not qualify) they are launched one by one.
+// The GEMMs of one layer (1 .. 4: the output phases of a transposed convolution with kernel != stride) as one launch + one finish
+// where the plan groups them, one by one where it does not; ws: at least gemm_group_ws_floats() floats, refused like the above.
 hipError_t launch_gemm_mfma_group(const GemmDesc* ds, int count, const float* X, const float* const* Bs, const float* const* biases, float* Y,
                                   hipStream_t s, float* ws, size_t ws_floats, bool batch_invariant = true, EpiAux aux = EpiAux());
-size_t gemm_group_ws_floats(const GemmDesc* ds, int count, bool batch_invariant = true);
 // Large launches of the wide decoder layers (ConvT#0's phases as one launch, ConvT#1): kernels_gemm32.hip.  Same arithmetic
 // as launch_gemm_mfma / launch_gemm_mfma_group (bit-identical results), K splits summed inside the workgroup.
 struct Gemm32Group {
@@ -73,7 +70,7 @@ struct Gemm32Group {
   int kchunk[4];
   int count;
 };
-bool gemm32_big_qualifies(const GemmDesc* ds, int count);
+// For what gemm32_big_qualifies (gemm32_plan.h) accepts.
 hipError_t launch_gemm32_big(const GemmDesc* ds, int count, const float* X, const float* const* Bs, const float* const* biases, float* Y,
                              hipStream_t s);
 // Two consecutive kernel == stride == 2 transposed convolutions (CI 32 -> 16 -> 8 channels: ConvT#3 -> ConvT#4 of
@@ -83,11 +80,12 @@ struct PairDesc {
   int n, H, W;         // input (n, H, W, 32); output (n, 4H, 4W, 8)
   int act_a, act_b;
 };
-// wa [2 tiles][16 k-steps][64 lanes], ba [16], wb [8 k-steps][64 lanes], bb [8]: see pack_convt_pair() in engine.hip
+// wa [2 tiles][16 k-steps][64 lanes], ba [16], wb [8 k-steps][64 lanes], bb [8]: see pack_convt_pair() in operand_pack.cpp
 hipError_t launch_convt_pair_f32(const PairDesc& d, const float* X, const float* wa, const float* ba, const float* wb, const float* bb,
                                  float* Y, hipStream_t s);
 // The same with one more layer in front: 64 -> 32 -> 16 -> 8 channels (ConvT#2 -> ConvT#3 -> ConvT#4), input (n, H, W, 64),
-// output (n, 8H, 8W, 8).  w1 [4 tiles][32 k-steps][64 lanes] (staged in LDS), b1 [32]; w2 [2][16][64], b2 [16]; w3 [8][64], b3 [8].
+// output (n, 8H, 8W, 8).  w1 [4 tiles][32 k-steps][64 lanes] (staged in LDS), b1 [32]; w2 [2][16][64], b2 [16]; w3 [8][64], b3 [8]:
+// pack_convt_triple() in operand_pack.cpp.
 struct TripleDesc {
   int n, H, W;
   int act1, act2, act3;
@@ -145,8 +143,7 @@ hipError_t launch_gemm_x3(const GemmDesc& d, const float* X, const uint16_t* Wt,
 hipError_t launch_gemm_x3_group(const GemmDesc* ds, int count, const float* X, const uint16_t* const* Wts, const float* const* biases, float* Y,
                                 hipStream_t s, int num_cus = 256);
 
-// Last layer + de-standardise + NaN guard + output cast in one kernel, for the layers gemm_fuses_finalize() accepts.
-bool gemm_fuses_finalize(const GemmDesc& d);
+// Last layer + de-standardise + NaN guard + output cast in one kernel, for the layers gemm_fuses_finalize() (gemm32_plan.h) accepts.
 hipError_t launch_gemm_finalize(const GemmDesc& d, const float* X, const float* B, const float* bias, void* out, int out_dtype,
                                 const float* affine, int nan_guard, unsigned long long* nonfinite, hipStream_t s);
 hipError_t launch_standardize(const float* x, float* y, const float* affine, int per_sample, int64_t total, hipStream_t s);

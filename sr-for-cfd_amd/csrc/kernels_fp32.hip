@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "act_device.h"
+#include "gemm32_plan.h"
 #include "kernels.h"
 
 namespace srcfd {
@@ -96,9 +97,8 @@ __global__ void __launch_bounds__(256) gemm_naive_f32(GemmDesc d, const float* _
 // f32 MFMA implicit GEMM.  Block = 256 threads = 4 waves; block tile 128 x
 // (32*NB); each wave owns 32 rows x NB tiles of 32 columns
 // (v_mfma_f32_32x32x2_f32: exact f32 products, k-ordered fmaf chain).
+// BM = 128 rows: gemm32_plan.h, which decides the launches of these kernels.
 // ---------------------------------------------------------------------------
-constexpr int BM = 128;
-
 // VEC 0: scalar gather (any CI); 1: CI % 4 == 0 (each 16-byte group of k sits inside one tap).
 // BKT: depth of a K slab, 16 or 32.  One slab = one round trip to memory, so launches that cannot hide it behind other
 // workgroups (a single field, a training micro-batch) take the deeper slab; full-batch launches run ~1 % faster with 16.
@@ -451,7 +451,7 @@ struct FinalEpilogue {
 
 __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f);
 
-constexpr int CT_H = 16, CT_W = 64, CT_PW = CT_W + 2;
+constexpr int CT_PW = CT_W + 2;   // CT_H x CT_W: gemm32_plan.h
 template <int FIN>
 __global__ void __launch_bounds__(256) conv_n1_tile_f32(GemmDesc d, const float* __restrict__ X, const float* __restrict__ B,
                                                          const float* __restrict__ bias, float* __restrict__ Y, FinalEpilogue fe) {
@@ -632,55 +632,25 @@ hipError_t launch_gemm_naive(const GemmDesc& d, const float* X, const float* B, 
   return hipGetLastError();
 }
 
-// Skinny problems (few output tiles, long K: the Dense layers, and every layer at training batch
-// sizes) are cut along K so that the weight matrix is streamed by >= 256 blocks instead of 1-6.
-int gemm_splitk_splits(const GemmDesc& d, int* kchunk_out, bool batch_invariant) {
-  if (kchunk_out) *kchunk_out = d.K;
-  if (batch_invariant) {
-    // inference: the summation order of a sample must not depend on the batch it sits in, so the cut depends on the
-    // layer only: Dense layers (one row per sample) with a long K are always cut into 256-deep slabs, small conv maps into 144-deep ones
-    if (d.M == 0) return 1;
-    if (d.MH * d.MW == 1 && d.K >= 1024) {
-      if (kchunk_out) *kchunk_out = 256;
-      return (d.K + 255) / 256;
-    }
-    if (d.MH * d.MW <= 64 && d.K >= 512) {  // small feature maps with a long K (encoder conv2d_1: 25 pixels, K = 576): too few row tiles
-      if (kchunk_out) *kchunk_out = 144;
-      return (d.K + 143) / 144;
-    }
-    if (d.MH * d.MW <= 256 && d.K >= 512) {  // ConvT#0's phases (144-169 pixels per sample, K up to 1024): a single field is 4 row tiles
-      if (kchunk_out) *kchunk_out = 256;     // -- costs ~3 % at batch 256 (slab traffic), cuts the one-field call by a third
-      return (d.K + 255) / 256;
-    }
-    return 1;
-  }
-  int nb = (d.Npad % 128 == 0) ? 4 : ((d.Npad % 64 == 0) ? 2 : 1);
-  int64_t tiles = (int64_t)((d.M + BM - 1) / BM) * (d.Npad / (32 * nb));
-  if (tiles >= 128 || d.K < 256 || tiles == 0) return 1;
-  int want = (int)std::min<int64_t>(std::min<int64_t>((512 + tiles - 1) / tiles, d.K / 64), 256);
-  if (want <= 1) return 1;
-  int kchunk = ((d.K + want - 1) / want + 31) / 32 * 32;
-  if (kchunk_out) *kchunk_out = kchunk;
-  return (d.K + kchunk - 1) / kchunk;
-}
+// The generic GEMM's launchers issue what plan_gemm32 (gemm32_plan.cpp) decided: kernel, tile, cut, grids.  No rule lives here.
+static dim3 dim3_of(const unsigned (&g)[3]) { return dim3(g[0], g[1], g[2]); }
 
-size_t gemm_splitk_ws_floats(const GemmDesc& d, bool batch_invariant) {
-  int splits = gemm_splitk_splits(d, nullptr, batch_invariant);
-  return splits > 1 ? (size_t)splits * d.M * d.Npad : 0;
+// the <NB, VEC, BKT> instance of a tile kernel that a planned launch names
+struct SingleTile { template <int NB, int VEC, int BKT> static constexpr auto kernel() { return &gemm_mfma_f32<NB, VEC, BKT>; } };
+struct GroupTile { template <int NB, int VEC, int BKT> static constexpr auto kernel() { return &gemm_mfma_group_f32<NB, VEC, BKT>; } };
+template <class T, int NB>
+static auto tile_kernel_nb(const Gemm32Launch& l) {
+  if (l.vec) return l.bkt == 32 ? T::template kernel<NB, 1, 32>() : T::template kernel<NB, 1, 16>();
+  return l.bkt == 32 ? T::template kernel<NB, 0, 32>() : T::template kernel<NB, 0, 16>();
 }
-
-static bool is_tiled_n1_conv(const GemmDesc& d) {
-  return d.N == 1 && d.nphx == 1 && d.TX == 3 && d.TY == 3 && d.CI == 8 && d.ax == 1 && d.bx == 1 && d.ay == 1 && d.by == 1 && d.cx == -1 &&
-         d.cy == -1 && d.os == 1 && d.ox0 == 0 && d.oy0 == 0 && d.OC == 1 && d.IH == d.OH && d.IW == d.OW && d.MH == d.OH && d.MW == d.OW &&
-         d.M > 0 && d.M % (d.MH * d.MW) == 0;
-}
-
-bool gemm_fuses_finalize(const GemmDesc& d) { return is_tiled_n1_conv(d); }
+template <class T>
+static auto tile_kernel(const Gemm32Launch& l) { return l.nb == 4 ? tile_kernel_nb<T, 4>(l) : (l.nb == 2 ? tile_kernel_nb<T, 2>(l) : tile_kernel_nb<T, 1>(l)); }
 
 hipError_t launch_gemm_finalize(const GemmDesc& d, const float* X, const float* B, const float* bias, void* out, int out_dtype,
                                 const float* affine, int nan_guard, unsigned long long* nonfinite, hipStream_t s) {
-  if (!is_tiled_n1_conv(d)) return hipErrorInvalidValue;
-  dim3 grid((d.OW + CT_W - 1) / CT_W, (d.OH + CT_H - 1) / CT_H, d.M / (d.MH * d.MW));
+  const Gemm32Op o = plan_gemm32(&d, 1, true).op[0];
+  if (o.route != Gemm32Route::TiledN1) return hipErrorInvalidValue;
+  const dim3 grid = dim3_of(o.l.grid);
   FinalEpilogue fe{out, affine, nan_guard, nonfinite};
   if (out_dtype == SRCFD_F32) hipLaunchKernelGGL(conv_n1_tile_f32<1>, grid, dim3(256), 0, s, d, X, B, bias, nullptr, fe);
   else if (out_dtype == SRCFD_BF16) hipLaunchKernelGGL(conv_n1_tile_f32<2>, grid, dim3(256), 0, s, d, X, B, bias, nullptr, fe);
@@ -689,123 +659,56 @@ hipError_t launch_gemm_finalize(const GemmDesc& d, const float* X, const float* 
   return hipGetLastError();
 }
 
-static bool is_ci1_conv(const GemmDesc& d) { return d.CI == 1 && d.N <= 8 && d.K <= 64 && d.nphx == 1 && d.CO == d.N; }
-
-hipError_t launch_gemm_mfma(const GemmDesc& d, const float* X, const float* B, const float* bias, float* Y, hipStream_t s, float* ws,
-                            size_t ws_floats, bool batch_invariant, EpiAux aux) {
-  if (d.M == 0 || d.N == 0) return hipSuccess;
+// one planned op on its own; ws: the workspace the plan was checked against
+static hipError_t issue_gemm(const GemmDesc& d, const Gemm32Op& o, const float* X, const float* B, const float* bias, float* Y, hipStream_t s,
+                             float* ws, const EpiAux& aux) {
+  if (o.route == Gemm32Route::None) return hipSuccess;
   if (aux.mode && !gemm_supports_epi_aux(d)) return hipErrorInvalidValue;
-  if (is_tiled_n1_conv(d)) {
-    dim3 grid((d.OW + CT_W - 1) / CT_W, (d.OH + CT_H - 1) / CT_H, d.M / (d.MH * d.MW));
-    hipLaunchKernelGGL(conv_n1_tile_f32<0>, grid, dim3(256), 0, s, d, X, B, bias, Y, FinalEpilogue{});
-    return hipGetLastError();
-  }
-  if (d.N == 1 && d.nphx == 1 && d.TX == 3 && d.TY == 3 && d.CI == 8 && d.ax == 1 && d.bx == 1 && d.ay == 1 && d.os == 1 && d.ox0 == 0 && d.OC == 1 &&
-      d.MW % 4 == 0 && d.OW % 4 == 0 && d.K <= 512) {
-    hipLaunchKernelGGL(conv_n1x4_f32, dim3((unsigned)((d.M / 4 + 255) / 256)), dim3(256), 0, s, d, X, B, bias, Y);
-    return hipGetLastError();
-  }
-  if (d.N == 1 && d.K <= 512 && d.nphx == 1) {
-    hipLaunchKernelGGL(conv_n1_f32, dim3((unsigned)((d.M + 255) / 256)), dim3(256), 0, s, d, X, B, bias, Y);
-    return hipGetLastError();
-  }
-  if (d.CI == 1 && d.N <= 8 && d.K <= 64 && d.nphx == 1 && d.CO == d.N) {
-    hipLaunchKernelGGL(conv_ci1_f32, dim3((unsigned)((d.M + 255) / 256)), dim3(256), 0, s, d, X, B, bias, Y, aux);
-    return hipGetLastError();
-  }
-  const int vec = (d.K > 0 && d.CI % 4 == 0) ? 1 : 0;
-  int nb = (d.Npad % 128 == 0) ? 4 : ((d.Npad % 64 == 0) ? 2 : 1);
-  int kchunk = d.K;
-  int splits = ws ? gemm_splitk_splits(d, &kchunk, batch_invariant) : 1;
-  if (splits > 1 && (size_t)splits * d.M * d.Npad > ws_floats) splits = 1;
-  float* wsp = splits > 1 ? ws : nullptr;
-  // few rows (a solver-side call is 3 samples): narrower column blocks per wave until the launch covers the chip, and
-  // deeper K slabs.  The k order of every output element is the same for any nb / slab depth, so results stay
-  // bit-identical across batch sizes.
-  const int64_t row_tiles = (d.M + BM - 1) / BM;
-  while (nb > 1 && row_tiles * (d.Npad / (32 * nb)) * splits < 512) nb >>= 1;
-  const bool deep = row_tiles * (d.Npad / (32 * nb)) * splits < 1024;
-  dim3 grid((unsigned)row_tiles, d.Npad / (32 * nb), splits);
-#define GO2(NBV, VECV) do { if (deep) hipLaunchKernelGGL((gemm_mfma_f32<NBV, VECV, 32>), grid, dim3(256), 0, s, d, X, B, bias, Y, wsp, kchunk, aux); \
-                            else hipLaunchKernelGGL((gemm_mfma_f32<NBV, VECV, 16>), grid, dim3(256), 0, s, d, X, B, bias, Y, wsp, kchunk, aux); } while (0)
-#define GO(NBV) do { if (vec) GO2(NBV, 1); else GO2(NBV, 0); } while (0)
-  if (nb == 4) GO(4); else if (nb == 2) GO(2); else GO(1);
-#undef GO2
-#undef GO
-  if (splits > 1) {
-    int64_t total = (int64_t)d.M * d.N;
-    const int groups = (splits >= 32 && total < 65536) ? 8 : 1, epb = 256 / groups;
-    hipLaunchKernelGGL(splitk_finish_f32, dim3((unsigned)((total + epb - 1) / epb)), dim3(256), 0, s, d, wsp, splits, bias, Y, groups, aux);
+  const dim3 grid = dim3_of(o.l.grid);
+  switch (o.route) {
+    case Gemm32Route::None: break;
+    case Gemm32Route::TiledN1: hipLaunchKernelGGL(conv_n1_tile_f32<0>, grid, dim3(256), 0, s, d, X, B, bias, Y, FinalEpilogue{}); break;
+    case Gemm32Route::N1x4: hipLaunchKernelGGL(conv_n1x4_f32, grid, dim3(256), 0, s, d, X, B, bias, Y); break;
+    case Gemm32Route::N1: hipLaunchKernelGGL(conv_n1_f32, grid, dim3(256), 0, s, d, X, B, bias, Y); break;
+    case Gemm32Route::Ci1: hipLaunchKernelGGL(conv_ci1_f32, grid, dim3(256), 0, s, d, X, B, bias, Y, aux); break;
+    case Gemm32Route::Mfma: {
+      float* slabs = o.splits > 1 ? ws + o.slab_off : nullptr;
+      hipLaunchKernelGGL(tile_kernel<SingleTile>(o.l), grid, dim3(256), 0, s, d, X, B, bias, Y, slabs, o.kchunk, aux);
+      if (o.l.fin[0]) hipLaunchKernelGGL(splitk_finish_f32, dim3(o.l.fin[0]), dim3(256), 0, s, d, slabs, o.splits, bias, Y, o.finish_groups, aux);
+    }
   }
   return hipGetLastError();
 }
 
-static bool uses_generic_gemm(const GemmDesc& d) {
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0) return false;
-  if (is_tiled_n1_conv(d)) return false;
-  if (d.N == 1 && d.K <= 512 && d.nphx == 1) return false;
-  if (d.CI == 1 && d.N <= 8 && d.K <= 64 && d.nphx == 1 && d.CO == d.N) return false;
-  return true;
-}
-
-size_t gemm_group_ws_floats(const GemmDesc* ds, int count, bool batch_invariant) {
-  size_t total = 0;
-  for (int i = 0; i < count; ++i) total += gemm_splitk_ws_floats(ds[i], batch_invariant);
-  return total;
-}
-
-// the kernels launch_gemm_mfma picks that apply an EpiAux: the generic GEMM and conv_ci1_f32 -- the latter only where the N == 1
-// kernels in front of it do not take the layer first (a 1 -> 1 channel conv goes to conv_n1_f32, which has no training epilogue)
-bool gemm_supports_epi_aux(const GemmDesc& d) {
-  return uses_generic_gemm(d) || (is_ci1_conv(d) && d.M > 0 && d.K > 0 && !is_tiled_n1_conv(d) && !(d.N == 1 && d.K <= 512 && d.nphx == 1));
+hipError_t launch_gemm_mfma(const GemmDesc& d, const float* X, const float* B, const float* bias, float* Y, hipStream_t s, float* ws,
+                            size_t ws_floats, bool batch_invariant, EpiAux aux) {
+  const Gemm32Plan p = plan_gemm32(&d, 1, batch_invariant);
+  if (!gemm32_ws_fits(p, ws, ws_floats)) return hipErrorInvalidValue;   // refused, never re-routed: an unsplit GEMM sums in another order
+  return issue_gemm(d, p.op[0], X, B, bias, Y, s, ws, aux);
 }
 
 hipError_t launch_gemm_mfma_group(const GemmDesc* ds, int count, const float* X, const float* const* Bs, const float* const* biases, float* Y,
                                   hipStream_t s, float* ws, size_t ws_floats, bool batch_invariant, EpiAux aux) {
-  bool group = count >= 2 && count <= 4;
-  for (int i = 0; group && i < count; ++i)
-    group = uses_generic_gemm(ds[i]) && ds[i].Npad == ds[0].Npad && (ds[i].CI % 4 == 0) == (ds[0].CI % 4 == 0);
-  GemmGroup g{};
-  int64_t tiles = 0, max_rows = 0, max_finish = 0;
-  size_t ws_used = 0;
-  bool any_split = false;
-  for (int i = 0; group && i < count; ++i) {
-    const GemmDesc& d = ds[i];
-    int kchunk = d.K;
-    int splits = ws ? gemm_splitk_splits(d, &kchunk, batch_invariant) : 1;
-    const size_t need = splits > 1 ? (size_t)splits * d.M * d.Npad : 0;
-    if (ws_used + need > ws_floats) { group = false; break; }
-    if (splits >= 32 && (int64_t)d.M * d.N < 65536) { group = false; break; }  // the single launch would finish in 8 groups
-    g.d[i] = d; g.B[i] = Bs[i]; g.bias[i] = biases[i];
-    g.ws[i] = splits > 1 ? ws + ws_used : nullptr;
-    g.kchunk[i] = kchunk;
-    g.zend[i] = (i ? g.zend[i - 1] : 0) + splits;
-    ws_used += need;
-    const int64_t rows = (d.M + BM - 1) / BM;
-    tiles += rows * splits;
-    max_rows = std::max(max_rows, rows);
-    if (splits > 1) { any_split = true; max_finish = std::max<int64_t>(max_finish, ((int64_t)d.M * d.N + 255) / 256); }
-  }
-  if (!group) {
+  const Gemm32Plan p = plan_gemm32(ds, count, batch_invariant);
+  if (p.count != count || !gemm32_ws_fits(p, ws, ws_floats)) return hipErrorInvalidValue;
+  if (!p.grouped) {
     for (int i = 0; i < count; ++i) {
-      hipError_t e = launch_gemm_mfma(ds[i], X, Bs[i], biases[i], Y, s, ws, ws_floats, batch_invariant, aux);
+      hipError_t e = issue_gemm(ds[i], p.op[i], X, Bs[i], biases[i], Y, s, ws, aux);
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
   }
+  GemmGroup g{};
+  for (int i = 0; i < count; ++i) {
+    const Gemm32Op& o = p.op[i];
+    g.d[i] = ds[i]; g.B[i] = Bs[i]; g.bias[i] = biases[i];
+    g.ws[i] = o.splits > 1 ? ws + o.slab_off : nullptr;
+    g.kchunk[i] = o.kchunk;
+    g.zend[i] = (i ? g.zend[i - 1] : 0) + o.splits;
+  }
   g.count = count;
-  const int vec = ds[0].CI % 4 == 0 ? 1 : 0, Npad = ds[0].Npad;
-  int nb = (Npad % 128 == 0) ? 4 : ((Npad % 64 == 0) ? 2 : 1);
-  while (nb > 1 && tiles * (Npad / (32 * nb)) < 512) nb >>= 1;
-  const bool deep = tiles * (Npad / (32 * nb)) < 1024;
-  dim3 grid((unsigned)max_rows, Npad / (32 * nb), g.zend[count - 1]);
-#define GO2(NBV, VECV) do { if (deep) hipLaunchKernelGGL((gemm_mfma_group_f32<NBV, VECV, 32>), grid, dim3(256), 0, s, g, X, Y, aux); \
-                            else hipLaunchKernelGGL((gemm_mfma_group_f32<NBV, VECV, 16>), grid, dim3(256), 0, s, g, X, Y, aux); } while (0)
-#define GO(NBV) do { if (vec) GO2(NBV, 1); else GO2(NBV, 0); } while (0)
-  if (nb == 4) GO(4); else if (nb == 2) GO(2); else GO(1);
-#undef GO2
-#undef GO
-  if (any_split) hipLaunchKernelGGL(splitk_finish_group_f32, dim3((unsigned)max_finish, count), dim3(256), 0, s, g, Y, aux);
+  hipLaunchKernelGGL(tile_kernel<GroupTile>(p.group), dim3_of(p.group.grid), dim3(256), 0, s, g, X, Y, aux);
+  if (p.group.fin[0]) hipLaunchKernelGGL(splitk_finish_group_f32, dim3(p.group.fin[0], p.group.fin[1]), dim3(256), 0, s, g, Y, aux);
   return hipGetLastError();
 }
 

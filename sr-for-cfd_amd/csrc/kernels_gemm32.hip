@@ -10,7 +10,7 @@
 //     so a thread recomputes its two source addresses only when the tap changes, not per 16-byte load;
 //   * the weight tile is fetched as 16-byte pieces;
 //   * a K split that the generic path does across workgroups (f32 slabs + a finish kernel, so that a sample's sums do not
-//     depend on its batch: gemm_splitk_splits) is done inside the workgroup: one MFMA chain per `kchunk`-deep slab,
+//     depend on its batch: gemm32_cut) is done inside the workgroup: one MFMA chain per `kchunk`-deep slab,
 //     added in slab order in registers, then the bias -- the same additions in the same order, without the slabs' round
 //     trip through HBM (ConvT#0: 0.5 GB written + read per 256 samples) or the finish launch;
 //   * the epilogue computes a row's output address once (not once per column tile), adds the lane's column offset, and
@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "gemm32_plan.h"
 #include "kernels.h"
 
 namespace srcfd {
@@ -28,7 +29,7 @@ namespace srcfd {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int GB_BM = 128, GB_BN = 128, GB_BK = 16, GB_LDA = GB_BK + 1;
+constexpr int GB_LDA = GB_BK + 1;   // GB_BM x GB_BN x GB_BK: gemm32_plan.h
 
 // x * rcp(1 + exp2(-log2(e) x)): kernels_fp32.hip, act_apply_precise (same expression, same bits)
 __device__ __forceinline__ float gb_swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
@@ -174,33 +175,13 @@ __global__ void __launch_bounds__(256) gemm32_big(Gemm32Group g, const float* __
   }
 }
 
-// A layer (1 GEMM) or the output phases of a transposed convolution (2-4 GEMMs) qualify when every GEMM is one of the
-// wide decoder layers this kernel is written for and the launch is large enough that the generic kernel would take its
-// widest tile anyway (so the choice does not depend on anything but the layer and "is the batch large").
-bool gemm32_big_qualifies(const GemmDesc* ds, int count) {
-  if (count < 1 || count > 4) return false;
-  int64_t tiles = 0;
-  for (int i = 0; i < count; ++i) {
-    const GemmDesc& d = ds[i];
-    if (d.M <= 0 || d.K <= 0 || d.CI % 16 != 0 || d.K % 16 != 0 || d.Npad % 128 != 0 || d.Npad != ds[0].Npad) return false;
-    if (d.act != SRCFD_ACT_SWISH && d.act != SRCFD_ACT_LINEAR) return false;
-    int kchunk = d.K;
-    (void)gemm_splitk_splits(d, &kchunk, true);
-    if (kchunk % GB_BK != 0) return false;   // a K slab of the batch-invariant split must be whole 16-deep tiles
-    tiles += (int64_t)((d.M + GB_BM - 1) / GB_BM) * (d.Npad / GB_BN);
-  }
-  return tiles >= 1024;
-}
-
 hipError_t launch_gemm32_big(const GemmDesc* ds, int count, const float* X, const float* const* Bs, const float* const* biases, float* Y,
                              hipStream_t s) {
   Gemm32Group g{};
   int max_rows = 0;
   for (int i = 0; i < count; ++i) {
     g.d[i] = ds[i]; g.B[i] = Bs[i]; g.bias[i] = biases[i];
-    int kchunk = ds[i].K;
-    (void)gemm_splitk_splits(ds[i], &kchunk, true);   // the batch-invariant cut of the generic path: the same slabs, summed in-kernel
-    g.kchunk[i] = kchunk;
+    g.kchunk[i] = gemm32_cut(ds[i], true).kchunk;   // the batch-invariant cut of the generic path: the same slabs, summed in-kernel
     max_rows = std::max(max_rows, (ds[i].M + GB_BM - 1) / GB_BM);
   }
   g.count = count;

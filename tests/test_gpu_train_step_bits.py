@@ -3,8 +3,8 @@ recorded by tests/golden/record_train_step.py on the commit that file names.  Th
 of every float addition are the recorded commit's, so the host code that plans the weight-gradient launches, the slab sums and
 the buffer sizes may be reorganised freely and no gradient bit moves.  A case is one fresh Trainer and four calls -- plain
 launches, the call that is captured, the replayed graph, and an overwriting call over NaN-filled buffers -- which must all give
-the recorded sha256 of the flat gradient and the recorded bits of the squared-error sum.  An undersized split-K workspace makes a
-GEMM run unsplit and sum in another order and an undersized slab space loses slabs, so the digests pin the sizing too.  An intended
+the recorded sha256 of the flat gradient and the recorded bits of the squared-error sum.  An undersized split-K workspace is
+refused (csrc/gemm32_plan.h, gemm32_ws_fits) and an undersized slab space loses slabs, so the digests pin the sizing too.  An intended
 change of a training kernel's arithmetic re-records the file and says so."""
 import hashlib
 import importlib

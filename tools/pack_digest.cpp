@@ -3,7 +3,8 @@
 // and prints JSON: per named section its offset, length (elements) and sha256.  Built by `make -C sr-for-cfd_amd/csrc pack_digest`
 // with -fsanitize=address,undefined; tests/test_operand_pack.py compares the output with tests/golden/operand_pack_digests.json.
 //   pack_digest <superres.h5> [dump-dir [family.h5]]     dump-dir: raw arrays for the test's property checks, and the training step's
-//   weight-gradient plan as text (dump_train_plan, tests/test_train_plan.py)
+//   weight-gradient plan as text (dump_train_plan, tests/test_train_plan.py), and the f32 GEMM's launch plan of every graph as text
+//   (PlanDump, tests/test_gemm32_plan.py)
 //   family.h5: a whole-model file of another member of the notebook's family (family.py, e.g. encoder_10 + decoder_100, with
 //   padding='same' transposed convolutions); adds `family.*` sections: its f32 plan and the trainer's maps without the fused tail.
 // Which fused kernels a graph qualifies for is decided in engine.hip / fused_bf16.hip / train_tail.hip (HIP translation units this
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "../sr-for-cfd_amd/csrc/gemm32_plan.h"
 #include "../sr-for-cfd_amd/csrc/operand_pack.h"
 #include "sha256.h"
 
@@ -165,6 +167,86 @@ static void dump_train_plan(const std::string& tag, const std::vector<Op>& iops,
   }
   std::fclose(f);
 }
+// The f32 GEMM's launch plan (gemm32_plan.cpp: what launch_gemm_mfma / launch_gemm_mfma_group issue and the slab buffers are sized
+// from) as text in the dump directory, for tests/test_gemm32_plan.py; no digest section.  mode 0: inference (batch-invariant cut),
+// 1: the training step's forward GEMMs, 2: its data-gradient GEMMs.  Per launch (the ops of one layer, or a single op) one line
+//   G mode n first count grouped nb bkt vec gx gy gz fx fy ws_floats fits(ws_floats - 1) fits(ws_floats) fits(null)      (-1: not asked)
+// and per op one line
+//   O mode n index route splits kchunk slab_off finish_groups nb bkt vec gx gy gz fx epi_aux fuses_finalize splitk_ws_floats  + the descriptor:
+//     M N K Npad MH MW TY TX CI IH IW ay by cy ax bx cx CO nphx OH OW OC os oy0 ox0 act
+struct PlanDump {
+  FILE* f = nullptr;
+  int next = 0;   // running op index of the file
+  explicit PlanDump(const std::string& tag) {
+    if (g_dump.empty()) return;
+    f = std::fopen((g_dump + "/" + tag + "gemm32.plan.txt").c_str(), "w");
+    if (!f) std::exit(2);
+  }
+  ~PlanDump() { if (f) std::fclose(f); }
+  void launch(int mode, int n, const GemmDesc* ds0, int count) {
+    if (!f) return;
+    GemmDesc ds[4];
+    for (int q = 0; q < count; ++q) { ds[q] = ds0[q]; ds[q].M = n * ds[q].MH * ds[q].MW; }
+    const bool inv = mode == 0;
+    const Gemm32Plan p = plan_gemm32(ds, count, inv);
+    if (p.count != count) std::exit(2);
+    float slab = 0.f;   // any non-null address: gemm32_ws_fits does not touch it
+    const Gemm32Launch& g = p.group;
+    std::fprintf(f, "G %d %d %d %d %d %d %d %d %u %u %u %u %u %zu %d %d %d\n", mode, n, next, count, (int)p.grouped, g.nb, g.bkt, g.vec, g.grid[0], g.grid[1],
+                 g.grid[2], g.fin[0], g.fin[1], p.ws_floats, p.ws_floats ? (int)gemm32_ws_fits(p, &slab, p.ws_floats - 1) : -1,
+                 (int)gemm32_ws_fits(p, &slab, p.ws_floats), (int)gemm32_ws_fits(p, nullptr, p.ws_floats));
+    for (int q = 0; q < count; ++q) {
+      const Gemm32Op& o = p.op[q];
+      const GemmDesc& d = ds[q];
+      std::fprintf(f, "O %d %d %d %d %d %d %zu %d %d %d %d %u %u %u %u %d %d %zu", mode, n, next + q, (int)o.route, o.splits, o.kchunk, o.slab_off, o.finish_groups,
+                   o.l.nb, o.l.bkt, o.l.vec, o.l.grid[0], o.l.grid[1], o.l.grid[2], o.l.fin[0], (int)gemm_supports_epi_aux(d), (int)gemm_fuses_finalize(d),
+                   gemm_splitk_ws_floats(d, inv));
+      for (int v : {d.M, d.N, d.K, d.Npad, d.MH, d.MW, d.TY, d.TX, d.CI, d.IH, d.IW, d.ay, d.by, d.cy, d.ax, d.bx, d.cx, d.CO, d.nphx, d.OH, d.OW, d.OC, d.os,
+                    d.oy0, d.ox0, d.act})
+        std::fprintf(f, " %d", v);
+      std::fprintf(f, "\n");
+    }
+  }
+  // every batch of a mode over a list of (descriptor, layer): the ops of one layer go out together, at most four
+  void ops(int mode, const std::vector<GemmDesc>& ds, const std::vector<int>& layer) {
+    const std::vector<int> batches = mode == 0 ? std::vector<int>{1, 3, 7, 64, 216, 768} : std::vector<int>{1, 2, 3, 4, 5, 6, 7, 8, 32};
+    const int first = next;
+    for (int n : batches) {
+      next = first;
+      for (size_t i = 0, j; i < ds.size(); i = j) {
+        for (j = i + 1; j < ds.size() && mode != 2 && layer[j] == layer[i] && j - i < 4; ++j) {}
+        launch(mode, n, ds.data() + i, (int)(j - i));
+        next += (int)(j - i);
+      }
+    }
+    next = first + (int)ds.size();
+  }
+  // a layer graph: its forward ops as the engine launches them, as the trainer does (activation left to the epilogue), and the trainer's data gradients
+  void graph(const ModelDesc& md) {
+    std::vector<Op> ops_;
+    std::vector<float> pack;
+    build_plan(md, ops_, pack);
+    std::vector<GemmDesc> ds;
+    std::vector<int> layer;
+    for (const Op& o : ops_) { ds.push_back(o.d); layer.push_back(o.layer); }
+    ops(0, ds, layer);
+    std::vector<LayerInfo> layers;
+    int64_t n_params = 0;
+    std::vector<float> init;
+    const ModelDesc im = index_model(md, layers, n_params, init);
+    build_plan(im, ops_, pack);
+    ds.clear(); layer.clear();
+    for (const TrainOp& o : train_ops(ops_, layers)) { ds.push_back(o.fwd); layer.push_back(o.layer); }
+    ops(1, ds, layer);
+    std::vector<DgradOp> dops;
+    std::vector<float> dpack;
+    build_dgrad(im, layers, dops, dpack);
+    ds.clear(); layer.clear();
+    for (const DgradOp& o : dops) { ds.push_back(o.d); layer.push_back(o.layer); }
+    ops(2, ds, layer);
+  }
+};
+
 static void dump_ops(const std::string& name, const std::vector<Op>& iops) {   // per op: K N Npad layer-kind, for the bijection check
   if (g_dump.empty()) return;
   FILE* f = std::fopen((g_dump + "/" + name).c_str(), "w");
@@ -280,6 +362,7 @@ static void small_graph(const std::string& tag, ModelDesc md, bool train_plan = 
   std::vector<Op> ops;
   std::vector<float> pack;
   f32_sections(tag, md, ops, pack);
+  PlanDump(tag).graph(md);
   if (train_plan) {   // trainer_build() layer by layer
     std::vector<LayerInfo> layers;
     int64_t n_params = 0;
@@ -326,11 +409,44 @@ int main(int argc, char** argv) {
                   layer(g, DE, SRCFD_ACT_LINEAR, 1, 1, 0, 128, 50, "l")};
       small_graph("noenc32.", m);
     }
+    PlanDump("").graph(md);
+    {  // graphs and descriptors for the branches of the f32 GEMM's plan that the graphs above do not reach (text dump only)
+      PlanDump hand("hand.");
+      Lcg g{4};
+      ModelDesc a; a.in_shape[0] = 10; a.in_shape[1] = 10; a.in_shape[2] = 8;   // 3x3 8 -> 1, not SAME, rows 8 wide: conv_n1x4_f32
+      a.layers = {layer(g, CV, SW, 3, 1, 0, 8, 1, "n1x4")};
+      a.infer_shapes();
+      hand.graph(a);
+      // 3 -> 1 channels (conv_n1_f32, CI % 4 != 0), 1 -> 4 SAME (conv_ci1_f32), then a ConvT with one output channel: a layer
+      // whose phases are no generic GEMMs
+      ModelDesc b; b.in_shape[0] = 6; b.in_shape[1] = 6; b.in_shape[2] = 3;
+      b.layers = {layer(g, CV, SW, 3, 1, 0, 3, 1, "n1"), layer(g, CV, SW, 3, 1, 1, 1, 4, "ci1"), layer(g, CT, SW, 3, 2, 0, 4, 1, "ct_n1")};
+      b.infer_shapes();
+      hand.graph(b);
+      // a ConvT with K = 4096 in its first phase: the training cut reaches 32 slabs and more, which a single launch finishes in 8 groups
+      ModelDesc c; c.in_shape[0] = 4; c.in_shape[1] = 4; c.in_shape[2] = 1024;
+      c.layers = {layer(g, CT, SW, 3, 2, 0, 1024, 4, "ct_deep")};
+      c.infer_shapes();
+      hand.graph(c);
+      // no real layer has phases of different widths or gather forms: the convt3 phases with one of them altered
+      ModelDesc m; m.in_shape[0] = 4; m.in_shape[1] = 4; m.in_shape[2] = 8;
+      m.layers = {layer(g, CT, SW, 3, 2, 0, 8, 4, "ct")};
+      m.infer_shapes();
+      std::vector<Op> o4;
+      std::vector<float> pk;
+      build_plan(m, o4, pk);
+      std::vector<GemmDesc> wide, odd;
+      for (const Op& o : o4) { wide.push_back(o.d); odd.push_back(o.d); }
+      wide[1].N = wide[1].CO = wide[1].OC = 40; wide[1].Npad = 64;
+      odd[2].CI = 6; odd[2].K = odd[2].TY * odd[2].TX * 6;
+      for (int mode = 0; mode < 2; ++mode) { hand.ops(mode, wide, {0, 0, 0, 0}); hand.ops(mode, odd, {0, 0, 0, 0}); }
+    }
     if (argc > 3) {
       ModelDesc fm;
       append_h5_whole(fm, argv[3]);
       fm.infer_shapes();
       family_sections(fm);
+      PlanDump("family.").graph(fm);
     }
     std::printf("\n]}\n");
   } catch (const FileError& e) {
