@@ -191,6 +191,11 @@ int srcfd_model_debug_activation(srcfd_model* m, int index, void* dst, size_t by
  * srcfd_predict* call; each selects a complete second implementation (the parity tests compare the two), none skips work, and a
  * captured hipGraph is replayed only under the switches it was captured with.  graph: eager | capture | replay. */
 int srcfd_model_last_plan(const srcfd_model* m, char* buf, size_t buf_len);
+/* Test hook: the steps an n-sample forward of the handle's f32-grade precision would take under the switches the environment holds
+ * now, as "first-op-name=kernel:ops" words separated by blanks, e.g. "conv2d=enc32:4 dense_1=skinny:1 conv2d_transpose.ph00=big:4 ...".
+ * kernel: enc32 | tail32 | triple | pair | x3 | big | group | skinny | finalize | mfma | naive (engine.h, F32Kernel).  Asks the same
+ * function the launch loop asks; launches nothing and works on a host-only handle.  SRCFD_EINVAL under a 16-bit precision. */
+int srcfd_model_f32_steps(const srcfd_model* m, int n, char* buf, size_t buf_len);
 
 /* ---- stats file ----------------------------------------------------------
  * `key value` lines, '#' comments (PyCFD_ML_accelerated.py:787-797).  Looks up

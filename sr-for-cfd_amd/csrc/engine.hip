@@ -895,6 +895,27 @@ int srcfd_model_last_plan(const srcfd_model* m, char* buf, size_t buf_len) {
   });
 }
 
+int srcfd_model_f32_steps(const srcfd_model* m, int n, char* buf, size_t buf_len) {
+  return srcfd::abi_guard("srcfd_model_f32_steps", [&]() -> int {
+    if (!m || !buf || buf_len == 0 || n < 1) { set_error("bad arguments"); return SRCFD_EINVAL; }
+    const Model& mm = *M(m);
+    if (mm.precision == SRCFD_PREC_BF16 || mm.precision == SRCFD_PREC_F16) { set_error("the 16-bit precisions have no f32 steps"); return SRCFD_EINVAL; }
+    static const char* const kernel[] = {"tail32", "triple", "pair", "x3", "big", "group", "skinny", "finalize", "mfma", "naive"};   // F32Kernel's order
+    const srcfd::Switches sw = srcfd::Switches::from_env();
+    std::string out;
+    const size_t first = mm.f32_first(mm.precision, sw);
+    if (first) out = mm.ops[0].name + "=enc32:" + std::to_string(first);
+    srcfd::F32Step st;
+    for (size_t i = first; i < mm.ops.size(); i += st.count) {
+      st = mm.f32_step(i, n, mm.precision, sw);
+      out += (out.empty() ? "" : " ") + mm.ops[i].name + "=" + kernel[(int)st.k] + ":" + std::to_string(st.count);
+    }
+    if (out.size() >= buf_len) { set_error("buffer too small"); return SRCFD_EINVAL; }
+    snprintf(buf, buf_len, "%s", out.c_str());
+    return SRCFD_OK;
+  });
+}
+
 int srcfd_model_debug_activation(srcfd_model* m, int index, void* dst, size_t bytes) {
   return srcfd::abi_guard("srcfd_model_debug_activation", [&]() -> int {
     if (!m || !dst || index < 0 || index > 1) { set_error("bad arguments"); return SRCFD_EINVAL; }

@@ -43,9 +43,11 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 // accumulation-order differences against the float64 oracle (tests: 1e-5 bar; measured 6e-7 on the full model).  A Newton
 // step on the reciprocal (3 more instructions; the training kernels keep it, act_device.h) bought nothing measurable here,
 // and on this chip vector instructions are not hidden behind the f32 MFMAs (tools/microbench8.hip: their times add).
-// For x -> -inf: exp2 = inf, rcp = 0, x * 0 = -0 (no NaN); x -> +inf: exp2 = 0, x * 1.
+// For x < -88: exp2 = inf, rcp = 0, x * 0 = -0 (no NaN); x = +inf: exp2 = 0, x * 1.  x = -inf itself would be -inf * 0 = NaN: the
+// factor in front is held at -FLT_MAX (one v_max_f32; every finite x keeps its bits), so swish(-inf) = -0, the limit.  A NaN stays
+// a NaN through the exponential.  tests/test_gpu_gemm32_forms.py asserts all three on an exact GEMM.
 __device__ __forceinline__ float act_apply_precise(float v, int act) {
-  if (act == SRCFD_ACT_SWISH) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
+  if (act == SRCFD_ACT_SWISH) return fmaxf(v, -3.402823466e38f) * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
   return act_apply(v, act);
 }
 

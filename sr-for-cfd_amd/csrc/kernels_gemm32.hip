@@ -32,7 +32,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int GB_LDA = GB_BK + 1;   // GB_BM x GB_BN x GB_BK: gemm32_plan.h
 
 // x * rcp(1 + exp2(-log2(e) x)): kernels_fp32.hip, act_apply_precise (same expression, same bits)
-__device__ __forceinline__ float gb_swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
+__device__ __forceinline__ float gb_swish(float v) { return fmaxf(v, -3.402823466e38f) * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
 
 template <bool SPLIT>   // SPLIT: some phase sums more than one K slab (needs a second accumulator set)
 __global__ void __launch_bounds__(256) gemm32_big(Gemm32Group g, const float* __restrict__ X, float* __restrict__ Y) {

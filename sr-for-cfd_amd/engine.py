@@ -435,6 +435,13 @@ class SRModel:
         L.check(L.lib.srcfd_model_last_plan(self._h, buf, len(buf)))
         return dict(w.split("=", 1) for w in buf.value.decode().split())
 
+    def f32_steps(self, n: int) -> List[Tuple[str, str, int]]:
+        """Test hook (srcfd_model_f32_steps): (first op's name, kernel, ops) of every step an n-sample f32-grade forward would take
+        under the environment's switches; works on a host-only handle."""
+        buf = C.create_string_buffer(1 << 14)
+        L.check(L.lib.srcfd_model_f32_steps(self._h, int(n), buf, len(buf)))
+        return [(w.rsplit("=", 1)[0],) + (lambda k, c: (k, int(c)))(*w.rsplit("=", 1)[1].split(":")) for w in buf.value.decode().split()]
+
     def set_profiling(self, on: bool):
         L.check(L.lib.srcfd_model_set_profiling(self._h, int(on)))
 

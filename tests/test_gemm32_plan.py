@@ -22,8 +22,13 @@ BATCHES = {0: (1, 3, 7, 64, 216, 768), 1: (1, 2, 3, 4, 5, 6, 7, 8, 32), 2: (1, 2
 
 def read_plan(path):
     """launches of one dump file: dict(mode, n, first, count, grouped, launch, ws, fits, ops=[dict(plan, derived, d)])"""
+    return read_plan_lines(open(path))
+
+
+def read_plan_lines(lines):
+    """the same of G / O lines from anywhere (tests/test_gemm32_forms.py: one case of the forms dump)"""
     launches, by_first = [], {}
-    for line in open(path):
+    for line in lines:
         kind, *v = line.split()
         v = [int(x) for x in v]
         if kind == "G":

@@ -5,6 +5,8 @@
 //   pack_digest <superres.h5> [dump-dir [family.h5]]     dump-dir: raw arrays for the test's property checks, and the training step's
 //   weight-gradient plan as text (dump_train_plan, tests/test_train_plan.py), and the f32 GEMM's launch plan of every graph as text
 //   (PlanDump, tests/test_gemm32_plan.py)
+//   pack_digest --forms <forms.txt> <dump-dir>           only the f32 GEMM launch plan of the layer graphs listed in forms.txt, each at
+//   its own batch size (tests/gemm32_forms.py writes the list, tests/test_gemm32_forms.py reads `forms.gemm32.plan.txt`); prints nothing
 //   family.h5: a whole-model file of another member of the notebook's family (family.py, e.g. encoder_10 + decoder_100, with
 //   padding='same' transposed convolutions); adds `family.*` sections: its f32 plan and the trainer's maps without the fused tail.
 // Which fused kernels a graph qualifies for is decided in engine.hip / fused_bf16.hip / train_tail.hip (HIP translation units this
@@ -221,6 +223,24 @@ struct PlanDump {
     }
     next = first + (int)ds.size();
   }
+  // one case of a forms list: the inference launches of a layer graph at one batch, the ops of a layer together as the engine sends
+  // them.  Behind a line `C name batch`, and behind every launch's G / O lines one line
+  //   B first count layer big      layer: index among the graph's layers; big: gemm32_big_qualifies for these descriptors at that batch
+  void form(const std::string& name, const ModelDesc& md, int n) {
+    if (!f) return;
+    std::vector<Op> ops_;
+    std::vector<float> pack;
+    build_plan(md, ops_, pack);
+    std::fprintf(f, "C %s %d\n", name.c_str(), n);
+    next = 0;
+    for (size_t i = 0, j; i < ops_.size(); i = j) {
+      GemmDesc ds[4];
+      for (j = i; j < ops_.size() && ops_[j].layer == ops_[i].layer && j - i < 4; ++j) { ds[j - i] = ops_[j].d; ds[j - i].M = n * ops_[j].d.MH * ops_[j].d.MW; }
+      launch(0, n, ds, (int)(j - i));
+      std::fprintf(f, "B %d %d %d %d\n", next, (int)(j - i), ops_[i].layer, (int)gemm32_big_qualifies(ds, (int)(j - i)));
+      next += (int)(j - i);
+    }
+  }
   // a layer graph: its forward ops as the engine launches them, as the trainer does (activation left to the epilogue), and the trainer's data gradients
   void graph(const ModelDesc& md) {
     std::vector<Op> ops_;
@@ -374,8 +394,52 @@ static void small_graph(const std::string& tag, ModelDesc md, bool train_plan = 
   }
 }
 
+// The forms list: plain text, one graph after the other (the whole-model .h5 layout holds an encoder / decoder pair of the
+// notebook's family only, which none of these graphs is).  Integers are the enums of include/srcfd.h:
+//   case <name> <batch> <in_h> <in_w> <in_c> <layers>
+//   layer <kind> <activation> <kh> <kw> <stride> <same> <cin> <cout>  x layers; the plan does not read the weights: zeros
+static int dump_forms(const char* list) {
+  FILE* in = std::fopen(list, "r");
+  if (!in) { std::fprintf(stderr, "cannot read %s\n", list); return 2; }
+  PlanDump out("forms.");
+  char name[128];
+  int n, h, w, c, nl, cases = 0;
+  while (std::fscanf(in, " case %127s %d %d %d %d %d", name, &n, &h, &w, &c, &nl) == 6) {
+    ModelDesc md;
+    md.in_shape[0] = h; md.in_shape[1] = w; md.in_shape[2] = c;
+    for (int i = 0; i < nl; ++i) {
+      Layer L;
+      int same;
+      if (std::fscanf(in, " layer %d %d %d %d %d %d %d %d", &L.kind, &L.act, &L.kh, &L.kw, &L.stride, &same, &L.cin, &L.cout) != 8 || L.kh < 0 || L.kw < 0 || L.cin < 0 || L.cout < 0) {
+        std::fprintf(stderr, "%s: bad layer %d of case %s\n", list, i, name);
+        std::fclose(in);
+        return 2;
+      }
+      L.same = same != 0; L.name = "l" + std::to_string(i);
+      if (L.kind != SRCFD_LAYER_FLATTEN) { L.kernel.assign((size_t)L.kh * L.kw * L.cin * L.cout, 0.f); L.bias.assign(L.cout, 0.f); }
+      md.layers.push_back(L);
+    }
+    md.infer_shapes();
+    out.form(name, md, n);
+    ++cases;
+  }
+  const bool whole = std::feof(in) != 0;
+  std::fclose(in);
+  if (!whole || !cases) { std::fprintf(stderr, "%s: not a forms list (stopped behind case %d)\n", list, cases); return 2; }
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: pack_digest <superres.h5> [dump-dir [family.h5]]\n"); return 2; }
+  if (argc == 4 && std::string(argv[1]) == "--forms") {
+    g_dump = argv[3];
+    try {
+      return dump_forms(argv[2]);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "pack_digest: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (argc < 2) { std::fprintf(stderr, "usage: pack_digest <superres.h5> [dump-dir [family.h5]] | pack_digest --forms <forms.txt> <dump-dir>\n"); return 2; }
   if (argc > 2) g_dump = argv[2];
   try {
     std::printf("{\"sections\": [");
