@@ -1,9 +1,11 @@
-// Host side of the bf16 / f16 throughput path: weight repacking (16-bit, log2e folding, MFMA fragment order) and the launches.
+// Host side of the bf16 / f16 throughput path: the device state of both graphs, the uploads of their operands (packed by
+// operand_pack.cpp), the reserve, and the loop that issues a chunk's launches.
 // encoder_10 + decoder_400 (the fused graph) is the four-launch pipeline  enc16 (conv2d .. latent_vector) -> dense1_16 -> mid16
 // (ConvT#0 -> ConvT#1) -> tail16; the layer-by-layer launches they replaced stay reachable (SRCFD_ENC=0, SRCFD_DENSE1=0,
 // SRCFD_MID=0) for the A/B tests.  encoder_10 + the other decoders of the family (any16) run  enc16 -> per layer gemm16
-// (CI % 64 == 0) or gemm16n (CI 16 / 32) -> outconv16.  Both graphs share one device state and reserve (Lowp16State), one
-// encoder stage (run_encoder) and one GEMM step (run_gemm).
+// (CI % 64 == 0) or gemm16n (CI 16 / 32) -> outconv16.  Both graphs share one device state and reserve (Lowp16State).  What a
+// chunk launches -- kernels, buffers, split-K cuts, grids, mid16's shape, the tail's segmentation -- is decided by plan_chunk16
+// (lowp16_plan.h, host only, tested on a CPU); issue_chunk below fills the parameter structs and launches, and decides nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -147,15 +149,14 @@ int fused_debug_read(Model& m, int index, void* dst, size_t bytes) {
 }
 
 // A forward runs chunks of up to 1024 samples through two activation buffers of the graph's largest activation and the split-K
-// slabs of dense (3200 -> 128): up to 16 K-slice slabs of (rows x 128) f32.  gemm16 forms its element offsets into a chunk's
+// slabs (lowp16_slab_elems, lowp16_plan.h: no chunk's plan needs more).  gemm16 forms its element offsets into a chunk's
 // activations in 32-bit int, so a chunk holds fewer samples where 1024 of the graph's largest activation would pass 2^31 elements
 // (any16_plan refuses a single activation of that size; the fused graph's 1024 x 160000 is far below).
 int lowp16_chunk_cap(const Model& m) { return (int)std::min<size_t>(1024, (((size_t)1 << 31) - 1) / act_elems(m)); }
 static size_t chunk_of(const Model& m, int n) { return (size_t)std::min(std::max(n, 0), lowp16_chunk_cap(m)); }
-static size_t slab_elems(size_t want) { return 16 * want * 128; }
 size_t lowp16_workspace_bytes(const Model& m, int n) {
   const size_t want = chunk_of(m, n);
-  return want ? 2 * want * act_elems(m) * sizeof(uint16_t) + slab_elems(want) * sizeof(float) : 0;
+  return want ? 2 * want * act_elems(m) * sizeof(uint16_t) + lowp16_slab_elems(want) * sizeof(float) : 0;
 }
 
 // Everything the 16-bit forward of an n-sample batch allocates or packs lazily: the operand packs of the current operand
@@ -170,7 +171,7 @@ int lowp16_reserve(Model& m, int n) {
     m.drop_graph();  // a captured forward holds the old buffers' addresses
     st->cap = 0;
     for (auto& b : st->act) { rc = b.alloc((size_t)want * act_elems(m)); if (rc) return rc; }
-    rc = st->d_part.alloc(slab_elems(want));
+    rc = st->d_part.alloc(lowp16_slab_elems(want));
     if (rc) return rc;
     st->cap = want;
   }
@@ -266,152 +267,103 @@ static int diag_tail_arm(TailParams&) { return SRCFD_OK; }
 static int diag_tail_report(bool, hipStream_t) { return SRCFD_OK; }
 #endif
 
-// One chunk of c samples on its way through the two activation buffers: act[cur] is what the next launch reads.
-struct Chunk16 {
-  Model& m;
-  Lowp16State& st;
-  const Dev16& P;
-  const bool f16;
-  const int c;
-  hipStream_t s;
-  int cur = 0, prev_layer = -1;
-  uint16_t* buf(int i) const { return st.act[i].get(); }
-};
-
-// The encoder front: enc16 (conv2d .. latent_vector in one launch), or conv2d alone when the encoder runs layer by layer.
-static int run_encoder(Chunk16& k, bool use_enc, const float* xin, const float* ain) {
-  const Plan16& h = k.st.plan;
-  const float* const d_f32 = k.st.d_f32.get();
-  if (!use_enc) return k.m.launch("conv2d", k.s, [&] { return launch_enc_conv1_16(k.f16, xin, ain, d_f32 + h.c1w_off, d_f32 + h.c1b_off, k.buf(0), k.c, k.s); });
-  EncParams ep;
-  ep.x = xin; ep.affine = ain; ep.n = k.c;
-  ep.w1 = d_f32 + h.c1w_off; ep.b1 = d_f32 + h.c1b_off;
-  ep.w2f = k.P.d_encf.get(); ep.b2f = k.P.d_encb.get();
-  ep.wdf = (const char*)k.P.d_encf.get() + k.P.enc_wd_off; ep.bd = d_f32 + h.ops[1].b_off;
-  ep.wlf = (const char*)k.P.d_encf.get() + k.P.enc_wl_off; ep.bl = d_f32 + h.ops[2].b_off;
-  ep.z = k.buf(1);
-  ep.act_dense = h.ops[1].d.act; ep.act_latent = h.ops[2].d.act;
-  ep.prof = nullptr;
-  int rc = k.m.has_fused ? diag_enc_arm(ep) : SRCFD_OK;   // the section timers are the fused graph's
-  if (!rc) rc = k.m.launch("encoder(conv2d..latent_vector)", k.s, [&] { return launch_enc16(k.f16, ep, k.s); });
-  if (!rc && k.m.has_fused) rc = diag_enc_report(k.s);
-  k.cur = 1;   // where the layer-by-layer chain leaves the latent vectors, too
-  return rc;
-}
-
-// One GEMM op of the chain.  The ops of one layer (the output phases of a transposed convolution) read and write the same buffers.
-static int run_gemm(Chunk16& k, const Op16& o, bool use_d1) {
-  if (o.layer != k.prev_layer && k.prev_layer >= 0) k.cur ^= 1;
-  k.prev_layer = o.layer;
-  GemmDesc d = o.d;
-  d.M = k.c * d.MH * d.MW;
-  const uint16_t* X = k.buf(k.cur);
-  uint16_t* Y = k.buf(k.cur ^ 1);
-  const uint16_t* W = k.P.d_w.get() + o.w_off;
-  const float* bias = k.st.d_f32.get() + o.b_off;
-  if (use_d1 && o.layer == 4 && dense1_16_qualifies(d, o.Kpad))
-    return k.m.launch(o.name.c_str(), k.s, [&] { return launch_dense1_16(k.f16, d, X, W, bias, Y, k.s); });
-  // a narrow op (CI 16 / 32) exists on the any16 graphs only: fused_init refuses CI % 64 != 0
-  if (any16_narrow(d)) return k.m.launch(o.name.c_str(), k.s, [&] { return launch_gemm16n(k.f16, d, X, W, o.Kpad, bias, Y, k.s); });
-  // dense layers with few rows and a long K: split K over workgroups (f32 slabs + finish kernel).  The finish kernel stores row m
-  // at Y + m OC: a layer with a 1x1 OUTPUT.  One row per sample alone does not say that -- the phase ops of a transposed
-  // convolution on a one-pixel image have it too, and their rows go to (oy0, ox0) of a 2x2 image.
-  int splits = 1;
-  if (d.OH == 1 && d.OW == 1 && d.MH == 1 && d.MW == 1 && d.K >= 1024) splits = std::max(1, std::min(16, d.K / 256));
-  if (splits > 1 && (size_t)splits * d.M * d.Npad > k.st.d_part.size()) splits = 1;
-  return k.m.launch(o.name.c_str(), k.s, [&] { return launch_gemm16(k.f16, d, X, W, o.Kpad, bias, Y, k.st.d_part.get(), splits, k.s); });
-}
-
-static int fused_chunk(Chunk16& k, FusedState& fs, const float* xin, const float* ain, const float* aout, void* y, int out_dtype, int flags,
-                       unsigned long long* nonfinite) {
-  Model& m = k.m;
-  const FusedState::Dev& X = fs.fx[k.f16 ? 1 : 0];
-  // functional A/B switches of the tests (both implementations of the encoder, of dense_1 and of the network's middle are complete):
-  // read once per call by Model::predict_device (Switches, engine.h), part of the hipGraph key
-  const bool use_enc = fs.enc_ok && m.sw.enc16;   // false: layer-by-layer encoder
-  const bool use_mid = m.sw.mid16;                // false: generic GEMMs
-  int rc = run_encoder(k, use_enc, xin, ain);
-  if (rc) return rc;
-  for (const Op16& o : fs.plan.ops) {
-    if (use_enc && o.layer < 4) continue;  // conv2d_1, dense, latent_vector ran inside enc16
-    if (use_mid && o.layer >= 5) break;    // ConvT#0 / ConvT#1 run in the fused mid kernel below
-    if ((rc = run_gemm(k, o, m.sw.dense1_16))) return rc;   // SRCFD_DENSE1=0: dense_1 on the generic GEMM
-  }
-  if (use_mid) {
-    k.cur ^= 1;  // dense_1 output
-    MidParams mp;
-    mp.in = k.buf(k.cur);
-    mp.out = k.buf(k.cur ^ 1);
-    mp.n = k.c;
-    int ph = 0;
-    for (const Op16& o : fs.plan.ops)
-      if (o.layer == 5) { mp.w0[ph] = k.P.d_w.get() + o.w_off; mp.kpad[ph] = o.Kpad; mp.w0t[ph] = X.d_w0t.get() + X.w0t_off[ph]; ++ph; }
-    mp.b0f = X.d_midb.get();
-    mp.w1f = X.d_w1f.get();
-    mp.b1f = X.d_midb.get() + 128;
-    mp.ablate = 0;
-    mp.order = m.sw.mid_order;
-    mp.prof = nullptr;
-    if ((rc = diag_mid_arm(mp, k.s))) return rc;
-    const int mid_waves = m.sw.mid_waves ? m.sw.mid_waves : (m.sw.mid_shape == 1 ? 8 : m.sw.mid_shape == 2 ? 82 : 42);
-    rc = m.launch("mid(convT0+convT1)", k.s, [&] { return launch_mid16(k.f16, mp, mid_waves, k.s); });
-    if (!rc) rc = diag_mid_report(k.s);
+// Issues the steps of one chunk's plan (lowp16_plan.h): fills each kernel's parameters from the device state and launches under the
+// names the profile reports.  Every decision -- kernels, buffers, cuts, grids, shapes, segmentation -- is the plan's.
+static int issue_chunk(Model& m, Lowp16State& st, const Chunk16Plan& plan, bool f16, int c, const float* xin, const float* ain, const float* aout,
+                       void* y, int out_dtype, int flags, unsigned long long* nonfinite, hipStream_t s) {
+  const Plan16& h = st.plan;
+  const Dev16& P = st.dev[f16 ? 1 : 0];
+  const float* const d_f32 = st.d_f32.get();
+  for (const Step16& q : plan.steps) {
+    const uint16_t* const X = q.src >= 0 ? st.act[q.src].get() : nullptr;
+    uint16_t* const Y = q.dst >= 0 ? st.act[q.dst].get() : nullptr;
+    const Op16* const o = q.nops ? &h.ops[q.op0] : nullptr;
+    int rc = SRCFD_OK;
+    switch (q.k) {
+      case Kernel16::EncConv1:
+        rc = m.launch("conv2d", s, [&] { return launch_enc_conv1_16(f16, xin, ain, d_f32 + h.c1w_off, d_f32 + h.c1b_off, Y, c, q.grid[0], s); });
+        break;
+      case Kernel16::Enc: {
+        EncParams ep;
+        ep.x = xin; ep.affine = ain; ep.n = c;
+        ep.w1 = d_f32 + h.c1w_off; ep.b1 = d_f32 + h.c1b_off;
+        ep.w2f = P.d_encf.get(); ep.b2f = P.d_encb.get();
+        ep.wdf = (const char*)P.d_encf.get() + P.enc_wd_off; ep.bd = d_f32 + h.ops[1].b_off;
+        ep.wlf = (const char*)P.d_encf.get() + P.enc_wl_off; ep.bl = d_f32 + h.ops[2].b_off;
+        ep.z = Y;
+        ep.act_dense = h.ops[1].d.act; ep.act_latent = h.ops[2].d.act;
+        ep.prof = nullptr;
+        rc = m.has_fused ? diag_enc_arm(ep) : SRCFD_OK;   // the section timers are the fused graph's
+        if (!rc) rc = m.launch("encoder(conv2d..latent_vector)", s, [&] { return launch_enc16(f16, ep, q.grid[0], s); });
+        if (!rc && m.has_fused) rc = diag_enc_report(s);
+        break;
+      }
+      case Kernel16::Dense1:
+        rc = m.launch(o->name.c_str(), s, [&] { return launch_dense1_16(f16, q.d, X, P.d_w.get() + o->w_off, d_f32 + o->b_off, Y, q.grid[0], s); });
+        break;
+      case Kernel16::GemmN:
+        rc = m.launch(o->name.c_str(), s, [&] { return launch_gemm16n(f16, q.d, X, P.d_w.get() + o->w_off, o->Kpad, d_f32 + o->b_off, Y, q.grid, s); });
+        break;
+      case Kernel16::Gemm:
+        rc = m.launch(o->name.c_str(), s, [&] {
+          // the reserve holds every plan's slabs (tests/test_lowp16_plan.py); a buffer that did not is withheld, and the launcher refuses
+          float* const part = q.cut.slab_floats <= st.d_part.size() ? st.d_part.get() : nullptr;
+          return launch_gemm16(f16, q.d, X, P.d_w.get() + o->w_off, o->Kpad, d_f32 + o->b_off, Y, part, q.cut, s);
+        });
+        break;
+      case Kernel16::Mid: {
+        const FusedState::Dev& F = fused_of(st).fx[f16 ? 1 : 0];
+        MidParams mp;
+        mp.in = X; mp.out = Y; mp.n = c;
+        int ph = 0;
+        for (int i = q.op0; i < q.op0 + q.nops; ++i)
+          if (h.ops[i].layer == 5) { mp.w0[ph] = P.d_w.get() + h.ops[i].w_off; mp.kpad[ph] = h.ops[i].Kpad; mp.w0t[ph] = F.d_w0t.get() + F.w0t_off[ph]; ++ph; }
+        mp.b0f = F.d_midb.get();
+        mp.w1f = F.d_w1f.get();
+        mp.b1f = F.d_midb.get() + 128;
+        std::copy(q.nblk, q.nblk + 4, mp.nblk);
+        mp.ablate = 0;
+        mp.order = m.sw.mid_order;
+        mp.prof = nullptr;
+        rc = diag_mid_arm(mp, s);
+        if (!rc) rc = m.launch("mid(convT0+convT1)", s, [&] { return launch_mid16(f16, mp, q.shape, s); });
+        if (!rc) rc = diag_mid_report(s);
+        break;
+      }
+      case Kernel16::Tail:
+      case Kernel16::TailS: {
+        const FusedState::Dev& F = fused_of(st).fx[f16 ? 1 : 0];
+        const bool tail_s = q.k == Kernel16::TailS;
+        TailParams tp;
+        tp.in = X; tp.out = y; tp.n = c;
+        tp.consts = F.d_consts.get();
+        tp.w2frags = F.d_w2f.get();
+        tp.aff_out = aout;
+        tp.nan_guard = flags & SRCFD_FLAG_NAN_GUARD;
+        tp.nonfinite = nonfinite;
+        tp.out_dtype = out_dtype;
+        tp.ablate = 0;
+        tp.prof = nullptr;
+        tp.seg = q.seg;
+        rc = diag_tail_arm(tp);
+        if (!rc) rc = m.launch("tail(convT2-4+out)", s, [&] { return tail_s ? launch_tail16s(f16, tp, q.blocks, s) : launch_tail16(f16, tp, q.blocks, s); });
+        if (!rc) rc = diag_tail_report(tail_s, s);
+        break;
+      }
+      case Kernel16::OutConv: {
+        const Any16State& as = any16_of(st);
+        OutConv16Params op;
+        op.in = X; op.out = y;
+        op.n = c; op.H = as.out.out_H; op.W = as.out.out_W; op.C = as.out.out_C;
+        op.w = as.d_wout[f16 ? 1 : 0].get(); op.bias = as.out.out_bias;
+        op.aff_out = aout; op.nan_guard = flags & SRCFD_FLAG_NAN_GUARD; op.nonfinite = nonfinite; op.out_dtype = out_dtype;
+        rc = m.launch(m.desc.layers[h.cl.back()].name.c_str(), s, [&] { return launch_outconv16(f16, op, q.grid[0], s); });
+        break;
+      }
+    }
     if (rc) return rc;
   }
-  k.cur ^= 1;
-  fs.t1_buf = k.cur;
-  TailParams tp;
-  tp.in = k.buf(k.cur);
-  tp.out = y;
-  tp.n = k.c;
-  tp.consts = X.d_consts.get();
-  tp.w2frags = X.d_w2f.get();
-  tp.aff_out = aout;
-  tp.nan_guard = flags & SRCFD_FLAG_NAN_GUARD;
-  tp.nonfinite = nonfinite;
-  tp.out_dtype = out_dtype;
-  tp.ablate = 0;
-  tp.prof = nullptr;
-  if ((rc = diag_tail_arm(tp))) return rc;
-  // Batches that do not fill the chip evenly (fewer samples than CUs, or a few more than a multiple of them): cut each
-  // sample into S segments so that the longest workgroup walks fewer strips.  Cost of a choice = strips walked by the
-  // busiest workgroup: ceil(n S / CUs) virtual samples of 50/S (+1 warm-up) strips, + 2 rounds of pipeline depth.
-  int seg = 1;
-  if (m.sw.tail_seg) seg = m.sw.tail_seg;   // SRCFD_TAIL_SEG (tests, tools): read per call, reported by srcfd_model_last_plan
-  else {
-    long best = ((long)(k.c + m.num_cus - 1) / m.num_cus) * 50 + 2;
-    for (int cand : {2, 5, 10, 25}) {
-      long cost = ((long)((long)k.c * cand + m.num_cus - 1) / m.num_cus) * (50 / cand + 1) + 2;
-      if (cost * 115 < best * 100) { best = cost; seg = cand; }  // warm-up strips and extra workgroups are not free: ask for 15 %
-    }
-  }
-  if (seg != 1 && seg != 2 && seg != 5 && seg != 10 && seg != 25) seg = 1;
-  tp.seg = seg;
-  m.plan.tail_seg = seg;
-  const int blocks = std::min(k.c * seg, m.num_cus);
-  const bool tail_s = m.sw.tail16s;
-  rc = m.launch("tail(convT2-4+out)", k.s, [&] { return tail_s ? launch_tail16s(k.f16, tp, blocks, k.s) : launch_tail16(k.f16, tp, blocks, k.s); });
-  return rc ? rc : diag_tail_report(tail_s, k.s);
-}
-
-static int any16_chunk(Chunk16& k, Any16State& as, const float* xin, const float* ain, const float* aout, void* y, int out_dtype, int flags,
-                       unsigned long long* nonfinite) {
-  Model& m = k.m;
-  const bool use_enc = m.sw.enc16;   // false: layer-by-layer encoder (functional A/B switch, part of the hipGraph key)
-  int rc = run_encoder(k, use_enc, xin, ain);
-  if (rc) return rc;
-  for (const Op16& o : as.plan.ops) {
-    if (use_enc && o.layer < 4) continue;  // conv2d_1, dense, latent_vector ran inside enc16
-    if ((rc = run_gemm(k, o, false))) return rc;
-  }
-  k.cur ^= 1;   // the last GEMM layer's output
-  OutConv16Params op;
-  op.in = k.buf(k.cur);
-  op.out = y;
-  op.n = k.c; op.H = as.out.out_H; op.W = as.out.out_W; op.C = as.out.out_C;
-  op.w = as.d_wout[k.f16 ? 1 : 0].get(); op.bias = as.out.out_bias;
-  op.aff_out = aout; op.nan_guard = flags & SRCFD_FLAG_NAN_GUARD; op.nonfinite = nonfinite; op.out_dtype = out_dtype;
-  return m.launch(m.desc.layers[as.plan.cl.back()].name.c_str(), k.s, [&] { return launch_outconv16(k.f16, op, k.s); });
+  return SRCFD_OK;
 }
 
 int lowp16_forward(Model& m, const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
@@ -422,14 +374,19 @@ int lowp16_forward(Model& m, const float* x_dev, int n, const float* aff_in, con
   const bool f16 = m.precision == SRCFD_PREC_F16;
   const int* os = m.desc.out_shape();
   const size_t out_bytes = (size_t)os[0] * os[1] * os[2] * (out_dtype == SRCFD_F32 ? 4 : 2);   // per sample
+  Graph16 g;
+  g.fused = m.has_fused;
+  if (m.has_fused) g.enc_ok = fused_of(st).enc_ok;
+  else { g.out_H = any16_of(st).out.out_H; g.out_W = any16_of(st).out.out_W; }
   for (int i0 = 0; i0 < n; i0 += st.cap) {
-    Chunk16 k{m, st, st.dev[f16 ? 1 : 0], f16, std::min(st.cap, n - i0), s};
+    const int c = std::min(st.cap, n - i0);
+    const Chunk16Plan plan = plan_chunk16(st.plan, g, m.sw, c, m.num_cus);
+    if (m.has_fused) { fused_of(st).t1_buf = plan.t1_buf; m.plan.tail_seg = plan.tail_seg; }
     const float* xin = x_dev + (size_t)i0 * 100;
     const float* ain = aff_in ? aff_in + 2 * (size_t)i0 : nullptr;
     const float* aout = aff_out ? aff_out + 2 * (size_t)i0 : nullptr;
     void* y = (char*)y_dev + (size_t)i0 * out_bytes;
-    rc = m.has_fused ? fused_chunk(k, fused_of(st), xin, ain, aout, y, out_dtype, flags, nonfinite)
-                     : any16_chunk(k, any16_of(st), xin, ain, aout, y, out_dtype, flags, nonfinite);
+    rc = issue_chunk(m, st, plan, f16, c, xin, ain, aout, y, out_dtype, flags, nonfinite, s);
     if (rc) return rc;
   }
   return SRCFD_OK;

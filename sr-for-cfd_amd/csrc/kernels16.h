@@ -1,4 +1,5 @@
-// Declarations shared by kernels_bf16.hip (device) and fused_bf16.hip (host).
+// Declarations shared by the 16-bit kernel files (device) and fused_bf16.hip (host).  The launchers issue what the chunk plan
+// (lowp16_plan.h) says: they take its grids, cuts and shapes and hold no sizing arithmetic of their own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "lowp16_plan.h"
 
 namespace srcfd {
 
@@ -60,15 +62,14 @@ struct MidParams {
   const float* b0f;        // ConvT#0 bias as accumulator init [m-tile 4][lane half 2][16]
   const void* w1f;         // ConvT#1 A operands [m-tile 8][k-step 8][64 lanes] x 16 B, k in accumulator order
   const float* b1f;        // ConvT#1 bias as accumulator init [channel half 2][lane half 2][16]
-  int nblk[4];             // workgroups per output phase (filled by launch_mid16)
+  int nblk[4];             // workgroups per output phase (Step16::nblk)
   int order;               // 0: phase by phase; 1: phases 0 / 3 and 1 / 2 alternating (SRCFD_MID_ORDER, A/B)
   int ablate;              // diagnostic (SRCFD_MID_ABLATE): 1 no main-loop MFMA, 2 no ConvT#1 stage, 4 no operand loads, 8 no global stores, 16 no ConvT#1 swish
   unsigned long long* prof;  // diagnostic (SRCFD_MID_PROF, DIAG builds): per phase [4][6]: workgroups, cycles entry -> tables, -> first stage ready, main loop, ConvT#0 swish, ConvT#1 stage; else null
 };
-hipError_t launch_mid16(bool f16, const MidParams& p, int waves /*4, 8 or 16 per workgroup*/, hipStream_t s);
+hipError_t launch_mid16(bool f16, const MidParams& p, MidShape shape, hipStream_t s);
 
 // The whole encoder in one launch (kernels_enc16.hip): conv2d -> conv2d_1 -> dense -> latent_vector
-constexpr int ENC_G = 5;   // samples per workgroup
 struct EncParams {
   const float* x;          // (n,10,10,1) f32
   const float* affine;     // (n,2) mean,std or null
@@ -85,23 +86,24 @@ struct EncParams {
   int act_dense, act_latent;
   unsigned long long* prof;  // diagnostic (-DSRCFD_DIAG, SRCFD_ENC_PROF): cycle stamps of workgroup 7 [8 waves][8], else null
 };
-hipError_t launch_enc16(bool f16, const EncParams& p, hipStream_t s);
-// Dense with one 64-deep k tile and N a multiple of 144 (dense_1: 64 -> 36 864): one workgroup per 144 features, all samples
-bool dense1_16_qualifies(const GemmDesc& d, int Kpad);
-hipError_t launch_dense1_16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, const float* bias, uint16_t* Y, hipStream_t s);
+hipError_t launch_enc16(bool f16, const EncParams& p, unsigned grid, hipStream_t s);
+// for what dense1_16_qualifies (lowp16_plan.h) accepts
+hipError_t launch_dense1_16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, const float* bias, uint16_t* Y, unsigned grid, hipStream_t s);
 
-hipError_t launch_enc_conv1_16(bool f16, const float* x, const float* affine, const float* w, const float* b, uint16_t* y, int n, hipStream_t s);
-// part/splits: optional split-K (dense layers with few rows): one f32 slab (M x Npad) per K slice in `part`,
-// summed in slice order by a finish kernel (deterministic)
+hipError_t launch_enc_conv1_16(bool f16, const float* x, const float* affine, const float* w, const float* b, uint16_t* y, int n, unsigned grid, hipStream_t s);
+// cut: the planned launch (lowp16_plan.h).  A split cut (dense layers with few rows) writes one f32 slab (M x Npad) per K slice into
+// `part`, summed in slice order by a finish kernel (deterministic); without `part` it is refused with hipErrorInvalidValue before
+// anything is launched (an unsplit GEMM would sum in another order)
 hipError_t launch_gemm16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y,
-                         float* part, int splits, hipStream_t s);
+                         float* part, const Gemm16Cut& cut, hipStream_t s);
 hipError_t launch_tail16(bool f16, const TailParams& p, int blocks, hipStream_t s);    // shipped kernel (kernels_bf16.hip): 16 waves, stage by stage
 hipError_t launch_tail16s(bool f16, const TailParams& p, int blocks, hipStream_t s);   // second implementation (kernels_tail16s.hip, SRCFD_TAIL=s): 8 waves, MFMAs inside the swish stream
 int tail_lds_bytes();
 
 // kernels_any16.hip: the 16-bit kernels of the family graphs outside encoder_10 + decoder_400
 // Implicit GEMM for CI 16 / 32 (k-step 16); Wt[Npad][Kpad] with Npad % 32 == 0, bias[Npad]; same GemmDesc as launch_gemm16
-hipError_t launch_gemm16n(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y, hipStream_t s);
+hipError_t launch_gemm16n(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y, const unsigned grid[2],
+                          hipStream_t s);
 struct OutConv16Params {
   const uint16_t* in;      // (n, H, W, C) 16-bit NHWC, C % 8 == 0, C <= 64
   void* out;               // (n, H, W) of out_dtype
@@ -113,6 +115,6 @@ struct OutConv16Params {
   unsigned long long* nonfinite;
   int out_dtype;
 };
-hipError_t launch_outconv16(bool f16, const OutConv16Params& p, hipStream_t s);
+hipError_t launch_outconv16(bool f16, const OutConv16Params& p, unsigned grid, hipStream_t s);
 
 }  // namespace srcfd

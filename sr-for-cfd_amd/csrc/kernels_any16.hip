@@ -68,10 +68,11 @@ __global__ void __launch_bounds__(256) gemm16n(GemmDesc d, const uint16_t* __res
   }
 }
 
-hipError_t launch_gemm16n(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y, hipStream_t s) {
+hipError_t launch_gemm16n(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y, const unsigned g[2],
+                          hipStream_t s) {
   if (d.M == 0) return hipSuccess;
   if (d.CI % 16 != 0 || d.K % 16 != 0 || d.Npad % 32 != 0 || d.N % 4 != 0 || d.CO % 4 != 0 || d.OC % 4 != 0 || Kpad % 8 != 0) return hipErrorInvalidValue;
-  const dim3 grid((d.M + 127) / 128, d.Npad / 32);
+  const dim3 grid(g[0], g[1]);
   if (f16) hipLaunchKernelGGL(gemm16n<true>, grid, dim3(256), 0, s, d, X, Wt, Kpad, bias, Y);
   else hipLaunchKernelGGL(gemm16n<false>, grid, dim3(256), 0, s, d, X, Wt, Kpad, bias, Y);
   return hipGetLastError();
@@ -136,11 +137,10 @@ __global__ void __launch_bounds__(256) outconv16(OutConv16Params p) {
   }
 }
 
-hipError_t launch_outconv16(bool f16, const OutConv16Params& p, hipStream_t s) {
+hipError_t launch_outconv16(bool f16, const OutConv16Params& p, unsigned blocks, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
   if (p.C % 8 != 0 || p.C > 64 || p.C <= 0) return hipErrorInvalidValue;
-  const int64_t total = (int64_t)p.n * p.H * p.W;
-  const dim3 grid((unsigned)((total + 255) / 256));
+  const dim3 grid(blocks);
 #define GO(F, O) hipLaunchKernelGGL((outconv16<F, O>), grid, dim3(256), 0, s, p)
   if (f16) { if (p.out_dtype == SRCFD_F32) GO(true, 0); else if (p.out_dtype == SRCFD_BF16) GO(true, 1); else GO(true, 2); }
   else { if (p.out_dtype == SRCFD_F32) GO(false, 0); else if (p.out_dtype == SRCFD_BF16) GO(false, 1); else GO(false, 2); }

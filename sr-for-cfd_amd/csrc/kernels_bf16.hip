@@ -73,6 +73,7 @@ __global__ void __launch_bounds__(256) enc_conv1_16(const float* __restrict__ x,
 // (zeroed by the caller); splitk_finish16 applies bias + activation.
 // ---------------------------------------------------------------------------
 constexpr int G_BP = 128, G_BK = 64, G_PITCH = 72;
+static_assert(G_BP == GEMM16_BP && G_BK == GEMM16_BK, "the chunk plan (lowp16_plan.h) cuts gemm16's grid and K slices with these");
 
 template <bool F16, int BN, bool SPLITK>
 __global__ void __launch_bounds__(256, BN == 128 ? 3 : 4) gemm16(GemmDesc d, const uint16_t* __restrict__ X, const uint16_t* __restrict__ Wt, int Kpad,
@@ -787,26 +788,22 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-hipError_t launch_enc_conv1_16(bool f16, const float* x, const float* affine, const float* w, const float* b, uint16_t* y, int n, hipStream_t s) {
+hipError_t launch_enc_conv1_16(bool f16, const float* x, const float* affine, const float* w, const float* b, uint16_t* y, int n, unsigned grid, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 grid((n * 25 * 16 + 255) / 256);
-  if (f16) hipLaunchKernelGGL(enc_conv1_16<true>, grid, dim3(256), 0, s, x, affine, w, b, y, n);
-  else hipLaunchKernelGGL(enc_conv1_16<false>, grid, dim3(256), 0, s, x, affine, w, b, y, n);
+  if (f16) hipLaunchKernelGGL(enc_conv1_16<true>, dim3(grid), dim3(256), 0, s, x, affine, w, b, y, n);
+  else hipLaunchKernelGGL(enc_conv1_16<false>, dim3(grid), dim3(256), 0, s, x, affine, w, b, y, n);
   return hipGetLastError();
 }
 
 static int gemm16_lds(int bn) { return (G_BP + bn) * G_PITCH * 2 + 3 * G_BP * 4; }
 
 hipError_t launch_gemm16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, int Kpad, const float* bias, uint16_t* Y,
-                         float* part, int splits, hipStream_t s) {
+                         float* part, const Gemm16Cut& cut, hipStream_t s) {
   if (d.M == 0) return hipSuccess;
-  const bool wide = d.Npad % 128 == 0;
-  const int bn = wide ? 128 : 64;
-  const bool sk = splits > 1 && part != nullptr;
-  int kslice = d.K;
-  if (sk) kslice = ((d.K / G_BK + splits - 1) / splits) * G_BK;
-  const int nz = sk ? (d.K + kslice - 1) / kslice : 1;
-  dim3 grid((d.M + G_BP - 1) / G_BP, d.Npad / bn, nz);
+  const bool wide = cut.bn == 128;
+  const bool sk = cut.splits > 1;
+  if (sk && part == nullptr) return hipErrorInvalidValue;
+  const dim3 grid(cut.grid[0], cut.grid[1], cut.grid[2]);
   void (*fn)(GemmDesc, const uint16_t*, const uint16_t*, int, const float*, uint16_t*, float*, int) = nullptr;
   int slot = (f16 ? 4 : 0) + (wide ? 2 : 0) + (sk ? 1 : 0);
   switch (slot) {
@@ -819,15 +816,14 @@ hipError_t launch_gemm16(bool f16, const GemmDesc& d, const uint16_t* X, const u
     case 6: fn = gemm16<true, 128, false>; break;
     default: fn = gemm16<true, 128, true>; break;
   }
-  const int lds = gemm16_lds(bn);
+  const int lds = gemm16_lds(cut.bn);
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(fn), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, d, X, Wt, Kpad, bias, Y, part, kslice);
+  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, d, X, Wt, Kpad, bias, Y, part, cut.kslice);
   e = hipGetLastError();
   if (e != hipSuccess || !sk) return e;
-  const int total = d.M * (d.N / 4);
-  if (f16) hipLaunchKernelGGL(splitk_finish16<true>, dim3((total + 255) / 256), dim3(256), 0, s, part, nz, bias, Y, d.M, d.N, d.Npad, d.OC, d.act);
-  else hipLaunchKernelGGL(splitk_finish16<false>, dim3((total + 255) / 256), dim3(256), 0, s, part, nz, bias, Y, d.M, d.N, d.Npad, d.OC, d.act);
+  if (f16) hipLaunchKernelGGL(splitk_finish16<true>, dim3(cut.fin), dim3(256), 0, s, part, cut.nz, bias, Y, d.M, d.N, d.Npad, d.OC, d.act);
+  else hipLaunchKernelGGL(splitk_finish16<false>, dim3(cut.fin), dim3(256), 0, s, part, cut.nz, bias, Y, d.M, d.N, d.Npad, d.OC, d.act);
   return hipGetLastError();
 }
 

@@ -261,12 +261,12 @@ __global__ void __launch_bounds__(E_NTHR, 1) enc16(EncParams p) {
 #endif
 }
 
-hipError_t launch_enc16(bool f16, const EncParams& p, hipStream_t s) {
+hipError_t launch_enc16(bool f16, const EncParams& p, unsigned grid, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
   void (*fn)(EncParams) = f16 ? enc16<true> : enc16<false>;
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(fn), E_LDS);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, dim3((p.n + E_G - 1) / E_G), dim3(E_NTHR), E_LDS, s, p);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(E_NTHR), E_LDS, s, p);
   return hipGetLastError();
 }
 
@@ -284,6 +284,7 @@ namespace srcfd {
 // transpose as 288-byte runs per sample.  No workgroup barrier anywhere.
 // ---------------------------------------------------------------------------
 constexpr int D1_FT = 9, D1_NF = D1_FT * 16;      // feature tiles / features per workgroup
+static_assert(D1_NF == DENSE1_NF, "dense1_16_qualifies and the chunk plan's grid (lowp16_plan.h) count features per workgroup with this");
 constexpr int D1_PITCH = D1_NF * 2 + 16;          // LDS row pitch of the transpose tile, bytes
 constexpr int D1_WAVES = 8;
 constexpr int D1_LDS = D1_WAVES * 16 * D1_PITCH;
@@ -343,14 +344,10 @@ __global__ void __launch_bounds__(64 * D1_WAVES, 1) dense1_16(const uint16_t* __
   }
 }
 
-bool dense1_16_qualifies(const GemmDesc& d, int Kpad) {
-  return d.MH == 1 && d.MW == 1 && d.K == 64 && Kpad == 64 && d.N == d.Npad && d.N % D1_NF == 0 && d.OC == d.N && d.CI == 64;
-}
-
-hipError_t launch_dense1_16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, const float* bias, uint16_t* Y, hipStream_t s) {
+hipError_t launch_dense1_16(bool f16, const GemmDesc& d, const uint16_t* X, const uint16_t* Wt, const float* bias, uint16_t* Y, unsigned grid, hipStream_t s) {
   if (d.M == 0) return hipSuccess;
   void (*fn)(const uint16_t*, const uint16_t*, const float*, uint16_t*, int, int, int) = f16 ? dense1_16<true> : dense1_16<false>;
-  hipLaunchKernelGGL(fn, dim3(d.N / D1_NF), dim3(64 * D1_WAVES), D1_LDS, s, X, Wt, bias, Y, d.M, d.N, d.act);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * D1_WAVES), D1_LDS, s, X, Wt, bias, Y, d.M, d.N, d.act);
   return hipGetLastError();
 }
 

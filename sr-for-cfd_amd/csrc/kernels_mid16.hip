@@ -432,21 +432,23 @@ static hipError_t launch_mid16_nw(const MidParams& p, hipStream_t s) {
   void (*fn)(MidParams) = mid16<F16, NW, PT>;
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(fn), C::LDS);
   if (e != hipSuccess) return e;
-  MidParams q = p;
-  const int per[4] = {169, 156, 156, 144};   // pixels per sample and output phase (13x13, 13x12, 12x13, 12x12)
-  int total = 0;
-  for (int ph = 0; ph < 4; ++ph) { q.nblk[ph] = (p.n * per[ph] + C::PX - 1) / C::PX; total += q.nblk[ph]; }
-  hipLaunchKernelGGL(fn, dim3(total), dim3(C::NTHR), C::LDS, s, q);
+  hipLaunchKernelGGL(fn, dim3(p.nblk[0] + p.nblk[1] + p.nblk[2] + p.nblk[3]), dim3(C::NTHR), C::LDS, s, p);
   return hipGetLastError();
 }
 
-hipError_t launch_mid16(bool f16, const MidParams& p, int waves, hipStream_t s) {
+// the chunk plan (lowp16_plan.h) counts a phase's workgroups with these
+static_assert(MidCfg<4>::PX == MID_PX[(int)MidShape::W4] && MidCfg<8>::PX == MID_PX[(int)MidShape::W8] && MidCfg<16>::PX == MID_PX[(int)MidShape::W16] &&
+              MidCfg<4, 2>::PX == MID_PX[(int)MidShape::W4x2] && MidCfg<8, 2>::PX == MID_PX[(int)MidShape::W8x2], "pixels per workgroup of mid16's five shapes");
+
+hipError_t launch_mid16(bool f16, const MidParams& p, MidShape shape, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  if (waves == 4) return f16 ? launch_mid16_nw<true, 4>(p, s) : launch_mid16_nw<false, 4>(p, s);
-  if (waves == 16) return f16 ? launch_mid16_nw<true, 16>(p, s) : launch_mid16_nw<false, 16>(p, s);
-  if (waves == 42) return f16 ? launch_mid16_nw<true, 4, 2>(p, s) : launch_mid16_nw<false, 4, 2>(p, s);   // 4 waves x 2 pixel tiles: 256 pixels per workgroup, two per CU, one wave of either on a SIMD
-  if (waves == 82) return f16 ? launch_mid16_nw<true, 8, 2>(p, s) : launch_mid16_nw<false, 8, 2>(p, s);   // 8 waves x 2 pixel tiles: 512 pixels per workgroup, one per CU
-  return f16 ? launch_mid16_nw<true, 8>(p, s) : launch_mid16_nw<false, 8>(p, s);
+  switch (shape) {
+    case MidShape::W4: return f16 ? launch_mid16_nw<true, 4>(p, s) : launch_mid16_nw<false, 4>(p, s);
+    case MidShape::W16: return f16 ? launch_mid16_nw<true, 16>(p, s) : launch_mid16_nw<false, 16>(p, s);
+    case MidShape::W4x2: return f16 ? launch_mid16_nw<true, 4, 2>(p, s) : launch_mid16_nw<false, 4, 2>(p, s);   // 4 waves x 2 pixel tiles: 256 pixels per workgroup, two per CU, one wave of either on a SIMD
+    case MidShape::W8x2: return f16 ? launch_mid16_nw<true, 8, 2>(p, s) : launch_mid16_nw<false, 8, 2>(p, s);   // 8 waves x 2 pixel tiles: 512 pixels per workgroup, one per CU
+    default: return f16 ? launch_mid16_nw<true, 8>(p, s) : launch_mid16_nw<false, 8>(p, s);
+  }
 }
 
 }  // namespace srcfd

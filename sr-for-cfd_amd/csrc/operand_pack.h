@@ -1,6 +1,7 @@
 // Host-side operand packing: every layout a kernel reads its weights in, as pure functions from the layer graph to host vectors
 // and offsets.  These layouts are the contract between host and kernel.  No HIP runtime calls in this unit: engine.hip (plan_*),
-// fused_bf16.hip (lowp16_plan, build_pack: both 16-bit graphs through plan16 / pack_wt16 / pack_enc16), train_tail.hip
+// fused_bf16.hip (lowp16_plan, build_pack: both 16-bit graphs through plan16 / pack_wt16 / pack_enc16; what a chunk of either
+// launches is the sister unit lowp16_plan.h's, from the Plan16 made here), train_tail.hip
 // (train_tail_plan) and train.hip (trainer_build) decide what qualifies and upload what these functions return.  The trainer's
 // launch arithmetic lives here too: the grid of every weight-gradient launch, the table of the step's one slab-sum launch and the
 // slab space it needs (plan_step, plan_slab_space); trainer_build sizes from it, trainer_step issues from it.
@@ -58,7 +59,7 @@ Tail32Pack tail32_slots(std::vector<Slot>& s);
 // map / scale / offsets of TrainTailPlan for a tail whose first parameter has flat index param_off
 void train_tail_slots(size_t param_off, TrainTailPlan& plan);
 
-// ---- bf16 / f16 path (fused_bf16.hip): two graphs, one front end ----
+// ---- bf16 / f16 path (fused_bf16.hip): two graphs, one front end, one chunk plan (lowp16_plan.h) ----
 // fused: encoder_10 + decoder_400 (enc16 -> dense1_16 -> mid16 -> tail16).  any16: encoder_10 + the other family decoders
 // (enc16 -> per layer gemm16, or the narrow-channel GEMM of kernels_any16.hip for CI 16 / 32 -> outconv16).  Both store swish
 // outputs scaled by log2e and fold 1 / log2e into the consumer's weights; both share plan16 / pack_wt16 / pack_enc16 below.

@@ -4,7 +4,8 @@ test_any16_cases.py (CPU) and test_gpu_any16_layers.py.
 A case is a decoder behind encoder_10: dense_1, an optional further Dense, a Reshape, one or two stride-2 transposed
 convolutions and the 3x3 'same' output convolution.  Every case is the smallest graph that reaches one branch of the 16-bit
 kernels which the five family decoders never take (see `reaches`).  `gemm_ops` restates, from a case alone, which kernel and
-which branch of it every GEMM op takes (build_plan / plan16 / run_gemm / launch_gemm16 of csrc/), and
+which branch of it every GEMM op takes (build_plan / plan16 / plan_chunk16 of csrc/; test_any16_cases.py holds it against the
+library's own plan), and
 test_any16_cases.py::test_table_reaches_every_branch_of_the_16bit_layer_kernels fails if a branch is reached by no case.
 
 Three weight sets per case:
@@ -211,10 +212,10 @@ def gemm_ops(case, n):
             narrow = d["CI"] % 64 != 0                           # any16_narrow
             d.update(layer=name, scaling=sc, kernel="gemm16n" if narrow else "gemm16", M=n * d["MH"] * d["MW"])
             d["Npad"] = _round_up(d["N"], 32 if narrow else 64)  # plan16
-            d["BN"] = 32 if narrow else (128 if d["Npad"] % 128 == 0 else 64)   # launch_gemm16: wide
+            d["BN"] = 32 if narrow else (128 if d["Npad"] % 128 == 0 else 64)   # gemm16: wide
             assert d["N"] % 4 == 0 and (narrow or d["K"] % 64 == 0), "any16_plan: GEMM shape"
-            # run_gemm: layers with a 1x1 output (Dense) and a long K split it over up to 16 slabs, if the slabs (16 x chunk x 128 f32)
-            # hold them.  One row per sample is not enough: wide_1px's phase ops have MH = MW = 1 and K = 2048 / 1024 too, and until
+            # plan_chunk16: layers with a 1x1 output (Dense) and a long K split it over up to 16 slabs, if the slabs the handle reserves
+            # for a chunk of this size (16 x chunk x 128 f32) hold them.  One row per sample is not enough: wide_1px's phase ops have MH = MW = 1 and K = 2048 / 1024 too, and until
             # 2026-10-19 they took this branch, whose finish kernel stores row m at Y + m OC (found by test_gpu_any16_layers.py)
             splits = max(1, min(16, d["K"] // 256)) if (d["shape"] == "dense" and not narrow and d["K"] >= 1024) else 1
             d["splitk"] = splits > 1 and splits * d["M"] * d["Npad"] <= 16 * n * 128

@@ -11,6 +11,7 @@ import any16_cases as ac
 import error_maps as em
 import family_ref as fr
 from conftest import STATS_TXT
+from test_lowp16_plan import lowp16_plans   # noqa: F401  (the session's one run of the plan harness)
 
 
 @pytest.fixture(scope="module")
@@ -66,6 +67,27 @@ def test_table_reaches_every_branch_of_the_16bit_layer_kernels():
     # ... with one row per sample and K >= 1024, as a Dense layer has: they must not take its split-K branch
     assert [d["K"] for d in one_px] == [2048, 1024, 1024, 512] and not any(d["splitk"] for d in one_px)
     assert {ac.batch_size(c) for c in ac.CASES} == {67, 259} and ac.batch_size("wide_1px") == 259      # 4 corners; one pixel of the % 4 lattice on 4 x 4
+
+
+def test_gemm_ops_agrees_with_the_library_plan(lowp16_plans):
+    """any16_cases.gemm_ops states from a case alone which kernel and branch every op takes; the library's own chunk plan
+    (csrc/lowp16_plan.cpp, dumped by the sanitizer-built harness of tests/test_lowp16_plan.py) says the same for every case and
+    every batch of BATCHES: kernel, BN, M and whether K is split, op by op, behind enc16 and up to the output convolution."""
+    for case in ac.CASES:
+        for n in ac.BATCHES:
+            steps = lowp16_plans[case]["chunks"][(0, 256, n)]["steps"]      # default switches
+            ops = ac.gemm_ops(case, n)
+            assert steps[0]["kernel"] == "enc16" and len(steps) == 1 + len(ops), (case, n)
+            for st, d in zip(steps[1:], ops):
+                assert st["kernel"] == d["kernel"], (case, n, d["layer"])
+                if d["kernel"] == "outconv16":
+                    assert st["grid"] == (-(-d["M"] // 256),)
+                    continue
+                assert (st["d"]["M"], st["d"]["N"], st["d"]["K"], st["d"]["Npad"], st["d"]["CI"]) == (d["M"], d["N"], d["K"], d["Npad"], d["CI"]), (case, n, d["layer"])
+                if d["kernel"] == "gemm16n":
+                    assert d["BN"] == 32 and st["grid"] == (-(-d["M"] // 128), d["Npad"] // d["BN"]) and not d["splitk"], (case, n, d["layer"])
+                else:
+                    assert st["cut"]["bn"] == d["BN"] and (st["cut"]["splits"] > 1) == d["splitk"], (case, n, d["layer"])
 
 
 def test_every_case_is_accepted_on_a_host_only_handle(srcfd, enc_weights):

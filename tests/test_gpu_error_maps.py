@@ -32,7 +32,7 @@ BATCHES = (8, 13, 256, 300)
 
 
 def auto_seg(n, cus):
-    """The automatic segmentation of the 16-bit tail: the cost rule of the fused forward (fused_bf16.hip, fused_chunk) restated.  Cost =
+    """The automatic segmentation of the 16-bit tail: the cost rule of the fused forward (lowp16_plan.cpp, tail_segments) restated.  Cost =
     strips walked by the busiest workgroup; a finer cut has to be 15 % cheaper than the best so far."""
     seg, best = 1, -(-n // cus) * 50 + 2
     for cand in (2, 5, 10, 25):

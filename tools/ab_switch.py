@@ -3,7 +3,7 @@
 
     python tools/ab_switch.py SRCFD_MID 1 2 [--fields 256] [--precision bf16] [--reps 30]
 
-The switches are read per call (engine.h Switches), so both arms run on the same handle, inputs and clocks, interleaved.
+The switches are read per call (switches.h Switches), so both arms run on the same handle, inputs and clocks, interleaved.
 """
 import argparse
 import os

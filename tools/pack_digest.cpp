@@ -7,17 +7,21 @@
 //   (PlanDump, tests/test_gemm32_plan.py)
 //   pack_digest --forms <forms.txt> <dump-dir>           only the f32 GEMM launch plan of the layer graphs listed in forms.txt, each at
 //   its own batch size (tests/gemm32_forms.py writes the list, tests/test_gemm32_forms.py reads `forms.gemm32.plan.txt`); prints nothing
+//   pack_digest --lowp16 <graphs.txt> <dump-dir>         only the 16-bit forward's chunk plan (lowp16_plan.cpp) of the graphs listed in
+//   graphs.txt, at every batch, CU count and switch set of tests/test_lowp16_plan.py, as `lowp16.plan.txt`; prints nothing
 //   family.h5: a whole-model file of another member of the notebook's family (family.py, e.g. encoder_10 + decoder_100, with
 //   padding='same' transposed convolutions); adds `family.*` sections: its f32 plan and the trainer's maps without the fused tail.
 // Which fused kernels a graph qualifies for is decided in engine.hip / fused_bf16.hip / train_tail.hip (HIP translation units this
 // harness does not link); find_chain() and the shape tests below restate those decisions for the graphs at hand, and the recorded
 // `plan` / `fused.c1_off` / `train.tail_plan` sections pin them.
 #include <cstdio>
+#include <functional>
 #include <numeric>
 #include <string>
 #include <vector>
 
 #include "../sr-for-cfd_amd/csrc/gemm32_plan.h"
+#include "../sr-for-cfd_amd/csrc/lowp16_plan.h"
 #include "../sr-for-cfd_amd/csrc/operand_pack.h"
 #include "sha256.h"
 
@@ -398,10 +402,10 @@ static void small_graph(const std::string& tag, ModelDesc md, bool train_plan = 
 // notebook's family only, which none of these graphs is).  Integers are the enums of include/srcfd.h:
 //   case <name> <batch> <in_h> <in_w> <in_c> <layers>
 //   layer <kind> <activation> <kh> <kw> <stride> <same> <cin> <cout>  x layers; the plan does not read the weights: zeros
-static int dump_forms(const char* list) {
+//   a Reshape layer carries its target in the last three places: layer <kind> 0 1 1 1 <h> <w> <c>
+static int read_graphs(const char* list, const std::function<void(const std::string&, const ModelDesc&, int)>& take) {
   FILE* in = std::fopen(list, "r");
   if (!in) { std::fprintf(stderr, "cannot read %s\n", list); return 2; }
-  PlanDump out("forms.");
   char name[128];
   int n, h, w, c, nl, cases = 0;
   while (std::fscanf(in, " case %127s %d %d %d %d %d", name, &n, &h, &w, &c, &nl) == 6) {
@@ -416,30 +420,95 @@ static int dump_forms(const char* list) {
         return 2;
       }
       L.same = same != 0; L.name = "l" + std::to_string(i);
-      if (L.kind != SRCFD_LAYER_FLATTEN) { L.kernel.assign((size_t)L.kh * L.kw * L.cin * L.cout, 0.f); L.bias.assign(L.cout, 0.f); }
+      if (L.kind == SRCFD_LAYER_RESHAPE) { L.reshape[0] = same; L.reshape[1] = L.cin; L.reshape[2] = L.cout; L.same = 0; L.cin = L.cout = 0; }
+      else if (L.kind != SRCFD_LAYER_FLATTEN) { L.kernel.assign((size_t)L.kh * L.kw * L.cin * L.cout, 0.f); L.bias.assign(L.cout, 0.f); }
       md.layers.push_back(L);
     }
     md.infer_shapes();
-    out.form(name, md, n);
+    take(name, md, n);
     ++cases;
   }
   const bool whole = std::feof(in) != 0;
   std::fclose(in);
-  if (!whole || !cases) { std::fprintf(stderr, "%s: not a forms list (stopped behind case %d)\n", list, cases); return 2; }
+  if (!whole || !cases) { std::fprintf(stderr, "%s: not a graph list (stopped behind case %d)\n", list, cases); return 2; }
   return 0;
+}
+static int dump_forms(const char* list) {
+  PlanDump out("forms.");
+  return read_graphs(list, [&](const std::string& name, const ModelDesc& md, int n) { out.form(name, md, n); });
+}
+
+// The 16-bit forward's chunk plan (lowp16_plan.cpp: what fused_bf16.hip issues) of every listed graph as text, for
+// tests/test_lowp16_plan.py; the graph goes through lowp16_plan() of fused_bf16.hip: plan16 for encoder_10 + decoder_400 (the fused
+// graph; enc_ok as fused_init finds it for encoder_10), any16_plan for the rest.  Per graph
+//   G name fused enc_ok out_H out_W ops
+//   Q index layer Kpad + the descriptor (M = 0)                        one line per op of the Plan16
+// then per switch set (SETS below, by index), CU count and chunk
+//   C set num_cus c steps t1_buf tail_seg slab_floats lowp16_slab_elems(c)
+//   S kernel op0 nops src dst bn splits kslice nz gx gy gz fin slab_floats g0 g1 shape nblk0..3 seg blocks + the descriptor   one per step
+static void print_desc(FILE* f, const GemmDesc& d) {
+  for (int v : {d.M, d.N, d.K, d.Npad, d.MH, d.MW, d.TY, d.TX, d.CI, d.IH, d.IW, d.ay, d.by, d.cy, d.ax, d.bx, d.cx, d.CO, d.nphx, d.OH, d.OW, d.OC, d.os, d.oy0,
+                d.ox0, d.act})
+    std::fprintf(f, " %d", v);
+  std::fprintf(f, "\n");
+}
+static int dump_lowp16(const char* list) {
+  FILE* f = std::fopen((g_dump + "/lowp16.plan.txt").c_str(), "w");
+  if (!f) return 2;
+  std::vector<Switches> sets(11);   // default, then SRCFD_ENC=0, DENSE1=0, MID=0, MID=1, MID=2, MID_WAVES=4, MID_WAVES=16, TAIL=s, TAIL_SEG=1, TAIL_SEG=5
+  sets[1].enc16 = false; sets[2].dense1_16 = false; sets[3].mid16 = false; sets[4].mid_shape = 1; sets[5].mid_shape = 2; sets[6].mid_waves = 4;
+  sets[7].mid_waves = 16; sets[8].tail16s = true; sets[9].tail_seg = 1; sets[10].tail_seg = 5;
+  bool bad = false;
+  const int rc = read_graphs(list, [&](const std::string& name, const ModelDesc& md, int) {
+    std::vector<Op> ops;
+    std::vector<float> pack;
+    build_plan(md, ops, pack);
+    Plan16 P;
+    Graph16 g;
+    g.fused = md.is_sr_10_400();
+    if (g.fused) {
+      plan16(md, ops, pack, 6, false, P);
+      g.enc_ok = true;
+    } else {
+      Any16Pack A;
+      any16_plan(md, ops, pack, P, A);
+      if (!A.ok) { std::fprintf(stderr, "%s: %s\n", name.c_str(), A.why.c_str()); bad = true; return; }
+      g.out_H = A.out_H; g.out_W = A.out_W;
+    }
+    std::fprintf(f, "G %s %d %d %d %d %zu\n", name.c_str(), (int)g.fused, (int)g.enc_ok, g.out_H, g.out_W, P.ops.size());
+    for (size_t i = 0; i < P.ops.size(); ++i) {
+      std::fprintf(f, "Q %zu %d %d", i, P.ops[i].layer, P.ops[i].Kpad);
+      print_desc(f, P.ops[i].d);
+    }
+    const std::vector<int> batches = g.fused ? std::vector<int>{1, 3, 7, 64, 216, 256, 257, 768, 1024} : std::vector<int>{1, 3, 130, 67, 259};
+    for (size_t q = 0; q < sets.size(); ++q)
+      for (int cus : {256, 64})
+        for (int c : batches) {
+          const Chunk16Plan p = plan_chunk16(P, g, sets[q], c, cus);
+          std::fprintf(f, "C %zu %d %d %zu %d %d %zu %zu\n", q, cus, c, p.steps.size(), p.t1_buf, p.tail_seg, p.slab_floats, lowp16_slab_elems((size_t)c));
+          for (const Step16& s : p.steps) {
+            std::fprintf(f, "S %d %d %d %d %d %d %d %d %d %u %u %u %u %zu %u %u %d %d %d %d %d %d %d", (int)s.k, s.op0, s.nops, s.src, s.dst, s.cut.bn, s.cut.splits,
+                         s.cut.kslice, s.cut.nz, s.cut.grid[0], s.cut.grid[1], s.cut.grid[2], s.cut.fin, s.cut.slab_floats, s.grid[0], s.grid[1], (int)s.shape,
+                         s.nblk[0], s.nblk[1], s.nblk[2], s.nblk[3], s.seg, s.blocks);
+            print_desc(f, s.d);
+          }
+        }
+  });
+  std::fclose(f);
+  return rc ? rc : (bad ? 2 : 0);
 }
 
 int main(int argc, char** argv) {
-  if (argc == 4 && std::string(argv[1]) == "--forms") {
+  if (argc == 4 && (std::string(argv[1]) == "--forms" || std::string(argv[1]) == "--lowp16")) {
     g_dump = argv[3];
     try {
-      return dump_forms(argv[2]);
+      return std::string(argv[1]) == "--forms" ? dump_forms(argv[2]) : dump_lowp16(argv[2]);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "pack_digest: %s\n", e.what());
       return 1;
     }
   }
-  if (argc < 2) { std::fprintf(stderr, "usage: pack_digest <superres.h5> [dump-dir [family.h5]] | pack_digest --forms <forms.txt> <dump-dir>\n"); return 2; }
+  if (argc < 2) { std::fprintf(stderr, "usage: pack_digest <superres.h5> [dump-dir [family.h5]] | pack_digest --forms <forms.txt> <dump-dir> | pack_digest --lowp16 <graphs.txt> <dump-dir>\n"); return 2; }
   if (argc > 2) g_dump = argv[2];
   try {
     std::printf("{\"sections\": [");
