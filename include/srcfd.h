@@ -274,6 +274,61 @@ int srcfd_prepare_inputs_device(const double* fields_dev, int n, int h, int w, c
                                 const double* train_stats_dev, int adaptive, double blend, float* x_dev, float* in_affine_dev,
                                 void* hip_stream);
 
+/* ---- scoring: predictions against targets, on the device, with numpy's bits -------------------------
+ * Replaces the reductions of `evaluate_for_re` (sr-ae-conv.ipynb:c323-369), the only accuracy numbers the reference publishes
+ * (MAE and range-normalised MAE per component at the held-out Reynolds number).  Per sample, with float32 pred and truth of
+ * `elems` elements and optional (mean, std) pairs:
+ *   p = pred * std + mean, t = truth * std + mean   (inverse_standardize: two float32 roundings each, never an fma; no pair: the
+ *                                                    value as it is);   d = t - p
+ *   metrics[SRCFD_SCORE_MAE]       np.mean(np.abs(t - p))        metrics[SRCFD_SCORE_MSE]       np.mean((t - p)**2)
+ *   metrics[SRCFD_SCORE_MAX_ABS]   np.max(np.abs(t - p))
+ *   metrics[SRCFD_SCORE_TRUTH_MIN] np.min(t)                     metrics[SRCFD_SCORE_TRUTH_MAX] np.max(t)
+ *   metrics[SRCFD_SCORE_PRED_MIN]  np.min(p)                     metrics[SRCFD_SCORE_PRED_MAX]  np.max(p)
+ *   metrics[SRCFD_SCORE_NONFINITE] number of non-finite d, as a float (exact: elems <= 2^24)
+ * Every value has the bit pattern numpy's float32 expression gives (tests/test_gpu_score.py), so a score does not depend on who
+ * computed it.  Min and max are NaN when a NaN is present, as numpy's are; which of -0.0 and +0.0 an extreme is, where both
+ * occur, is as little defined as it is in numpy.
+ * The two means follow numpy's summation order, which is NOT one pairwise tree over the field:
+ *   1. the flattened array is cut into consecutive chunks of 8192 elements (np.getbufsize()), the last one shorter;
+ *   2. a chunk of n elements is summed by pairwise_sum: n < 8 serially from 0.f; 8 <= n <= 128 with eight accumulators
+ *      r[j] = a[j], r[j] += a[i + j] for i = 8, 16, .. < n - n % 8, res = ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), then res += a[i]
+ *      for the last n % 8 elements; n > 128: n2 = n / 2, n2 -= n2 % 8, pairwise(a, n2) + pairwise(a + n2, n - n2);
+ *   3. res = 0.f; res += chunk sum, chunk by chunk;   4. mean = res / (float)elems.   Every operation float32, round to nearest.
+ * elems: 1 .. 2 560 000 (1600 x 1600), else SRCFD_EINVAL.  One launch per call (one workgroup per sample), csrc/score.hip. */
+#define SRCFD_SCORE_FIELDS 8
+#define SRCFD_SCORE_MAE 0
+#define SRCFD_SCORE_MSE 1
+#define SRCFD_SCORE_MAX_ABS 2
+#define SRCFD_SCORE_TRUTH_MIN 3
+#define SRCFD_SCORE_TRUTH_MAX 4
+#define SRCFD_SCORE_PRED_MIN 5
+#define SRCFD_SCORE_PRED_MAX 6
+#define SRCFD_SCORE_NONFINITE 7
+/* Test hook: the summation order for a field of `elems` elements (csrc/score_plan.h), the tables the kernel reads, as JSON:
+ * {"elems":E,"chunk":8192,"n_chunks":..,"full":{"leaves":[[off,len],..],"nodes":[[left,right,height],..]}|null,"last":{..}|null}
+ * "full": a chunk of 8192, "last": the chunk of E % 8192.  "nodes" are the inner nodes, every one after its children; a child
+ * index below len(leaves) names a leaf, any other nodes[index - len(leaves)].  Needs no device. */
+int srcfd_score_plan(int64_t elems, char* buf, size_t len);
+/* pred, truth: float32 (n, elems) host; affines float32 (n, 2) host or NULL; metrics float32 (n, SRCFD_SCORE_FIELDS) host.
+ * Blocks until metrics is complete. */
+int srcfd_score_fields(int device, const float* pred, const float* truth, int n, int64_t elems,
+                       const float* pred_affine, const float* truth_affine, float* metrics);
+/* A held-out set that stays on the device.  create uploads x (n, in_elems), truth (n, out_elems) and the affines ((n, 2) each, or
+ * NULL) ONCE.  score predicts the set's x with m at m's current precision, in chunks of up to 256 samples (the chunks of
+ * srcfd_predict into pageable memory, so every sample has the bits srcfd_predict of the whole set gives it), and scores every
+ * chunk's device result against the resident truth; only the n x SRCFD_SCORE_FIELDS metrics cross to the host.  The forward
+ * applies in_affine and nothing else (no out_affine, no NaN guard); the scorer applies pred_affine and truth_affine -- the
+ * notebook's order, predict standardised, then inverse-standardise both -- so the metrics equal numpy's on
+ * `model.predict(x)` in every precision (the 16-bit forwards fuse an out_affine into one fma and would not).
+ * SRCFD_EINVAL when m's input or output element count is not the set's, or m is on another device.  m is left as it was
+ * (weights, precision).  A set belongs to one device and score runs on m's workspace on the default stream: the rule "one
+ * handle, one stream at a time" of srcfd_predict_device holds for m while score runs, and a set is not thread-safe. */
+typedef struct srcfd_evalset srcfd_evalset;
+int srcfd_evalset_create(int device, const float* x, int64_t in_elems, const float* truth, int64_t out_elems, int n,
+                         const float* in_affine, const float* pred_affine, const float* truth_affine, srcfd_evalset** out);
+int srcfd_evalset_score(srcfd_evalset* e, srcfd_model* m, float* metrics);
+int srcfd_evalset_destroy(srcfd_evalset* e);
+
 /* ---- hand-off into the solver state ---------------------------------------------------------
  * Replaces the three transposed assignments `solver.Var[k, 1:-1, 1:-1] = ml_initial_fields[c].T` and the
  * ghost-cell pass `_apply_bc_wrapper(k)` that follow the SR call (PyCFD_ML_accelerated.py:936-943,

@@ -8,7 +8,8 @@ from ._lib import (LIB_PATH, NoDeviceError, SrcfdError)  # noqa: F401  (raises I
 from .engine import SRModel, device_count, layers_from_weights  # noqa: F401
 from .fine import FineSolver  # noqa: F401
 from .h5 import H5File, H5Writer, read_coarse_fields  # noqa: F401
+from .score import EvalSet, score_fields  # noqa: F401
 from .stats import load_stats, save_stats  # noqa: F401
 
 __all__ = ["SRModel", "device_count", "layers_from_weights", "H5File", "H5Writer", "read_coarse_fields",
-           "load_stats", "save_stats", "FineSolver", "LIB_PATH", "NoDeviceError", "SrcfdError"]
+           "load_stats", "save_stats", "FineSolver", "EvalSet", "score_fields", "LIB_PATH", "NoDeviceError", "SrcfdError"]

@@ -22,6 +22,8 @@ ACT_LINEAR, ACT_SWISH, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
 FLAG_NAN_GUARD = 1
 CASE_RUNNING, CASE_CONVERGED, CASE_DIVERGED = 0, 1, 2
 FINE_MODE_LAUNCHES, FINE_MODE_RESIDENT = 0, 1
+SCORE_FIELDS = 8   # srcfd_score_fields / srcfd_evalset_score: float32 values per sample, in this order
+SCORE_NAMES = ("mae", "mse", "max_abs", "truth_min", "truth_max", "pred_min", "pred_max", "nonfinite")
 
 
 class SrcfdError(RuntimeError):
@@ -166,6 +168,11 @@ _protos = {
     "srcfd_h5w_attr_strings": (C.c_int, [_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "srcfd_h5w_attr_numeric": (C.c_int, [_p, C.c_char_p, C.c_char_p, C.c_int, _p, C.c_int, C.c_int]),
     "srcfd_h5w_save": (C.c_int, [_p, C.c_char_p]),
+    "srcfd_score_plan": (C.c_int, [C.c_int64, C.c_char_p, _sz]),
+    "srcfd_score_fields": (C.c_int, [C.c_int, _p, _p, C.c_int, C.c_int64, _p, _p, _p]),
+    "srcfd_evalset_create": (C.c_int, [C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p, _p, C.POINTER(_p)]),
+    "srcfd_evalset_score": (C.c_int, [_p, _p, _p]),
+    "srcfd_evalset_destroy": (C.c_int, [_p]),
 }
 for _name, (_res, _args) in _protos.items():
     _fn = getattr(lib, _name)  # AttributeError here = ABI drift, fail loudly

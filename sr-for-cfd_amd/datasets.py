@@ -194,6 +194,25 @@ def prepare_training_set(file_paths: Iterable[str], lr_dim: int, hr_dim: int, re
                 stats_lr=stats_lr, stats_hr=stats_hr, reynolds_to_evaluate=evaluate)
 
 
+def evalset_from_split(data, reynolds=None, device: int = 0):
+    """The held-out samples of `prepare_training_set`'s result as a device-resident `EvalSet` (score.py): the standardised test
+    inputs and targets of the given Reynolds numbers (one number, several, or None: all), prediction and truth both
+    inverse-standardised with `stats_hr[comps_test[i]]` as `evaluate_for_re` does (sr-ae-conv.ipynb:c323-369).  The set carries
+    `index` (positions in the test arrays), `res_test` and `comps_test` of its samples, so that a result can be grouped per
+    Reynolds number and component like the notebook's printout."""
+    from .score import EvalSet
+    res = np.asarray(data["res_test"])
+    if reynolds is None:
+        index = np.arange(len(res))
+    else:
+        index = np.where(np.isin(res, np.atleast_1d(reynolds)))[0]
+    comps = np.asarray(data["comps_test"])[index]
+    affine = np.array([data["stats_hr"][c] for c in comps], np.float32).reshape(len(index), 2)
+    es = EvalSet(data["x_lr_test"][index], data["x_hr_test"][index], pred_affine=affine, truth_affine=affine, device=device)
+    es.index, es.res_test, es.comps_test = index, res[index], comps
+    return es
+
+
 _INT_ATTRS = ("nx", "ny", "total_points")
 
 

@@ -178,9 +178,30 @@ class Trainer:
         return SRModel.from_layers(specs, self.model.input_shape, self.model.device if device is None else device)
 
 
+def validate(trainer: Trainer, validation, epoch: int) -> dict:
+    """One validation pass of `fit`: the trainer's current weights as a fresh inference handle (`export_model`: a handle creation
+    and a re-pack of the weights; cost in DESIGN.md, "Scoring"), `validation.score(model)` on the device, the handle closed again.
+    Appends {"epoch", "val_mae", "val_nmae_percent", "val_mse" (float64 means over the samples), "per_sample"} to
+    `validation.history` and returns it.  No collective; reads the parameters, changes nothing of the trainer."""
+    model = trainer.export_model()
+    try:
+        per = validation.score(model)
+    finally:
+        model.close()
+    mean = lambda k: float(np.mean(per[k], dtype=np.float64)) if len(per[k]) else float("nan")
+    entry = {"epoch": int(epoch), "val_mae": mean("mae"), "val_nmae_percent": mean("nmae_percent"), "val_mse": mean("mse"), "per_sample": per}
+    validation.history.append(entry)
+    return entry
+
+
 def fit(trainer: Trainer, x_lr: np.ndarray, x_hr: np.ndarray, epochs: int, batch_size: int = 8, seed: int = 0,
-        log_every: int = 0) -> List[float]:
-    """`model.fit(ds, epochs=...)` (sr-ae-conv.ipynb:c558-560) for host arrays; returns per-epoch mean loss."""
+        log_every: int = 0, validation=None, validation_every: int = 1) -> List[float]:
+    """`model.fit(ds, epochs=...)` (sr-ae-conv.ipynb:c558-560) for host arrays; returns per-epoch mean loss.
+    validation: an `EvalSet` (score.py), Keras' `validation_data`: after every `validation_every`-th epoch and after the last one
+    rank 0 scores it with the current weights (`validate`) and appends the `val_*` entry to `validation.history`; with all of the
+    set's affines None, `val_mse` is Keras' `recon_loss` of the held-out set.  None: nothing changes."""
+    if validation is not None and int(validation_every) < 1:
+        raise ValueError("validation_every must be >= 1")
     import torch
     r, w = rank(), world_size()
     xs = torch.from_numpy(np.ascontiguousarray(x_lr, np.float32)).to(trainer.device)
@@ -222,4 +243,6 @@ def fit(trainer: Trainer, x_lr: np.ndarray, x_hr: np.ndarray, epochs: int, batch
         history.append(float(epoch_loss.item()) / max(steps, 1))   # one read-back per epoch: mean of the batch losses
         if log_every and r == 0 and (ep + 1) % log_every == 0:
             print(f"epoch {ep + 1}: recon_loss {history[-1]:.6f}")
+        if validation is not None and r == 0 and ((ep + 1) % validation_every == 0 or ep + 1 == epochs):
+            validate(trainer, validation, ep + 1)   # after the epoch's read-back: the main stream is idle, the side stream holds no work
     return history

@@ -72,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--suffix", default="swish_trained_upto_700_multiBC")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--log-every", type=int, default=50)
+    ap.add_argument("--validate-every", type=int, default=0,
+                    help="K > 0: score the held-out samples on the device after every K-th epoch (and the last); the report gains a 'validation' list")
     args = ap.parse_args(argv)
 
     import torch
@@ -102,11 +104,16 @@ def main(argv=None):
     if len(data["res_train"]) == 0:
         raise SystemExit("training set is empty")
     trainer = tr.Trainer(build_model(args.lr_dim, args.hr_dim, args.seed, device=local), max_batch=args.batch_size)
+    validation = None
+    if args.validate_every > 0 and rank == 0 and len(data["res_test"]):
+        validation = ds.evalset_from_split(data, device=local)
     hist = tr.fit(trainer, data["x_lr_train"], data["x_hr_train"], epochs=args.epochs, batch_size=args.batch_size, seed=args.seed,
-                  log_every=args.log_every)
+                  log_every=args.log_every, validation=validation, validation_every=max(args.validate_every, 1))
     if rank == 0:
         model = trainer.export_model()
         report = {"final_recon_loss": hist[-1], "epochs": args.epochs, "train_samples": int(len(data["res_train"])), "world_size": world}
+        if args.validate_every > 0:
+            report["validation"] = [{k: v for k, v in e.items() if k != "per_sample"} for e in (validation.history if validation else [])]
         all_mae, all_nmae = [], []
         for re_val in data["reynolds_to_evaluate"]:
             r = evaluate_for_re(re_val, model, data, args.hr_dim)
