@@ -19,6 +19,7 @@
 #include "dev16.h"
 #include "kernels16.h"
 #include "tail16_layout.h"
+#include "tail16_schedule.h"
 
 namespace srcfd {
 
@@ -350,29 +351,23 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   const int d_olane = ((lane >> 5) * 400 + 8 * d_tsel + 4 * ((lane >> 4) & 1)) * OUTSZ;   // output byte offset inside the item's row pair
   const bool d_last_on = d_tsel < 2;                                                       // tiles 48, 49: the two that exist in a row pair's fourth item
 
-  // ---- static schedule (per round: 14 BC, 8 A, 16 D items over 16 waves) ----
+  // ---- static schedule (per round: 13 BC, 8 A, 16 D items over 16 waves): tail16_schedule.h ----
   // The kernel is VALU-issue bound and wave w runs on SIMD w % 4, so the schedule balances VALU instructions
   // per SIMD (measured with SRCFD_TAIL_PROF: BC ~266, A ~92, D ~65 instructions; the last wave of a SIMD
-  // simply drains what the older waves leave): SIMD 0,1 get 4 BC + 2 A + 2 D, SIMD 2,3 get 3 BC + 2 A + 6 D.
+  // simply drains what the older waves leave).  Those units overrate a D item -- a latency chain of MFMAs -- against a BC item: the SIMD
+  // with four BC items ends the round (profiles/tail16_bc13), so SIMD 0 gets 4 BC + 2 A and no D, SIMD 1, 2 get 3 BC + 2 A + 5 D, SIMD 3 gets 3 BC + 2 A + 6 D.
   //   A : waves 0-7, item = wave; weights resident, activations prefetched one round ahead
-  //   BC: waves 0,1,4,5,8,9,12,13 -> items 0-7; waves 2,3,6,7,10,11 -> items 8-13
-  //   D : waves 8,9,12,13 -> one item each (0-3); waves 10,11 -> two each (8-11); waves 14,15 -> four each (12-15 and 4-7)
+  //   BC: waves 0-12, one item each; item 12 (wave 9) is the eight pixels 192-199 with BOTH ConvT#3 tap rows (16 of its 32 columns in use)
+  //   D : waves 9, 10 -> one item each (2, 3); wave 11 -> one pair (14, 15); waves 13, 14, 15 -> four each, as two interleaved pairs
   // Two wave roles, each with a round loop of its own (`rounds`, below): P = waves 0-7 (BC + A, no D state), Q = waves 8-15
   // (D + BC, no ConvT#2 operands).  ConvT#2's resident weights and prefetched input (32 registers) and D's lane constants are
   // then live only in the role that uses them, which is what leaves room for two interleaved D chains in role Q -- and, at 96
   // registers of the 128 a wave may have, for the constants of a wave's BC item (its ConvT#3 and ConvT#4 weight fragments and b4),
   // which both roles read once per launch: a BC item is 6 ds_read_b128 (2 data + b3), not 17.
   const int a_mt = wave & 3, a_ct = (wave >> 2) & 1;
-  const int sq = wave >> 2, sl = wave & 3;       // wave = 4 * sq + sl, SIMD = sl
-  int bc_item = -1, d_first = 0, d_cnt = 0, d_second = 0;   // D items d_first .. + min(d_cnt, 2) - 1, and d_second, d_second + 1 when d_cnt == 4
-  if (sl < 2) {                                   // SIMD 0,1
-    bc_item = 2 * sq + sl;                        // 0..7
-    if (sq >= 2) { d_first = 2 * (sq - 2) + sl; d_cnt = 1; }        // waves 8,9,12,13 -> 0..3
-  } else {                                        // SIMD 2,3
-    if (sq < 3) bc_item = 8 + 2 * sq + (sl - 2);  // waves 2,3,6,7,10,11 -> 8..13
-    if (sq >= 2) { d_first = 8 + 4 * (sq - 2) + 2 * (sl - 2); d_cnt = 2; }   // waves 10,11,14,15 -> 8..15
-    if (sq == 3) { d_second = 4 + 2 * (sl - 2); d_cnt = 4; }                 // waves 14,15 -> also 4..7 (same tiles, row pair 1 instead of 3)
-  }
+  const int bc_item = tail16_sched::bc_item(wave);
+  const int d_first = tail16_sched::d_first(wave), d_cnt = tail16_sched::d_count(wave), d_second = tail16_sched::d_second(wave);   // D items d_first .. + min(d_cnt, 2) - 1, and d_second, d_second + 1 when d_cnt == 4
+  const bool bc_merged = bc_item == tail16_sched::BC_MERGED;   // wave-uniform: the one wave whose item carries both tap rows
 
   int d_b0[2], d_b1[2];   // per D item of a pair of this wave: within-row byte offsets of window column pair 0 (pair 4 = + 16) and 1 (pairs 2, 3 = + 2, 4 planes); (d_second + i) & 3 == (d_first + i) & 3
 #pragma unroll
@@ -383,11 +378,13 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
     d_b1[i] = (tx + 1) * 16 + ((lane >> 5) ? 2 : 1) * T_PLANE * 16;
   }
   unsigned bad_wave = 0;  // non-finite outputs zeroed by the fast path (wave-uniform count)
-  // BC item of this wave (bc_item = 2 * pixel tile + ConvT#3 row tile): the lane's 100-level pixel never changes
-  int bc_idx = 32 * (bc_item >= 0 ? bc_item >> 1 : 0) + l31;
-  const bool bc_valid = bc_idx < 200;
+  // BC item of this wave (items 0-11: 2 * pixel tile + ConvT#3 row tile; item 12: pixels 192-199, row tile m3 = (l31 >> 3) & 1 per lane,
+  // lanes 16-31 clamped and never stored): the lane's 100-level pixel never changes
+  int bc_idx = tail16_sched::bc_pixel(bc_item, l31);
+  const bool bc_valid = bc_idx >= 0;
   bc_idx = bc_valid ? bc_idx : 199;
   const bool bc_a = bc_idx >= 100;
+  const bool bc_sel = bc_merged ? (l31 & 8) != 0 : bc_a;   // which of a round's two candidate ring row pairs the lane writes: by 100-level row, or (item 12, all in row 1) by tap row
   const int bc_x = bc_idx - (bc_a ? 100 : 0);
   const int bc_l0 = l100_off(bc_a ? 1 : 0, bc_x, h);                                              // chunk h; chunk 2 + h is 2 * 212 granules further
   char* const bc_wbase = ring + ((((bc_x & 1) * (4 * T_PLANE) + (bc_x >> 1) + 1) << 4) + 8 * h);  // x = 4 bc_x + c: plane c + 4 (bc_x & 1), granule (bc_x >> 1) + 1
@@ -448,7 +445,7 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
   // of a 1024-thread workgroup may have): the two ConvT#3 weight fragments of the item's row tile, ConvT#4's fragment, and b4,
   // which is the C operand of both ConvT#4 MFMAs (each result goes to an accumulator of its own: no copy).  hipcc cannot hoist
   // these reads itself: the loop writes LDS.  b3 (16 more) does not fit beside b4 and stays in LDS, as does role P's b2.  Waves
-  // 14 and 15 have no BC item and never use theirs.  (121-122 registers, no scratch: tests/test_tail16_listing.py.)
+  // 13, 14 and 15 have no BC item and never use theirs; the wave of item 12 reads tap row 1's two fragments from LDS every round.  (121-122 registers, no scratch: tests/test_tail16_listing.py.)
   const int m3 = bc_item & 1;
   const uint4 w3r0 = w3_f[(m3 * 2 + 0) * 64 + lane], w3r1 = w3_f[(m3 * 2 + 1) * 64 + lane], w4r = w4_f[lane];
   const f32x16 b4r = load_bias16(cst + TC_OFF_B4 + h * 64);
@@ -494,21 +491,37 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
       const int g = r - 1;
       if (!(bc_item >= 0 && g >= 0 && g < G && !TAIL_ABL(8))) return;
       { int sm, sx, sg, sl; strip_of(g, sm, sx, sg, sl); if (sx < 0) return; }  // warm-up strip of a top segment: nothing above the image
-      const char* src = l100 + (g & 1) * T_L100_BUF;
+      const char* src = l100 + ((r & 1) ^ 1) * T_L100_BUF;   // (g & 1), from the loop counter: a scalar
       uint4 b0 = *reinterpret_cast<const uint4*>(src + bc_l0), b1 = *reinterpret_cast<const uint4*>(src + bc_l0 + 2 * 212 * 16);
       f32x16 acc3 = load_bias16(cst + TC_OFF_B3 + h * 64);
-      acc3 = mfma32<F16>(w3r0, b0, acc3);
-      acc3 = mfma32<F16>(w3r1, b1, acc3);
+      const bool merged = ROLE_Q && bc_merged;   // wave-uniform
+      if (merged) {
+        // Item 12: the resident fragments are tap row 0's; tap row 1's pair comes from LDS here, where little else is live.  Both
+        // pairs run on the same B operand (lanes 8-15 read the pixels of lanes 0-7), each from the bias, and a lane keeps the
+        // accumulator of its own tap row: per column the same MFMAs, A rows and k order as an item of one tap row -- same bits.
+        const uint4 w3s0 = w3_f[(2 + 0) * 64 + lane], w3s1 = w3_f[(2 + 1) * 64 + lane];
+        f32x16 acc3s = mfma32<F16>(w3s0, b0, acc3);
+        acc3s = mfma32<F16>(w3s1, b1, acc3s);
+        acc3 = mfma32<F16>(w3r0, b0, acc3);
+        acc3 = mfma32<F16>(w3r1, b1, acc3);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc3[i] = bc_sel ? acc3s[i] : acc3[i];
+      } else {
+        acc3 = mfma32<F16>(w3r0, b0, acc3);
+        acc3 = mfma32<F16>(w3r1, b1, acc3);
+      }
       uint32_t f3[8];
       const uint4 w4 = w4r;
       // the item writes ring rows 8g + 4a + 2 m3 + {0, 1} (a = 100-level row of the lane's pixel; the ConvT#3 tap row is m3
-      // for both taps tt): two wave-uniform row offsets per value of a, picked per lane, + the lane's constant granule
+      // for both taps tt): two wave-uniform row offsets, picked per lane, + the lane's constant granule.  Items 0-11: m3 is the
+      // item's, the candidates are a = 0 and a = 1; item 12: a = 1 for every lane, the candidates are m3 = 0 and m3 = 1.
       const int rbase = (8 * g) % T_RING_ROWS;
-      int ra0 = rbase + 2 * m3, ra1 = ra0 + 1, rb0 = ra0 + 4, rb1 = ra0 + 5;
+      int ra0 = rbase + (merged ? 4 : 2 * m3), ra1 = ra0 + 1, rb0 = ra0 + (merged ? 2 : 4), rb1 = rb0 + 1;
       ra0 = ra0 >= T_RING_ROWS ? ra0 - T_RING_ROWS : ra0; ra1 = ra1 >= T_RING_ROWS ? ra1 - T_RING_ROWS : ra1;
       rb0 = rb0 >= T_RING_ROWS ? rb0 - T_RING_ROWS : rb0; rb1 = rb1 >= T_RING_ROWS ? rb1 - T_RING_ROWS : rb1;
-      char* w0 = bc_wbase + (bc_a ? rb0 : ra0) * T_ROWP;
-      char* w1 = bc_wbase + (bc_a ? rb1 : ra1) * T_ROWP;
+      ra0 &= 31; ra1 &= 31; rb0 &= 31; rb1 &= 31;   // no-ops on rows < 18 (scalar): they tell hipcc the range, so the per-lane multiply below is the full-rate 24-bit one, not v_mul_lo_u32
+      char* w0 = bc_wbase + (bc_sel ? rb0 : ra0) * T_ROWP;
+      char* w1 = bc_wbase + (bc_sel ? rb1 : ra1) * T_ROWP;
       // Round 3: ConvT#4's two MFMAs ride INSIDE this wave's own swish stream (tools/microbench9.hip: a v_mfma_f32_32x32x16 between the
       // transcendentals of the same wave costs the SIMD 3.6 ns, in front of its own swish block and waited for -- round 2 -- 10.7 ns).
       // Accumulator registers 0-7 of ConvT#3 are tap 0's sixteen channels (k order of w4), 8-15 tap 1's: activate the first half, start
@@ -746,7 +759,7 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
         } else {
           run_d_fast(d_first, d_cnt);
         }
-        // the second pair of waves 14, 15 lies in row pair 1: never at a seam, and without rows in a flush / warm-up round
+        // the second pair of waves 13, 14, 15 is never in row pair 0 (tail16_schedule.h): never at a seam, and without rows in a flush / warm-up round
         if (d_cnt == 4 && !d_warm) run_d_fast(d_second, 2);
       };
       // Role Q does its latency-bound D items first, so that its VALU-heavy BC item overlaps the tail (A items) of the role-P
