@@ -125,13 +125,15 @@ struct Model {
     const void* x = nullptr; const void* y = nullptr; const float* ain = nullptr; const float* aout = nullptr;
     unsigned long long* nf = nullptr; int n = -1, out_dtype = 0, flags = 0, precision = 0;
     unsigned switches = 0;   // Switches::bits(): the A/B switches select different kernels, so they belong to the key
+    bool x3 = false;         // Model::x3_call: a remainder chunk of a large call and a small call of its own run different kernels at the same n
     bool operator==(const GraphKey& o) const {
       return x == o.x && y == o.y && ain == o.ain && aout == o.aout && nf == o.nf && n == o.n && out_dtype == o.out_dtype &&
-             flags == o.flags && precision == o.precision && switches == o.switches;
+             flags == o.flags && precision == o.precision && switches == o.switches && x3 == o.x3;
     }
   };
   GraphKey graph_key, last_key;
   Switches sw;            // of the call in progress
+  bool x3_call = false;   // of the call in progress: x3_for(the n the caller passed); every chunk of the call follows it
   Plan plan, graph_plan;  // of the last forward / of the captured graph
   Stream graph_stream;
   GraphExec graph_exec;
@@ -141,17 +143,22 @@ struct Model {
   int init_device();
   // The f32-grade forward's kernel choice (engine.hip): the loop of forward_generic and the sizes of its buffers all ask f32_step
   size_t f32_first(int precision, const Switches& sw) const;   // 4: enc32 takes ops [0, 4) in front of the loop; else 0
-  F32Step f32_step(size_t i, int n, int precision, const Switches& sw) const;
+  // SRCFD_PREC_FP32X3 runs the split-bf16 kernels from 64 samples PER CALL on: decided once from the n the caller passed
+  // (srcfd_predict's, srcfd_predict_device's), never from a chunk's
+  static constexpr int X3_MIN_CALL = 64;
+  bool x3_for(int call_n, int precision) const { return precision == SRCFD_PREC_FP32X3 && !pack_x3.empty() && call_n >= X3_MIN_CALL; }
+  F32Step f32_step(size_t i, int n, int precision, const Switches& sw, bool x3) const;   // n: the chunk's samples; x3: the call's x3_for
   void f32_span(size_t i, int count, int n, GemmDesc ds[4], F32Operands* w = nullptr) const;
   size_t max_act_elems(int precision, const Switches& sw) const;
   int chunk_cap(int precision, const Switches& sw) const;
-  size_t splitk_need(int n, int precision, const Switches& sw) const;
-  int ensure_workspace(int n, const Switches& sw);
+  size_t splitk_need(int n, int precision, const Switches& sw, bool x3) const;
+  int ensure_workspace(int n, const Switches& sw, bool x3);
   int launch(const char* name, hipStream_t s, const std::function<hipError_t()>& fn);
   int forward_generic(const float* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
                       unsigned long long* nonfinite, hipStream_t s);
+  // call_n: the samples of the caller's whole call where these n are one chunk of it (predict_host, the scorer); 0: n is the call
   int predict_device(const void* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
-                     unsigned long long* nonfinite, hipStream_t s);
+                     unsigned long long* nonfinite, hipStream_t s, int call_n = 0);
   // sink (optional): consumes each chunk's device result [first, first+count) on the default stream instead of the copy into y;
   // a chunk is up to STAGE_SAMPLES samples then, as for a pageable y
   static constexpr int STAGE_SAMPLES = 256;

@@ -182,12 +182,12 @@ void Model::f32_span(size_t i, int count, int n, GemmDesc ds[4], F32Operands* w)
 // enc32: standardise + the encoder's four layers as one launch in front of the loop
 size_t Model::f32_first(int precision, const Switches& sw) const { return enc32_ok && sw.enc32 && precision != SRCFD_PREC_FP32_NAIVE ? 4 : 0; }
 
-F32Step Model::f32_step(size_t i, int n, int precision, const Switches& sw) const {
+F32Step Model::f32_step(size_t i, int n, int precision, const Switches& sw, bool x3) const {
   if (precision == SRCFD_PREC_FP32_NAIVE) return {F32Kernel::Naive, 1, false};   // the bring-up path: every op on its own
-  // SRCFD_PREC_FP32X3: the split-bf16 kernels from 64 samples on: below that their serial k loops lose to the generic f32 kernels'
-  // split-K launches (tools/precision_sweep.py: 0.26 vs 0.13 ms at 3 samples, break-even between 48 and 96), so small calls run
-  // exactly the SRCFD_PREC_FP32 path.
-  const bool x3 = precision == SRCFD_PREC_FP32X3 && !pack_x3.empty() && n >= 64;
+  // SRCFD_PREC_FP32X3: the split-bf16 kernels from 64 samples per call on (x3_for): below that their serial k loops lose to the generic
+  // f32 kernels' split-K launches (tools/precision_sweep.py: 0.26 vs 0.13 ms at 3 samples, break-even between 48 and 96), so small
+  // calls run exactly the SRCFD_PREC_FP32 path.  The caller decides once per call; a chunk of any size follows, so a sample's bits
+  // do not depend on where the call was cut.
   int cnt = 1;   // the ops of one layer (ConvT output phases) are launched together
   while (i + cnt < ops.size() && ops[i + cnt].layer == ops[i].layer && cnt < 4) ++cnt;
   GemmDesc ds[4];
@@ -213,7 +213,7 @@ size_t Model::max_act_elems(int precision, const Switches& sw) const {
   int stop = (int)desc.layers.size();
   F32Step st;
   for (size_t i = 0; i < ops.size() && stop == (int)desc.layers.size(); i += st.count) {
-    st = f32_step(i, 1, precision, sw);
+    st = f32_step(i, 1, precision, sw, false);   // the streaming tail is chosen whatever x3 says
     if (st.k == F32Kernel::Tail32) stop = ops[i].layer;
   }
   for (int i = 0; i < stop; ++i) {
@@ -233,11 +233,11 @@ int Model::chunk_cap(int precision, const Switches& sw) const {
 
 // Split-K slab floats of an n-sample chunk: what the generic GEMM launches that f32_step returns FOR THAT n ask for.  Not
 // monotonic in n: a layer that gemm32_big takes at a large batch needs slabs at a small one.
-size_t Model::splitk_need(int n, int precision, const Switches& sw) const {
+size_t Model::splitk_need(int n, int precision, const Switches& sw, bool x3) const {
   size_t need = 0;
   F32Step st;
   for (size_t i = f32_first(precision, sw); i < ops.size(); i += st.count) {
-    st = f32_step(i, n, precision, sw);
+    st = f32_step(i, n, precision, sw, x3);
     if (st.k != F32Kernel::Group && st.k != F32Kernel::Mfma) continue;
     GemmDesc ds[4];
     f32_span(i, st.count, n, ds);
@@ -248,12 +248,12 @@ size_t Model::splitk_need(int n, int precision, const Switches& sw) const {
 
 // Buffers of an n-sample forward: the two activation buffers grow to the call's chunk, the slabs to what its chunks (whole ones
 // and the remainder) ask for; neither shrinks on a smaller call.
-int Model::ensure_workspace(int n, const Switches& sw) {
+int Model::ensure_workspace(int n, const Switches& sw, bool x3) {
   const int chunk = std::min(n, chunk_cap(precision, sw));
   const size_t per = max_act_elems(precision, sw);   // depends on the precision: the bring-up path materialises every layer
   const bool grow = chunk > ws_chunk || per > ws_per_sample;
   const int step = grow ? chunk : ws_chunk;   // predict_device's chunks: min(n, step) samples, then n % step
-  const size_t need = std::max(splitk_need(std::min(n, step), precision, sw), n > step && n % step ? splitk_need(n % step, precision, sw) : 0);
+  const size_t need = std::max(splitk_need(std::min(n, step), precision, sw, x3), n > step && n % step ? splitk_need(n % step, precision, sw, x3) : 0);
   if (!grow && need <= d_splitk.size()) return SRCFD_OK;
   drop_graph();  // a captured forward holds the old buffers' addresses
   if (need > d_splitk.size()) { int rc = d_splitk.alloc(need); if (rc) return rc; }
@@ -313,7 +313,7 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
   int cur = 0;   // buf[cur]: the input of the next step
   F32Step st;
   for (size_t i = first; i < ops.size() && !rc; i += st.count) {
-    st = f32_step(i, n, precision, sw);
+    st = f32_step(i, n, precision, sw, x3_call);
     const Op& op = ops[i];
     GemmDesc ds[4];
     F32Operands w;
@@ -390,7 +390,7 @@ int Model::forward_generic(const float* x_dev, int n, const float* aff_in, const
 }
 
 int Model::predict_device(const void* x_dev, int n, const float* aff_in, const float* aff_out, void* y_dev, int out_dtype, int flags,
-                          unsigned long long* nonfinite, hipStream_t s) {
+                          unsigned long long* nonfinite, hipStream_t s, int call_n) {
   if (device < 0) { set_error("host-only handle: no device was requested at create"); return SRCFD_ENODEV; }
   if (n < 0) { set_error("negative batch"); return SRCFD_EINVAL; }
   if (out_dtype != SRCFD_F32 && out_dtype != SRCFD_BF16 && out_dtype != SRCFD_F16) { set_error("unsupported output dtype"); return SRCFD_EINVAL; }
@@ -403,8 +403,9 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   const bool use_any16 = use_fused && !has_fused && lowp16;
   plan.sw = sw; plan.precision = precision; plan.fused = use_fused && !use_any16; plan.any16 = use_any16;
   if (use_fused && !lowp_ok()) { set_error(LOWP_REFUSAL); return SRCFD_EINVAL; }
+  x3_call = x3_for(call_n > 0 ? call_n : n, precision);   // once per call: ws_chunk's chunks below and the host entry's all follow it
   if (!use_fused) {
-    int rc = ensure_workspace(n, sw);  // (re)allocates before anything is captured; drops a stale graph when it does
+    int rc = ensure_workspace(n, sw, x3_call);  // (re)allocates before anything is captured; drops a stale graph when it does
     if (rc) return rc;
   }
   const int in_elems = desc.in_shape[0] * desc.in_shape[1] * desc.in_shape[2];
@@ -431,7 +432,7 @@ int Model::predict_device(const void* x_dev, int n, const float* aff_in, const f
   if (graphs) {
     GraphKey key;
     key.x = x_dev; key.y = y_dev; key.ain = aff_in; key.aout = aff_out; key.nf = nonfinite; key.n = n;
-    key.out_dtype = out_dtype; key.flags = flags; key.precision = precision; key.switches = sw.bits();
+    key.out_dtype = out_dtype; key.flags = flags; key.precision = precision; key.switches = sw.bits(); key.x3 = x3_call;
     if (graph_exec && key == graph_key) {
       HIPCHECK(hipGraphLaunch(graph_exec, s));
       plan = graph_plan; plan.graph = 2;
@@ -527,7 +528,7 @@ int Model::predict_host(const float* x, int n, const float* aff_in, const float*
     if (aff_in) { ain = d_aff.get(); HIPCHECK(hipMemcpyAsync(ain, aff_in + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
     if (aff_out) { aout = d_aff.get() + 2 * (size_t)stage_chunk; HIPCHECK(hipMemcpyAsync(aout, aff_out + 2 * (size_t)i, (size_t)c * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
     if (pinned && k >= 2) HIPCHECK(hipStreamWaitEvent(nullptr, ev_copied[b], 0));   // the buffer's previous contents have left
-    int rc = predict_device(d_x_stage.get(), c, ain, aout, ydev, SRCFD_F32, flags, d_nonfinite.get(), nullptr);
+    int rc = predict_device(d_x_stage.get(), c, ain, aout, ydev, SRCFD_F32, flags, d_nonfinite.get(), nullptr, n);
     if (rc) return rc;
     if (sink) { rc = sink(ydev, i, c); if (rc) return rc; HIPCHECK(hipStreamSynchronize(nullptr)); }
     else if (pinned) {
@@ -773,7 +774,7 @@ int srcfd_model_reserve(srcfd_model* m, int n) {
       if (!mm.lowp_ok()) { set_error(srcfd::LOWP_REFUSAL); return SRCFD_EINVAL; }
       return srcfd::lowp16_reserve(mm, n);
     }
-    return mm.ensure_workspace(n, srcfd::Switches::from_env());
+    return mm.ensure_workspace(n, srcfd::Switches::from_env(), mm.x3_for(n, mm.precision));
   });
 }
 
@@ -907,7 +908,7 @@ int srcfd_model_f32_steps(const srcfd_model* m, int n, char* buf, size_t buf_len
     if (first) out = mm.ops[0].name + "=enc32:" + std::to_string(first);
     srcfd::F32Step st;
     for (size_t i = first; i < mm.ops.size(); i += st.count) {
-      st = mm.f32_step(i, n, mm.precision, sw);
+      st = mm.f32_step(i, n, mm.precision, sw, mm.x3_for(n, mm.precision));   // one call of n samples
       out += (out.empty() ? "" : " ") + mm.ops[i].name + "=" + kernel[(int)st.k] + ":" + std::to_string(st.count);
     }
     if (out.size() >= buf_len) { set_error("buffer too small"); return SRCFD_EINVAL; }

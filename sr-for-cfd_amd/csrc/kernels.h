@@ -134,7 +134,8 @@ int tail32_segments(int n, int H, int num_cus);
 int tail32_blocks(int n, int seg, int num_cus);   // workgroups launch_tail32 starts
 
 // f32-grade GEMM on bf16 MFMAs, operands split exactly into three bf16 terms (kernels_x3.hip; SRCFD_PREC_FP32X3).
-// Wt: [plane 3][N][Kpad] bf16 from gemm_x3_split_weights(); d.M set (the 32-bit input offsets bound the batch).
+// Wt: [plane 3][N][Kpad] bf16 from gemm_x3_split_weights(); d.M set (the 32-bit input offsets bound the batch).  What qualifies, which kernel
+// takes an op and every grid: x3_plan.cpp (host only).
 bool gemm_x3_qualifies(const GemmDesc& d);
 int gemm_x3_kpad(const GemmDesc& d);
 void gemm_x3_split_weights(const GemmDesc& d, const float* B, uint16_t* out);

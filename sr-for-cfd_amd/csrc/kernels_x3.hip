@@ -24,10 +24,11 @@
 #include "kernels.h"
 #include "kernels16.h"   // lds_attr_once
 #include "operand_pack.h"
+#include "x3_plan.h"
 
 namespace srcfd {
 
-constexpr int X3_BP = 128, X3_BN = 128, X3_BK = 32, X3_PITCH = 40;     // weight rows in LDS: 32 k + 8 pad = 80 B (5 x 16 B: conflict-free b128 reads)
+constexpr int X3_PITCH = 40;                                            // (tile X3_BP x X3_BN x X3_BK: x3_plan.h) weight rows in LDS: 32 k + 8 pad = 80 B (5 x 16 B: conflict-free b128 reads)
 constexpr int X3_PLANE = X3_BN * X3_PITCH;                              // elements per weight plane
 constexpr int X3_BUF = 3 * X3_PLANE;                                    // one stage: three planes
 constexpr int X3_WLDS = 2 * X3_BUF * 2;                                 // two stages: 61 440 B
@@ -257,7 +258,7 @@ __global__ void __launch_bounds__(256, 2) gemm_x3_group(const X3Group g, const f
 // (3 x 128 x K bf16 = 96 KB), loaded once; eight waves per CU each walk their own 32-pixel tiles with NO barrier after that, the
 // next tile's first operands in flight under the current tile's epilogue, so the waves drift apart and one wave's stores and
 // loads sit under the others' MFMAs.
-constexpr int X3R_K = 128, X3R_PITCH = X3R_K + 8;                       // weight rows: 272 B = 17 x 16 B (conflict-free b128 reads)
+constexpr int X3R_PITCH = X3R_K + 8;                                    // weight rows: 272 B = 17 x 16 B (conflict-free b128 reads)
 constexpr int X3R_PLANE = X3_BN * X3R_PITCH;
 constexpr int X3R_LDS = 3 * X3R_PLANE * 2 + 8 * 32 * X3_EP * 4;         // 104 448 + 36 864 B
 
@@ -341,49 +342,36 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_res(GemmDesc d, const float* _
   }
 }
 
-bool gemm_x3_res_qualifies(const GemmDesc& d) {
-  return d.K <= X3R_K && d.K % X3_BK == 0 && d.TY * d.TX == 1 && d.cy == 0 && d.cx == 0;
-}
-
-// Qualifies: a GEMM the generic f32 kernel would run, with whole 32-deep k-tiles inside a tap and whole 128-channel blocks,
-// channel groups of 32 inside one output phase, 16-byte aligned rows on both sides, swish or linear.
-bool gemm_x3_qualifies(const GemmDesc& d) {
-  return d.K >= 128 && d.CI % X3_BK == 0 && d.N % X3_BN == 0 && d.CO % 32 == 0 && d.OC % 4 == 0 && (d.act == SRCFD_ACT_SWISH || d.act == SRCFD_ACT_LINEAR) &&
-         (d.M <= 0 || ((int64_t)(d.M / (d.MH * d.MW) + 1) * d.IH * d.IW * d.CI < (1ll << 31) &&     // 32-bit element offsets into X ...
-                       (int64_t)(d.M / (d.MH * d.MW) + 1) * d.OH * d.OW * d.OC < (1ll << 31)));     // ... and into Y
-}
-
-int gemm_x3_kpad(const GemmDesc& d) { return (d.K + X3_BK - 1) / X3_BK * X3_BK; }
-
 // B[K][Npad] f32 (the f32 engine's operand) -> Wt[plane 3][N][Kpad] bf16, exact three-way split by truncation
 void gemm_x3_split_weights(const GemmDesc& d, const float* B, uint16_t* out) { split_planes(B, d.K, d.N, d.Npad, gemm_x3_kpad(d), out); }
 
-hipError_t launch_gemm_x3(const GemmDesc& d, const float* X, const uint16_t* Wt, const float* bias, float* Y, hipStream_t s, int num_cus) {
+// one op on its own, as the plan (x3_plan.cpp) says
+static hipError_t launch_x3_op(const GemmDesc& d, const X3Op& o, const float* X, const uint16_t* Wt, const float* bias, float* Y, hipStream_t s) {
   if (d.M <= 0) return hipSuccess;
-  const int Kpad = gemm_x3_kpad(d);
-  if (gemm_x3_res_qualifies(d)) {   // short K, no taps: weights resident in LDS, one workgroup per CU and channel block walks the pixel tiles
+  if (o.k == X3Kernel::Res) {
     hipError_t e = lds_attr_once(reinterpret_cast<const void*>(gemm_x3_res), X3R_LDS);
     if (e != hipSuccess) return e;
-    const int ntiles = (d.M + 31) / 32, nblk = d.N / X3_BN;
-    const int gx = std::max(1, std::min((ntiles + 7) / 8, std::max(1, num_cus / nblk)));
-    hipLaunchKernelGGL(gemm_x3_res, dim3(gx, nblk), dim3(512), X3R_LDS, s, d, X, Wt, Kpad, (int64_t)d.N * Kpad, bias, Y, ntiles);
+    hipLaunchKernelGGL(gemm_x3_res, dim3(o.grid[0], o.grid[1]), dim3(512), X3R_LDS, s, d, X, Wt, o.kpad, (int64_t)d.N * o.kpad, bias, Y, o.ntiles);
     return hipGetLastError();
   }
   hipError_t e = lds_attr_once(reinterpret_cast<const void*>(gemm_x3), X3_LDS);
   if (e != hipSuccess) return e;
-  dim3 grid((unsigned)((d.M + X3_BP - 1) / X3_BP), (unsigned)(d.N / X3_BN));
-  hipLaunchKernelGGL(gemm_x3, grid, dim3(256), X3_LDS, s, d, X, Wt, Kpad, (int64_t)d.N * Kpad, bias, Y);
+  hipLaunchKernelGGL(gemm_x3, dim3(o.grid[0], o.grid[1]), dim3(256), X3_LDS, s, d, X, Wt, o.kpad, (int64_t)d.N * o.kpad, bias, Y);
   return hipGetLastError();
 }
 
-// ops of one layer: one launch when every op takes the tiled kernel (gemm_x3), else one launch per op
+hipError_t launch_gemm_x3(const GemmDesc& d, const float* X, const uint16_t* Wt, const float* bias, float* Y, hipStream_t s, int num_cus) {
+  return launch_x3_op(d, plan_gemm_x3(&d, 1, num_cus).op[0], X, Wt, bias, Y, s);
+}
+
+// ops of one layer: what plan_gemm_x3 decides -- one launch when every op takes the tiled kernel (gemm_x3), else one launch per op
 hipError_t launch_gemm_x3_group(const GemmDesc* ds, int count, const float* X, const uint16_t* const* Wts, const float* const* biases, float* Y,
                                 hipStream_t s, int num_cus) {
-  bool group = count >= 2 && count <= 4;
-  for (int i = 0; group && i < count; ++i) group = ds[i].M > 0 && !gemm_x3_res_qualifies(ds[i]);
-  if (!group) {
+  if (count < 1 || count > 4) return hipErrorInvalidValue;
+  const X3Plan p = plan_gemm_x3(ds, count, num_cus);
+  if (!p.grouped) {
     for (int i = 0; i < count; ++i) {
-      hipError_t e = launch_gemm_x3(ds[i], X, Wts[i], biases[i], Y, s, num_cus);
+      hipError_t e = launch_x3_op(ds[i], p.op[i], X, Wts[i], biases[i], Y, s);
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -392,14 +380,9 @@ hipError_t launch_gemm_x3_group(const GemmDesc* ds, int count, const float* X, c
   if (e != hipSuccess) return e;
   X3Group g;
   g.count = count;
-  int total = 0;
-  for (int i = 0; i < count; ++i) {
-    g.d[i] = ds[i]; g.Wt[i] = Wts[i]; g.bias[i] = biases[i];
-    g.first[i] = total;
-    total += ((ds[i].M + X3_BP - 1) / X3_BP) * (ds[i].N / X3_BN);
-  }
-  for (int i = count; i <= 4; ++i) g.first[i] = total;
-  hipLaunchKernelGGL(gemm_x3_group, dim3((unsigned)total), dim3(256), X3_LDS, s, g, X, Y);
+  for (int i = 0; i < count; ++i) { g.d[i] = ds[i]; g.Wt[i] = Wts[i]; g.bias[i] = biases[i]; }
+  for (int i = 0; i <= 4; ++i) g.first[i] = p.first[i];
+  hipLaunchKernelGGL(gemm_x3_group, dim3(p.group_grid), dim3(256), X3_LDS, s, g, X, Y);
   return hipGetLastError();
 }
 

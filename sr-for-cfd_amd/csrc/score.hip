@@ -348,7 +348,7 @@ int srcfd_evalset_score(srcfd_evalset* e, srcfd_model* m, float* metrics) {
     for (int i = 0; i < es.n; i += Model::STAGE_SAMPLES) {
       const int c = std::min(Model::STAGE_SAMPLES, es.n - i);
       int rc = mm.predict_device(es.d_x.get() + (size_t)i * es.in_elems, c, es.d_in_aff ? es.d_in_aff.get() + 2 * (size_t)i : nullptr, nullptr,
-                                 es.d_y.get(), SRCFD_F32, 0, nullptr, nullptr);
+                                 es.d_y.get(), SRCFD_F32, 0, nullptr, nullptr, es.n);
       if (!rc) rc = launch_score(es.d_y.get(), es.d_truth.get() + (size_t)i * es.out_elems, c, es.out_elems,
                                  es.d_pred_aff ? es.d_pred_aff.get() + 2 * (size_t)i : nullptr,
                                  es.d_truth_aff ? es.d_truth_aff.get() + 2 * (size_t)i : nullptr, es.d_tab.get(),

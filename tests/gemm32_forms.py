@@ -168,11 +168,11 @@ WANT |= {"step:big:1", "step:big:4", "step:skinny", "step:mfma", "step:group", "
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the graphs as the harness and the engine take them
 # ---------------------------------------------------------------------------------------------------------------------------------
-def forms_text():
-    """the list tools/pack_digest.cpp --forms reads"""
+def forms_text(cases=None):
+    """the list tools/pack_digest.cpp --forms reads (of this table, or of another one of `Case`s: tests/x3_forms.py)"""
     eng = importlib.import_module("sr-for-cfd_amd.engine")
     out = []
-    for c in CASES:
+    for c in CASES if cases is None else cases:
         out.append(f"case {c.name} {c.batch} {c.in_shape[0]} {c.in_shape[1]} {c.in_shape[2]} {len(c.layers)}")
         for l in c.layers:
             out.append(f"layer {eng._KIND[l['kind']]} {eng._ACT[l['act']]} {l['kh']} {l['kw']} {l['stride']} {int(l['same'])} {l['cin']} {l['cout']}")

@@ -6,7 +6,8 @@
 //   weight-gradient plan as text (dump_train_plan, tests/test_train_plan.py), and the f32 GEMM's launch plan of every graph as text
 //   (PlanDump, tests/test_gemm32_plan.py)
 //   pack_digest --forms <forms.txt> <dump-dir>           only the f32 GEMM launch plan of the layer graphs listed in forms.txt, each at
-//   its own batch size (tests/gemm32_forms.py writes the list, tests/test_gemm32_forms.py reads `forms.gemm32.plan.txt`); prints nothing
+//   its own batch size (tests/gemm32_forms.py writes the list, tests/test_gemm32_forms.py reads `forms.gemm32.plan.txt`) and, in a file of its own, `forms.x3.plan.txt`, the split-bf16 GEMM's plan
+//   (x3_plan.cpp) of every layer of those graphs that it takes, on 256 CUs (tests/x3_forms.py, tests/test_x3_forms.py); prints nothing
 //   pack_digest --lowp16 <graphs.txt> <dump-dir>         only the 16-bit forward's chunk plan (lowp16_plan.cpp) of the graphs listed in
 //   graphs.txt, at every batch, CU count and switch set of tests/test_lowp16_plan.py, as `lowp16.plan.txt`; prints nothing
 //   family.h5: a whole-model file of another member of the notebook's family (family.py, e.g. encoder_10 + decoder_100, with
@@ -22,6 +23,7 @@
 
 #include "../sr-for-cfd_amd/csrc/gemm32_plan.h"
 #include "../sr-for-cfd_amd/csrc/lowp16_plan.h"
+#include "../sr-for-cfd_amd/csrc/x3_plan.h"
 #include "../sr-for-cfd_amd/csrc/operand_pack.h"
 #include "sha256.h"
 
@@ -182,13 +184,36 @@ static void dump_train_plan(const std::string& tag, const std::vector<Op>& iops,
 //     M N K Npad MH MW TY TX CI IH IW ay by cy ax bx cx CO nphx OH OW OC os oy0 ox0 act
 struct PlanDump {
   FILE* f = nullptr;
+  FILE* fx = nullptr;   // forms only: the split-bf16 GEMM's plan (x3_plan.cpp), a file of its own
   int next = 0;   // running op index of the file
-  explicit PlanDump(const std::string& tag) {
+  explicit PlanDump(const std::string& tag, bool x3 = false) {
     if (g_dump.empty()) return;
     f = std::fopen((g_dump + "/" + tag + "gemm32.plan.txt").c_str(), "w");
     if (!f) std::exit(2);
+    if (x3 && !(fx = std::fopen((g_dump + "/" + tag + "x3.plan.txt").c_str(), "w"))) std::exit(2);
   }
-  ~PlanDump() { if (f) std::fclose(f); }
+  ~PlanDump() { if (f) std::fclose(f); if (fx) std::fclose(fx); }
+  // The split-bf16 GEMM's answer for the ops of one layer at batch n, where every op qualifies (what the engine asks before it sends a
+  // layer there), on `cus` CUs.  Per layer one line
+  //   X first count layer cus grouped group_grid first0 .. first4
+  // and per op one line
+  //   P index kernel(0 tile, 1 resident) kpad gx gy ntiles res_qualifies  + the descriptor
+  void x3(const GemmDesc* ds, int count, int layer, int cus) {
+    if (!fx) return;
+    for (int q = 0; q < count; ++q) if (!gemm_x3_qualifies(ds[q])) return;
+    const X3Plan p = plan_gemm_x3(ds, count, cus);
+    if (p.count != count) std::exit(2);
+    std::fprintf(fx, "X %d %d %d %d %d %u %d %d %d %d %d\n", next, count, layer, cus, (int)p.grouped, p.group_grid, p.first[0], p.first[1], p.first[2], p.first[3], p.first[4]);
+    for (int q = 0; q < count; ++q) {
+      const X3Op& o = p.op[q];
+      const GemmDesc& d = ds[q];
+      std::fprintf(fx, "P %d %d %d %u %u %d %d", next + q, (int)o.k, o.kpad, o.grid[0], o.grid[1], o.ntiles, (int)gemm_x3_res_qualifies(d));
+      for (int v : {d.M, d.N, d.K, d.Npad, d.MH, d.MW, d.TY, d.TX, d.CI, d.IH, d.IW, d.ay, d.by, d.cy, d.ax, d.bx, d.cx, d.CO, d.nphx, d.OH, d.OW, d.OC, d.os,
+                    d.oy0, d.ox0, d.act})
+        std::fprintf(fx, " %d", v);
+      std::fprintf(fx, "\n");
+    }
+  }
   void launch(int mode, int n, const GemmDesc* ds0, int count) {
     if (!f) return;
     GemmDesc ds[4];
@@ -236,11 +261,13 @@ struct PlanDump {
     std::vector<float> pack;
     build_plan(md, ops_, pack);
     std::fprintf(f, "C %s %d\n", name.c_str(), n);
+    if (fx) std::fprintf(fx, "C %s %d\n", name.c_str(), n);
     next = 0;
     for (size_t i = 0, j; i < ops_.size(); i = j) {
       GemmDesc ds[4];
       for (j = i; j < ops_.size() && ops_[j].layer == ops_[i].layer && j - i < 4; ++j) { ds[j - i] = ops_[j].d; ds[j - i].M = n * ops_[j].d.MH * ops_[j].d.MW; }
       launch(0, n, ds, (int)(j - i));
+      x3(ds, (int)(j - i), ops_[i].layer, 256);
       std::fprintf(f, "B %d %d %d %d\n", next, (int)(j - i), ops_[i].layer, (int)gemm32_big_qualifies(ds, (int)(j - i)));
       next += (int)(j - i);
     }
@@ -434,7 +461,7 @@ static int read_graphs(const char* list, const std::function<void(const std::str
   return 0;
 }
 static int dump_forms(const char* list) {
-  PlanDump out("forms.");
+  PlanDump out("forms.", true);
   return read_graphs(list, [&](const std::string& name, const ModelDesc& md, int n) { out.form(name, md, n); });
 }
 
