@@ -329,6 +329,57 @@ int srcfd_evalset_create(int device, const float* x, int64_t in_elems, const flo
 int srcfd_evalset_score(srcfd_evalset* e, srcfd_model* m, float* metrics);
 int srcfd_evalset_destroy(srcfd_evalset* e);
 
+/* ---- tiled super-resolution on the device: cut, predict and stitch ---------------------------------
+ * BASELINE config 5 without the host in between (the host form is pipeline.tiled_super_resolution; the reference defines no
+ * tiling): a float32 coarse field (TY*lh, TX*lw, C), C-contiguous on the device, is cut into TY x TX tiles of the
+ * model's input size; component c of tile (ty, tx) is sample s = (ty*TX + tx)*C + c of a ONE-channel model lh x lw -> hh x hw; the
+ * samples' results are stitched into out (TY*hh, TX*hw, C), channel-interleaved, float32.  No overlap, no blending.  The two
+ * kernels (csrc/tiles.hip) only move values: out has the bits of numpy's reshape / transpose of srcfd_predict's results.
+ *
+ * srcfd_tiled_plan (host only, needs no device): what a tiler of these sizes would do, as JSON --
+ *   {"n":N,"chunk":K,"n_chunks":M,"chunks":[[first,count],..]|null,"v":V,"cut":{"grid":G,"block":256},
+ *    "stitch":{"block":256,"items_per_tile":I,"blocks_per_tile":B,"grid":[one per chunk]|null},"intermediate_bytes":Y}
+ * (lh, lw, in_channels) / (hh, hw, out_channels): the model's input / output shape.  K: the largest multiple of C not above
+ * max_chunk when max_chunk > 0, else not above model_chunk (what srcfd_model_workspace returns for N samples), never below C: a
+ * chunk never splits the C components of a tile.  V: floats per lane and source row of the stitch, the widest of 4, 2, 1 with
+ * hw % V == 0 and align_bytes (the alignment of the stitch's two base pointers; 16 and more count as 16) a multiple of 4 V.
+ * Y = K*hh*hw*4.  The two lists are null above 65536 chunks.  SRCFD_EINVAL with the reason: C outside 1 .. 8, TY or TX < 1, more
+ * than INT_MAX samples, a model input or output of more than one channel.  The launch code executes exactly this plan.
+ *
+ * A srcfd_tiler belongs to one model handle (borrowed: once the model is destroyed, srcfd_tiler_destroy is the only call left)
+ * and one (TY, TX, C, max_chunk); it owns the tile buffer, the per-sample affine arrays and the planar intermediate of one chunk.
+ * create: SRCFD_ENODEV on a host-only model; the
+ * chunk is sized from the model's precision at that moment (a later change of precision stays correct: srcfd_predict_device
+ * chunks by itself).  max_chunk <= 0: none.
+ * Streams: the stream is BOUND to the handle (set_stream; a hipStream_t, NULL = the default stream, which is also the initial
+ * binding), not passed per call.  run, cut and stitch enqueue on it and return without synchronising.  "One handle, one stream at
+ * a time" (srcfd_predict_device) holds for the tiler AND for the model it borrows: the tiler's buffers, the model's workspace
+ * and its captured hipGraph are ordered only by that one stream; a caller that rebinds the stream, or uses the model elsewhere,
+ * orders the two uses itself.  These entries take no per-call stream parameter, so the table of tests/test_gpu_stream_order.py
+ * (built from the parameter name it looks for) does not list them; what the table stands for -- a side-stream test of every
+ * stream-ordered entry point -- is met for srcfd_tiler_run, srcfd_tiles_cut_device and srcfd_tiles_stitch_device by
+ * tests/test_gpu_tiled_device.py (test_side_stream_*).  A change of that table's rule should pick these three up.
+ *
+ * srcfd_tiler_run: cut, then per chunk srcfd_predict_device into the intermediate and a stitch of the chunk's tiles.
+ * in_affine_dev / out_affine_dev: per-COMPONENT (C, 2) (mean, std) device arrays or NULL, applied as srcfd_predict applies row
+ * s % C to sample s.  flags / nonfinite_dev: passed to every predict call (SRCFD_FLAG_NAN_GUARD; the counter is ADDED to).
+ * srcfd_tiles_cut_device: the cut alone -- x_dev (N, lh, lw, 1), and for each (C, 2) array given the per-sample (N, 2) array.
+ * srcfd_tiles_stitch_device: the stitch alone, of the samples [s0, s1) (multiples of C) of the tiler's grid: sample s is plane
+ * src_index_dev[s] of y_dev (int32 device array of N entries, indexed by s) or, with NULL, plane s - s0; y_dev holds y_rows planes
+ * of hh x hw float32.  Only the tiles of [s0, s1) are written.  A tile whose index lies outside [0, y_rows) is left as it was. */
+typedef struct srcfd_tiler srcfd_tiler;
+int srcfd_tiled_plan(int lh, int lw, int in_channels, int hh, int hw, int out_channels, int tiles_y, int tiles_x, int channels,
+                     int max_chunk, int model_chunk, int align_bytes, char* buf, size_t len);
+int srcfd_tiler_create(srcfd_model* m, int tiles_y, int tiles_x, int channels, int max_chunk, srcfd_tiler** out);
+void srcfd_tiler_destroy(srcfd_tiler* t);
+int srcfd_tiler_set_stream(srcfd_tiler* t, void* stream);
+int srcfd_tiler_run(srcfd_tiler* t, const float* field_dev, const float* in_affine_dev, const float* out_affine_dev, float* out_dev,
+                    int flags, int64_t* nonfinite_dev);
+int srcfd_tiles_cut_device(srcfd_tiler* t, const float* field_dev, const float* in_affine_dev, const float* out_affine_dev,
+                           float* x_dev, float* in_affine_n_dev, float* out_affine_n_dev);
+int srcfd_tiles_stitch_device(srcfd_tiler* t, const float* y_dev, int64_t y_rows, const int32_t* src_index_dev, int s0, int s1,
+                              float* out_dev);
+
 /* ---- hand-off into the solver state ---------------------------------------------------------
  * Replaces the three transposed assignments `solver.Var[k, 1:-1, 1:-1] = ml_initial_fields[c].T` and the
  * ghost-cell pass `_apply_bc_wrapper(k)` that follow the SR call (PyCFD_ML_accelerated.py:936-943,

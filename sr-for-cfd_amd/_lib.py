@@ -173,6 +173,13 @@ _protos = {
     "srcfd_evalset_create": (C.c_int, [C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p, _p, C.POINTER(_p)]),
     "srcfd_evalset_score": (C.c_int, [_p, _p, _p]),
     "srcfd_evalset_destroy": (C.c_int, [_p]),
+    "srcfd_tiled_plan": (C.c_int, [C.c_int] * 12 + [C.c_char_p, _sz]),
+    "srcfd_tiler_create": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_p)]),
+    "srcfd_tiler_destroy": (None, [_p]),
+    "srcfd_tiler_set_stream": (C.c_int, [_p, _p]),
+    "srcfd_tiler_run": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, _p]),
+    "srcfd_tiles_cut_device": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
+    "srcfd_tiles_stitch_device": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int, C.c_int, _p]),
 }
 for _name, (_res, _args) in _protos.items():
     _fn = getattr(lib, _name)  # AttributeError here = ABI drift, fail loudly

@@ -452,3 +452,120 @@ class SRModel:
         L.check(L.lib.srcfd_model_get_profile(self._h, names, len(names), ms, C.byref(cnt), 4096))
         ns = names.value.decode().split("\n") if cnt.value else []
         return [(ns[i], float(ms[i])) for i in range(cnt.value)]
+
+
+def tiled_plan(in_shape, out_shape, tiles_y: int, tiles_x: int, channels: int, max_chunk: Optional[int] = None, model_chunk: int = 1024,
+               align_bytes: int = 16) -> dict:
+    """What a `Tiler` of these sizes does (srcfd_tiled_plan; host only, needs no device): sample count, chunks, the stitch's vector
+    width, both grids, the bytes of the planar intermediate.  in_shape / out_shape: the model's (h, w, c)."""
+    import json
+    buf = C.create_string_buffer(1 << 16)
+    while True:
+        rc = L.lib.srcfd_tiled_plan(int(in_shape[0]), int(in_shape[1]), int(in_shape[2]), int(out_shape[0]), int(out_shape[1]), int(out_shape[2]),
+                                    int(tiles_y), int(tiles_x), int(channels), int(max_chunk or 0), int(model_chunk), int(align_bytes), buf, len(buf))
+        if rc == L.EINVAL and "buffer too small" in L.last_error() and len(buf) < (1 << 24):
+            buf = C.create_string_buffer(len(buf) * 8)
+            continue
+        L.check(rc)
+        return json.loads(buf.value.decode())
+
+
+class Tiler:
+    """Owns one ``srcfd_tiler*``: cut, predict and stitch of a (TY*lh, TX*lw, C) field on the model's device (include/srcfd.h,
+    "tiled super-resolution").  Torch CUDA tensors are plumbing only.  The tiler borrows `model` (kept alive here) and is bound to
+    one stream at a time, like the model itself."""
+
+    def __init__(self, model: SRModel, tiles_y: int, tiles_x: int, channels: int, max_chunk: Optional[int] = None):
+        h = C.c_void_p()
+        L.check(L.lib.srcfd_tiler_create(model._h, int(tiles_y), int(tiles_x), int(channels), int(max_chunk or 0), C.byref(h)))
+        self._h = h
+        self.model = model
+        self.tiles_y, self.tiles_x, self.channels, self.max_chunk = int(tiles_y), int(tiles_x), int(channels), max_chunk
+        self.n = self.tiles_y * self.tiles_x * self.channels
+        self.lh, self.lw, _ = model.input_shape
+        self.hh, self.hw, _ = model.output_shape
+        self._index = {}     # world size -> device int32 src_index of the sharded path
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib.srcfd_tiler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def in_shape(self):
+        return (self.tiles_y * self.lh, self.tiles_x * self.lw, self.channels)
+
+    @property
+    def out_shape(self):
+        return (self.tiles_y * self.hh, self.tiles_x * self.hw, self.channels)
+
+    def plan(self, align_bytes: int = 16) -> dict:
+        """The plan this tiler executes for stitch pointers of that alignment (srcfd_tiled_plan with the model's own figures)."""
+        chunk = L.check(L.lib.srcfd_model_workspace(self.model._h, max(self.n, 1), None))
+        return tiled_plan(self.model.input_shape, self.model.output_shape, self.tiles_y, self.tiles_x, self.channels, self.max_chunk, chunk, align_bytes)
+
+    @staticmethod
+    def _p(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _check(self, t, shape, what, dtype=None):
+        import torch
+        dtype = dtype or torch.float32
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device.index == self.model.device):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{self.model.device}")
+
+    def set_stream(self, stream=None):
+        """Binds the torch stream (None: the current one) every later call of this tiler enqueues on."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.model.device))
+        L.check(L.lib.srcfd_tiler_set_stream(self._h, C.c_void_p(st.cuda_stream)))
+
+    def run(self, field, out, in_affine=None, out_affine=None, nan_guard: bool = False, nonfinite=None, stream=None):
+        """field (TY*lh, TX*lw, C) -> out (TY*hh, TX*hw, C), float32 CUDA tensors; affines (C, 2) CUDA tensors or None;
+        `nonfinite`: optional int64 CUDA counter that is added to.  Enqueues on `stream` and returns without synchronising."""
+        self._check(field, self.in_shape, "field")
+        self._check(out, self.out_shape, "out")
+        for a, nm in ((in_affine, "in_affine"), (out_affine, "out_affine")):
+            if a is not None:
+                self._check(a, (self.channels, 2), nm)
+        self.set_stream(stream)
+        L.check(L.lib.srcfd_tiler_run(self._h, self._p(field), self._p(in_affine), self._p(out_affine), self._p(out),
+                                      L.FLAG_NAN_GUARD if nan_guard else 0, self._p(nonfinite)))
+        return out
+
+    def cut(self, field, in_affine=None, out_affine=None, stream=None):
+        """The cut alone: (x (n, lh, lw, 1), in_affine (n, 2) or None, out_affine (n, 2) or None), new CUDA tensors."""
+        import torch
+        self._check(field, self.in_shape, "field")
+        x = torch.empty((self.n, self.lh, self.lw, 1), dtype=torch.float32, device=field.device)
+        per = [None, None]
+        for i, (a, nm) in enumerate(((in_affine, "in_affine"), (out_affine, "out_affine"))):
+            if a is not None:
+                self._check(a, (self.channels, 2), nm)
+                per[i] = torch.empty((self.n, 2), dtype=torch.float32, device=field.device)
+        self.set_stream(stream)
+        L.check(L.lib.srcfd_tiles_cut_device(self._h, self._p(field), self._p(in_affine), self._p(out_affine), self._p(x), self._p(per[0]), self._p(per[1])))
+        return x, per[0], per[1]
+
+    def stitch(self, y, out, s0: int = 0, s1: Optional[int] = None, src_index=None, stream=None):
+        """The stitch alone: samples [s0, s1) from the planes of y (rows, hh, hw[, 1]) into out.  src_index: int32 CUDA tensor of
+        n entries (sample -> plane of y) or None (sample s is plane s - s0)."""
+        import torch
+        s1 = self.n if s1 is None else s1
+        if not (y.is_cuda and y.is_contiguous() and y.dtype == torch.float32 and y.dim() >= 3 and tuple(y.shape[1:3]) == (self.hh, self.hw)
+                and y.numel() == y.shape[0] * self.hh * self.hw):
+            raise ValueError(f"y must be a contiguous float32 CUDA tensor (rows, {self.hh}, {self.hw})")
+        if src_index is not None:
+            self._check(src_index, (self.n,), "src_index", torch.int32)
+        # out may be a view into a larger allocation: only its own extent is written
+        if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == self.out_shape):
+            raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {self.out_shape}")
+        self.set_stream(stream)
+        L.check(L.lib.srcfd_tiles_stitch_device(self._h, self._p(y), int(y.shape[0]), self._p(src_index), int(s0), int(s1), self._p(out)))
+        return out

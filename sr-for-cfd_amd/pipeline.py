@@ -343,3 +343,105 @@ def tiled_super_resolution(field: np.ndarray, model, lr_dim: int = 10, in_affine
         y = np.concatenate([parts[r][:shard_range(n, r, world)[1] - shard_range(n, r, world)[0]].cpu().numpy() for r in range(world)])
     hr = y.shape[1]
     return y.reshape(ty, tx, C, hr, hr).transpose(0, 3, 1, 4, 2).reshape(ty * hr, tx * hr, C)
+
+
+def tile_source_index(n: int, world: int) -> np.ndarray:
+    """Sharded tiling: the row of the gathered (world * per, hh, hw) buffer that holds tile sample s, per = ceil(n / world).  Rank r
+    predicts the samples shard_range(n, r, world) into rows r * per onward, so the map is the identity only when n divides evenly."""
+    from .shard import shard_range
+    per = -(-n // world)
+    idx = np.empty(n, np.int32)
+    for r in range(world):
+        lo, hi = shard_range(n, r, world)
+        idx[lo:hi] = r * per + np.arange(hi - lo, dtype=np.int32)
+    return idx
+
+
+def _tiler_for(model, ty, tx, C, max_chunk):
+    """One Tiler per (model, TY, TX, C, max_chunk), kept on the model object: it lives and dies with the handle it borrows."""
+    from .engine import Tiler
+    cache = model.__dict__.setdefault("_tilers", {})
+    key = (ty, tx, C, max_chunk)
+    if key not in cache:
+        cache[key] = Tiler(model, ty, tx, C, max_chunk)
+    return cache[key]
+
+
+def tiled_super_resolution_device(field, model, lr_dim: int = 10, in_affine=None, out_affine=None, out=None, stream=None,
+                                  max_chunk: Optional[int] = None, distributed: bool = False):
+    """`tiled_super_resolution` with the cut, the network and the stitch on the model's device (csrc/tiles.hip): the same tiles in
+    the same sample order, and a result with the same bits.
+
+    field: a float32 CUDA tensor (T_y*lr, T_x*lr, C) -- the stitched (T_y*hr, T_x*hr, C) tensor is returned (`out` when given) and
+    nothing is synchronised: the work is enqueued on `stream` (a torch stream; None: the current one) -- or a numpy array, which
+    is uploaded; the result then comes back as a numpy array (page-locked, from the result pool of `predict`).
+    in_affine / out_affine: per-component (C, 2) (mean, std) pairs, numpy or CUDA tensors.  max_chunk: at most that many samples per
+    network call (rounded down to whole tiles); None: the model's own largest unchunked call.
+    model: an `SRModel`.  An object that only has `.predict` is what the host function takes.
+
+    distributed=True (inside an initialised `torch.distributed` group, one process per GPU): every rank cuts all tiles, predicts
+    its `shard.shard_range` block into its rows of one (world * per, hr, hr) device buffer, the blocks are exchanged with one
+    all_gather_into_tensor of device tensors (backend "gloo": the collective's payload alone goes through the host), and every
+    rank stitches the whole field once through `tile_source_index`."""
+    import torch
+    from .engine import SRModel, _result_pool
+    if not isinstance(model, SRModel):
+        raise TypeError(f"tiled_super_resolution_device runs on an SRModel's device; {type(model).__name__} is not one -- an object "
+                        "with only .predict is what pipeline.tiled_super_resolution takes")
+    dev = torch.device("cuda", model.device)
+    from_numpy = not isinstance(field, torch.Tensor)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+
+    def on_device(a, shape=None):
+        if a is None:
+            return None
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        a = a.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        return a if shape is None else a.reshape(shape)
+
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        f = on_device(field)
+        if f.dim() != 3:
+            raise ValueError("field must have shape (H, W, C)")
+        H, W, C = (int(v) for v in f.shape)
+        ih, iw, _ = model.input_shape
+        if (ih, iw) != (lr_dim, lr_dim):
+            raise ValueError(f"the model takes {ih} x {iw} tiles, lr_dim is {lr_dim}")
+        ty, tx = H // lr_dim, W // lr_dim
+        if ty * lr_dim != H or tx * lr_dim != W:
+            raise ValueError("field size must be a multiple of the tile size")
+        tiler = _tiler_for(model, ty, tx, C, max_chunk)
+        ain, aout = on_device(in_affine, (C, 2)), on_device(out_affine, (C, 2))
+        res = out if out is not None else torch.empty(tiler.out_shape, dtype=torch.float32, device=dev)
+        if not distributed:
+            tiler.run(f, res, in_affine=ain, out_affine=aout, stream=st)
+        else:
+            import torch.distributed as dist
+            from .shard import shard_range
+            rank, world = dist.get_rank(), dist.get_world_size()
+            n = tiler.n
+            per = -(-n // world)
+            lo, hi = shard_range(n, rank, world)
+            x, ain_n, aout_n = tiler.cut(f, ain, aout, stream=st)
+            y = torch.empty((world * per, tiler.hh, tiler.hw, 1), dtype=torch.float32, device=dev)
+            mine = y[rank * per:(rank + 1) * per]
+            if hi > lo:
+                model.predict_device(x[lo:hi], mine[:hi - lo], in_affine=None if ain_n is None else ain_n[lo:hi],
+                                     out_affine=None if aout_n is None else aout_n[lo:hi], stream=st)
+            if world > 1:
+                if dist.get_backend() == "nccl":
+                    dist.all_gather_into_tensor(y, mine)
+                else:   # the collective's payload through the host, nothing else
+                    block = mine.cpu()
+                    parts = [torch.empty_like(block) for _ in range(world)]
+                    dist.all_gather(parts, block)
+                    y.copy_(torch.cat(parts), non_blocking=False)
+            if world not in tiler._index:
+                tiler._index[world] = torch.from_numpy(tile_source_index(n, world)).to(dev)
+            tiler.stitch(y, res, 0, n, src_index=tiler._index[world], stream=st)
+        if not from_numpy:
+            return res
+        host = _result_pool.empty(tiler.out_shape)
+        torch.from_numpy(host).copy_(res)     # synchronises with the stream
+        return host
