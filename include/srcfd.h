@@ -333,7 +333,7 @@ int srcfd_evalset_destroy(srcfd_evalset* e);
  * BASELINE config 5 without the host in between (the host form is pipeline.tiled_super_resolution; the reference defines no
  * tiling): a float32 coarse field (TY*lh, TX*lw, C), C-contiguous on the device, is cut into TY x TX tiles of the
  * model's input size; component c of tile (ty, tx) is sample s = (ty*TX + tx)*C + c of a ONE-channel model lh x lw -> hh x hw; the
- * samples' results are stitched into out (TY*hh, TX*hw, C), channel-interleaved, float32.  No overlap, no blending.  The two
+ * samples' results are stitched into out (TY*hh, TX*hw, C), channel-interleaved, float32.  No overlap and no blending here (below: the overlapped form).  The two
  * kernels (csrc/tiles.hip) only move values: out has the bits of numpy's reshape / transpose of srcfd_predict's results.
  *
  * srcfd_tiled_plan (host only, needs no device): what a tiler of these sizes would do, as JSON --
@@ -366,11 +366,40 @@ int srcfd_evalset_destroy(srcfd_evalset* e);
  * srcfd_tiles_cut_device: the cut alone -- x_dev (N, lh, lw, 1), and for each (C, 2) array given the per-sample (N, 2) array.
  * srcfd_tiles_stitch_device: the stitch alone, of the samples [s0, s1) (multiples of C) of the tiler's grid: sample s is plane
  * src_index_dev[s] of y_dev (int32 device array of N entries, indexed by s) or, with NULL, plane s - s0; y_dev holds y_rows planes
- * of hh x hw float32.  Only the tiles of [s0, s1) are written.  A tile whose index lies outside [0, y_rows) is left as it was. */
+ * of hh x hw float32.  Only the tiles of [s0, s1) are written.  A tile whose index lies outside [0, y_rows) is left as it was.
+ *
+ * Overlapping tiles with blended seams (srcfd_tiled_plan_overlap, srcfd_tiler_create_overlap; overlap 0 on both axes is exactly the
+ * tiler above).  Per axis, y shown, x alike and independent:
+ *   overlap oy coarse cells, 0 <= oy, 2*oy <= lh (a point lies in at most two tiles per axis); with oy > 0 or ox > 0 both hh % lh
+ *   and hw % lw must be 0, sy = hh / lh.  Coarse stride ly = lh - oy; the field has H = TY*ly + oy rows and tile ty takes coarse
+ *   rows [ty*ly, ty*ly + lh).  Fine stride Sy = ly*sy, fine overlap Oy = oy*sy (hh = Sy + Oy); the output has H*sy = TY*Sy + Oy
+ *   rows.  The sample order is unchanged.  Ramp: wy[j] = float32((j + 0.5) / Oy), j = 0 .. Oy-1, the division in float64 and
+ *   rounded once, computed on the host and uploaded at create (the device never divides); strictly increasing, inside (0, 1).
+ *   Output row R: t1 = min(R / Sy, TY-1), r1 = R - t1*Sy.  If t1 >= 1 and r1 < Oy the row is blended from tile t1-1 at row r1 + Sy
+ *   (value a) and tile t1 at row r1 (value b) with w = wy[r1]; otherwise it is tile t1, row r1, copied.
+ *   Blend: a + w*(b - a), three float32 operations, each rounded, no fused multiply-add: equal contributions come out exactly.
+ *   Two axes: x first inside each contributing tile row (top = ax + wx*(bx - ax) in tile row t1-1, bottom likewise in t1), then
+ *   out = top + wy*(bottom - top).  An axis with one source does no arithmetic: a pixel outside every overlap zone has its tile's
+ *   bits.  The order matters: y first gives other bits at the corners.
+ * srcfd_tiled_plan_overlap: the plan's keys, then "overlap":[oy,ox],"stride":[ly,lx],"field":[H,W],"out":[H*sy,W*sx],
+ *   "blend":{"grid":G,"block":256,"blocks_per_row":B,"ramp":[Oy,Ox]}|null.  With an overlap "stitch" is null, "blend" is the one
+ *   blending stitch (one lane per output pixel position, B workgroups per output row) and intermediate_bytes = N*hh*hw*4: a
+ *   blended pixel may need tiles of different chunks, so every chunk predicts into its own planes of an intermediate that holds
+ *   all N samples, and one stitch follows the last chunk.  Without one "blend" is null and the rest is srcfd_tiled_plan's.
+ *   Further refusals: an overlap below 0 or above half the tile, an output side that is no multiple of the input side, an output
+ *   side above INT_MAX, N*hh*hw beyond the 64-bit element offsets, a stitch of more workgroups than one launch takes.
+ * On a handle of srcfd_tiler_create_overlap with an overlap, run, cut and set_stream work as documented above on the
+ * (TY*ly + oy, TX*lx + ox, C) field and the (TY*Sy + Oy, TX*Sx + Ox, C) output; srcfd_tiles_stitch_device takes the whole range
+ * only (s0 == 0, s1 == N; anything else is SRCFD_EINVAL: a blended stitch needs every tile), and a PIXEL with a contributing
+ * index outside [0, y_rows) is left as it was. */
 typedef struct srcfd_tiler srcfd_tiler;
 int srcfd_tiled_plan(int lh, int lw, int in_channels, int hh, int hw, int out_channels, int tiles_y, int tiles_x, int channels,
                      int max_chunk, int model_chunk, int align_bytes, char* buf, size_t len);
+int srcfd_tiled_plan_overlap(int lh, int lw, int in_channels, int hh, int hw, int out_channels, int tiles_y, int tiles_x, int channels,
+                             int overlap_y, int overlap_x, int max_chunk, int model_chunk, int align_bytes, char* buf, size_t len);
 int srcfd_tiler_create(srcfd_model* m, int tiles_y, int tiles_x, int channels, int max_chunk, srcfd_tiler** out);
+int srcfd_tiler_create_overlap(srcfd_model* m, int tiles_y, int tiles_x, int channels, int overlap_y, int overlap_x, int max_chunk,
+                               srcfd_tiler** out);
 void srcfd_tiler_destroy(srcfd_tiler* t);
 int srcfd_tiler_set_stream(srcfd_tiler* t, void* stream);
 int srcfd_tiler_run(srcfd_tiler* t, const float* field_dev, const float* in_affine_dev, const float* out_affine_dev, float* out_dev,

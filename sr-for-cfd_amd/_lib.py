@@ -175,6 +175,8 @@ _protos = {
     "srcfd_evalset_destroy": (C.c_int, [_p]),
     "srcfd_tiled_plan": (C.c_int, [C.c_int] * 12 + [C.c_char_p, _sz]),
     "srcfd_tiler_create": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_p)]),
+    "srcfd_tiled_plan_overlap": (C.c_int, [C.c_int] * 14 + [C.c_char_p, _sz]),
+    "srcfd_tiler_create_overlap": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_p)]),
     "srcfd_tiler_destroy": (None, [_p]),
     "srcfd_tiler_set_stream": (C.c_int, [_p, _p]),
     "srcfd_tiler_run": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, _p]),

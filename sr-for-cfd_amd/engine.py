@@ -454,15 +454,32 @@ class SRModel:
         return [(ns[i], float(ms[i])) for i in range(cnt.value)]
 
 
+def overlap_pair(overlap) -> tuple:
+    """`overlap` as (oy, ox): an int stands for both axes."""
+    if isinstance(overlap, (tuple, list)):
+        if len(overlap) != 2:
+            raise ValueError(f"overlap is an int or (oy, ox), not {overlap!r}")
+        return int(overlap[0]), int(overlap[1])
+    return int(overlap), int(overlap)
+
+
 def tiled_plan(in_shape, out_shape, tiles_y: int, tiles_x: int, channels: int, max_chunk: Optional[int] = None, model_chunk: int = 1024,
-               align_bytes: int = 16) -> dict:
+               align_bytes: int = 16, overlap=0) -> dict:
     """What a `Tiler` of these sizes does (srcfd_tiled_plan; host only, needs no device): sample count, chunks, the stitch's vector
-    width, both grids, the bytes of the planar intermediate.  in_shape / out_shape: the model's (h, w, c)."""
+    width, both grids, the bytes of the planar intermediate.  in_shape / out_shape: the model's (h, w, c).
+    overlap (an int or (oy, ox), coarse cells) other than 0: srcfd_tiled_plan_overlap -- the same keys, then the overlap, the
+    strides, the field and output sizes and the blending stitch's grid (include/srcfd.h)."""
     import json
+    oy, ox = overlap_pair(overlap)
+    sizes = (int(in_shape[0]), int(in_shape[1]), int(in_shape[2]), int(out_shape[0]), int(out_shape[1]), int(out_shape[2]),
+             int(tiles_y), int(tiles_x), int(channels))
+    tail = (int(max_chunk or 0), int(model_chunk), int(align_bytes))
     buf = C.create_string_buffer(1 << 16)
     while True:
-        rc = L.lib.srcfd_tiled_plan(int(in_shape[0]), int(in_shape[1]), int(in_shape[2]), int(out_shape[0]), int(out_shape[1]), int(out_shape[2]),
-                                    int(tiles_y), int(tiles_x), int(channels), int(max_chunk or 0), int(model_chunk), int(align_bytes), buf, len(buf))
+        if (oy, ox) == (0, 0):
+            rc = L.lib.srcfd_tiled_plan(*sizes, *tail, buf, len(buf))
+        else:
+            rc = L.lib.srcfd_tiled_plan_overlap(*sizes, oy, ox, *tail, buf, len(buf))
         if rc == L.EINVAL and "buffer too small" in L.last_error() and len(buf) < (1 << 24):
             buf = C.create_string_buffer(len(buf) * 8)
             continue
@@ -473,11 +490,18 @@ def tiled_plan(in_shape, out_shape, tiles_y: int, tiles_x: int, channels: int, m
 class Tiler:
     """Owns one ``srcfd_tiler*``: cut, predict and stitch of a (TY*lh, TX*lw, C) field on the model's device (include/srcfd.h,
     "tiled super-resolution").  Torch CUDA tensors are plumbing only.  The tiler borrows `model` (kept alive here) and is bound to
-    one stream at a time, like the model itself."""
+    one stream at a time, like the model itself.
+    overlap (an int or (oy, ox), coarse cells, at most half a tile): neighbouring tiles share that many cells and the stitch blends
+    them with a linear ramp; the field is then (TY*(lh-oy) + oy, TX*(lw-ox) + ox, C) and `stitch` takes the whole range only."""
 
-    def __init__(self, model: SRModel, tiles_y: int, tiles_x: int, channels: int, max_chunk: Optional[int] = None):
+    def __init__(self, model: SRModel, tiles_y: int, tiles_x: int, channels: int, max_chunk: Optional[int] = None, overlap=0):
         h = C.c_void_p()
-        L.check(L.lib.srcfd_tiler_create(model._h, int(tiles_y), int(tiles_x), int(channels), int(max_chunk or 0), C.byref(h)))
+        self.overlap = overlap_pair(overlap)
+        if self.overlap == (0, 0):
+            L.check(L.lib.srcfd_tiler_create(model._h, int(tiles_y), int(tiles_x), int(channels), int(max_chunk or 0), C.byref(h)))
+        else:
+            L.check(L.lib.srcfd_tiler_create_overlap(model._h, int(tiles_y), int(tiles_x), int(channels), self.overlap[0], self.overlap[1],
+                                                     int(max_chunk or 0), C.byref(h)))
         self._h = h
         self.model = model
         self.tiles_y, self.tiles_x, self.channels, self.max_chunk = int(tiles_y), int(tiles_x), int(channels), max_chunk
@@ -499,16 +523,21 @@ class Tiler:
 
     @property
     def in_shape(self):
-        return (self.tiles_y * self.lh, self.tiles_x * self.lw, self.channels)
+        oy, ox = self.overlap
+        return (self.tiles_y * (self.lh - oy) + oy, self.tiles_x * (self.lw - ox) + ox, self.channels)
 
     @property
     def out_shape(self):
-        return (self.tiles_y * self.hh, self.tiles_x * self.hw, self.channels)
+        if self.overlap == (0, 0):
+            return (self.tiles_y * self.hh, self.tiles_x * self.hw, self.channels)
+        h, w, _ = self.in_shape      # an overlap needs an integer scale (the plan refuses anything else)
+        return (h * (self.hh // self.lh), w * (self.hw // self.lw), self.channels)
 
     def plan(self, align_bytes: int = 16) -> dict:
         """The plan this tiler executes for stitch pointers of that alignment (srcfd_tiled_plan with the model's own figures)."""
         chunk = L.check(L.lib.srcfd_model_workspace(self.model._h, max(self.n, 1), None))
-        return tiled_plan(self.model.input_shape, self.model.output_shape, self.tiles_y, self.tiles_x, self.channels, self.max_chunk, chunk, align_bytes)
+        return tiled_plan(self.model.input_shape, self.model.output_shape, self.tiles_y, self.tiles_x, self.channels, self.max_chunk, chunk, align_bytes,
+                          self.overlap)
 
     @staticmethod
     def _p(t):
@@ -555,7 +584,7 @@ class Tiler:
 
     def stitch(self, y, out, s0: int = 0, s1: Optional[int] = None, src_index=None, stream=None):
         """The stitch alone: samples [s0, s1) from the planes of y (rows, hh, hw[, 1]) into out.  src_index: int32 CUDA tensor of
-        n entries (sample -> plane of y) or None (sample s is plane s - s0)."""
+        n entries (sample -> plane of y) or None (sample s is plane s - s0).  With an overlap: the whole range only."""
         import torch
         s1 = self.n if s1 is None else s1
         if not (y.is_cuda and y.is_contiguous() and y.dtype == torch.float32 and y.dim() >= 3 and tuple(y.shape[1:3]) == (self.hh, self.hw)

@@ -299,21 +299,83 @@ def inject_into_solver_state(hr_fields: Dict[str, np.ndarray], Var: np.ndarray) 
         Var[k, 1:-1, 1:-1] = hr_fields[c].T
 
 
-def tiled_super_resolution(field: np.ndarray, model, lr_dim: int = 10, in_affine=None, out_affine=None, distributed: bool = False) -> np.ndarray:
-    """BASELINE config 5: a (T*lr, T*lr, C) coarse field is cut into T x T non-overlapping
+def _tile_counts(H: int, W: int, lr_dim: int, oy: int, ox: int):
+    """(TY, TX) of an (H, W) field cut into lr x lr tiles that share oy rows / ox columns with their neighbours; ValueError for an
+    overlap outside 0 <= 2*o <= lr and for a size that is not T*(lr - o) + o, naming the two nearest sizes that are."""
+    counts = []
+    for axis, size, o in (("height", H, oy), ("width", W, ox)):
+        if o < 0 or 2 * o > lr_dim:
+            raise ValueError(f"overlap {o} on the {axis}: an overlap is at least 0 and at most half a tile (2*overlap <= lr_dim = {lr_dim}), "
+                             "so that a point lies in at most two tiles per axis")
+        step = lr_dim - o
+        t = max((size - o) // step, 1)
+        if t * step + o != size:
+            raise ValueError(f"field {axis} {size} is not T*(lr_dim - overlap) + overlap for lr_dim {lr_dim}, overlap {o}; "
+                             f"the nearest sizes that fit are {t * step + o} and {(t + 1) * step + o}")
+        counts.append(t)
+    return counts[0], counts[1]
+
+
+def _blend_axis(y, T, S, O, w):
+    """Stitches T tiles along one axis with the ramp across the overlaps.  y (..., T, ..., S + O) with the tile index at axis 0
+    and the blended axis last; returns (..., T*S + O) without the tile axis.  float32, every operation rounded: a + w*(b - a)."""
+    out = np.empty(y.shape[1:-1] + (T * S + O,), np.float32)
+    for t in range(T):
+        lo = O if t else 0
+        hi = S if t < T - 1 else S + O
+        out[..., t * S + lo:t * S + hi] = y[t][..., lo:hi]          # one source: the tile's bits
+        if t:
+            a, b = y[t - 1][..., S:S + O], y[t][..., :O]
+            out[..., t * S:t * S + O] = a + w * (b - a)
+    return out
+
+
+def _stitch_overlapped(y, ty, tx, C, oy, ox, lr_dim):
+    """The overlapped stitch of the samples y (n, hh, hw[, 1]) in sample order s = (ty*TX + tx)*C + c: along x inside every tile
+    row first, then along y (the order matters at the corners)."""
+    hh, hw = int(y.shape[1]), int(y.shape[2])
+    if hh % lr_dim or hw % lr_dim:
+        raise ValueError(f"an overlap needs an output that is a whole multiple of the input; the model maps {lr_dim} x {lr_dim} -> {hh} x {hw}")
+    sy, sx = hh // lr_dim, hw // lr_dim
+    Sy, Oy, Sx, Ox = (lr_dim - oy) * sy, oy * sy, (lr_dim - ox) * sx, ox * sx
+    wy = ((np.arange(Oy, dtype=np.float64) + 0.5) / max(Oy, 1)).astype(np.float32)
+    wx = ((np.arange(Ox, dtype=np.float64) + 0.5) / max(Ox, 1)).astype(np.float32)
+    t = np.asarray(y, np.float32).reshape(ty, tx, C, hh, hw)
+    rows = _blend_axis(t.transpose(1, 0, 2, 3, 4), tx, Sx, Ox, wx)                    # (TY, C, hh, W)
+    full = _blend_axis(rows.transpose(0, 1, 3, 2), ty, Sy, Oy, wy)                    # (C, W, H): y last
+    return np.ascontiguousarray(full.transpose(2, 1, 0))
+
+
+def tiled_super_resolution(field: np.ndarray, model, lr_dim: int = 10, in_affine=None, out_affine=None, distributed: bool = False,
+                           overlap=0) -> np.ndarray:
+    """BASELINE config 5: a (T*lr, T*lr, C) coarse field is cut into T x T
     lr x lr tiles, each component of each tile super-resolved independently with the same
-    weights, and the 400x400 results stitched to (T*400, T*400, C).  No overlap or blending:
-    the reference defines none.
+    weights, and the 400x400 results stitched to (T*400, T*400, C).  The reference defines
+    no tiling; overlap=0, the default, cuts disjoint tiles and copies them.
+
+    overlap (an int or (oy, ox), coarse cells, 0 <= 2*o <= lr): neighbouring tiles share o cells, the field is
+    (TY*(lr-oy) + oy, TX*(lr-ox) + ox, C) and the model's output must be a whole multiple s of its input.  Per axis, with the fine
+    stride S = (lr-o)*s and the fine overlap O = o*s: output row R belongs to tile t1 = min(R // S, T-1) at row r1 = R - t1*S; if
+    t1 >= 1 and r1 < O it is a + w*(b - a) of tile t1-1 at row r1 + S (a) and tile t1 at row r1 (b) with w = float32((r1 + 0.5) / O),
+    three float32 operations each rounded; otherwise it is copied.  x is blended first inside each tile row, then y; a pixel outside
+    every overlap zone has its tile's bits.  This function is the specification `tiled_super_resolution_device` is held to.
 
     distributed=True (inside an initialised `torch.distributed` group, one process per GPU): every rank
     super-resolves its contiguous block of the T*T*C tile samples (shard.shard_range) and the blocks are
     exchanged with one all_gather, so each rank returns the whole stitched field.  The tiles are independent:
     there is no other collective."""
+    from .engine import overlap_pair
     H, W, C = field.shape
-    ty, tx = H // lr_dim, W // lr_dim
-    if ty * lr_dim != H or tx * lr_dim != W:
-        raise ValueError("field size must be a multiple of the tile size")
-    tiles = field.reshape(ty, lr_dim, tx, lr_dim, C).transpose(0, 2, 4, 1, 3).reshape(ty * tx * C, lr_dim, lr_dim, 1)
+    oy, ox = overlap_pair(overlap)
+    if (oy, ox) == (0, 0):
+        ty, tx = H // lr_dim, W // lr_dim
+        if ty * lr_dim != H or tx * lr_dim != W:
+            raise ValueError("field size must be a multiple of the tile size")
+        tiles = field.reshape(ty, lr_dim, tx, lr_dim, C).transpose(0, 2, 4, 1, 3).reshape(ty * tx * C, lr_dim, lr_dim, 1)
+    else:
+        ty, tx = _tile_counts(H, W, lr_dim, oy, ox)
+        ly, lx = lr_dim - oy, lr_dim - ox
+        tiles = np.stack([field[a * ly:a * ly + lr_dim, b * lx:b * lx + lr_dim, c] for a in range(ty) for b in range(tx) for c in range(C)])[..., None]
     tiles = np.ascontiguousarray(tiles, dtype=np.float32)
     n = tiles.shape[0]
     ai = np.tile(np.asarray(in_affine, np.float32), (ty * tx, 1)) if in_affine is not None else None
@@ -341,6 +403,8 @@ def tiled_super_resolution(field: np.ndarray, model, lr_dim: int = 10, in_affine
         parts = [torch.empty_like(buf) for _ in range(world)]
         dist.all_gather(parts, buf)
         y = np.concatenate([parts[r][:shard_range(n, r, world)[1] - shard_range(n, r, world)[0]].cpu().numpy() for r in range(world)])
+    if (oy, ox) != (0, 0):
+        return _stitch_overlapped(y, ty, tx, C, oy, ox, lr_dim)
     hr = y.shape[1]
     return y.reshape(ty, tx, C, hr, hr).transpose(0, 3, 1, 4, 2).reshape(ty * hr, tx * hr, C)
 
@@ -357,18 +421,19 @@ def tile_source_index(n: int, world: int) -> np.ndarray:
     return idx
 
 
-def _tiler_for(model, ty, tx, C, max_chunk):
-    """One Tiler per (model, TY, TX, C, max_chunk), kept on the model object: it lives and dies with the handle it borrows."""
+def _tiler_for(model, ty, tx, C, max_chunk, overlap=(0, 0)):
+    """One Tiler per (model, TY, TX, C, max_chunk[, overlap]), kept on the model object: it lives and dies with the handle it borrows.
+    Without an overlap the key is the four figures alone."""
     from .engine import Tiler
     cache = model.__dict__.setdefault("_tilers", {})
-    key = (ty, tx, C, max_chunk)
+    key = (ty, tx, C, max_chunk) if tuple(overlap) == (0, 0) else (ty, tx, C, max_chunk, tuple(overlap))
     if key not in cache:
-        cache[key] = Tiler(model, ty, tx, C, max_chunk)
+        cache[key] = Tiler(model, ty, tx, C, max_chunk, overlap)
     return cache[key]
 
 
 def tiled_super_resolution_device(field, model, lr_dim: int = 10, in_affine=None, out_affine=None, out=None, stream=None,
-                                  max_chunk: Optional[int] = None, distributed: bool = False):
+                                  max_chunk: Optional[int] = None, distributed: bool = False, overlap=0):
     """`tiled_super_resolution` with the cut, the network and the stitch on the model's device (csrc/tiles.hip): the same tiles in
     the same sample order, and a result with the same bits.
 
@@ -378,6 +443,8 @@ def tiled_super_resolution_device(field, model, lr_dim: int = 10, in_affine=None
     in_affine / out_affine: per-component (C, 2) (mean, std) pairs, numpy or CUDA tensors.  max_chunk: at most that many samples per
     network call (rounded down to whole tiles); None: the model's own largest unchunked call.
     model: an `SRModel`.  An object that only has `.predict` is what the host function takes.
+    overlap: as in `tiled_super_resolution` -- strided tiles and the blending stitch (tiles_blend), bit for bit the host function's
+    result; every chunk predicts into its planes of an intermediate of all samples and one stitch follows the last.
 
     distributed=True (inside an initialised `torch.distributed` group, one process per GPU): every rank cuts all tiles, predicts
     its `shard.shard_range` block into its rows of one (world * per, hr, hr) device buffer, the blocks are exchanged with one
@@ -408,10 +475,18 @@ def tiled_super_resolution_device(field, model, lr_dim: int = 10, in_affine=None
         ih, iw, _ = model.input_shape
         if (ih, iw) != (lr_dim, lr_dim):
             raise ValueError(f"the model takes {ih} x {iw} tiles, lr_dim is {lr_dim}")
-        ty, tx = H // lr_dim, W // lr_dim
-        if ty * lr_dim != H or tx * lr_dim != W:
-            raise ValueError("field size must be a multiple of the tile size")
-        tiler = _tiler_for(model, ty, tx, C, max_chunk)
+        from .engine import overlap_pair
+        oy, ox = overlap_pair(overlap)
+        if (oy, ox) == (0, 0):
+            ty, tx = H // lr_dim, W // lr_dim
+            if ty * lr_dim != H or tx * lr_dim != W:
+                raise ValueError("field size must be a multiple of the tile size")
+        else:
+            ty, tx = _tile_counts(H, W, lr_dim, oy, ox)
+            oh, ow, _ = model.output_shape
+            if oh % lr_dim or ow % lr_dim:
+                raise ValueError(f"an overlap needs an output that is a whole multiple of the input; the model maps {lr_dim} x {lr_dim} -> {oh} x {ow}")
+        tiler = _tiler_for(model, ty, tx, C, max_chunk, (oy, ox))
         ain, aout = on_device(in_affine, (C, 2)), on_device(out_affine, (C, 2))
         res = out if out is not None else torch.empty(tiler.out_shape, dtype=torch.float32, device=dev)
         if not distributed:

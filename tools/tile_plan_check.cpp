@@ -2,14 +2,19 @@
 // UBSan by `make -C sr-for-cfd_amd/csrc tile_plan_check`.  Over a grid of tile sizes, tile grids, channel counts, chunk bounds and
 // alignments -- the largest ones the plan accepts included, where 32-bit arithmetic would overflow -- it checks what the launch
 // code relies on: the chunks are whole tiles, cover [0, n) once and in order and fit the intermediate; V divides the row and the
-// stated alignment; every lane of a stitch grid maps to a tile of its chunk; the refusals refuse.  Prints the number of plans
-// checked; exit status 1 and a message on the first violation.
+// stated alignment; every lane of a stitch grid maps to a tile of its chunk; the refusals refuse.
+// Overlapped tiling: for every lh <= 12, overlap <= lh / 2, scale <= 4 and T <= 4 it walks the per-axis source map of tile_map.h --
+// the statement the blending kernel runs -- over all output rows: every row maps to in-range tiles and rows, every (tile, row) is
+// used exactly once, the blended rows are exactly the O * (T - 1) expected ones, the ramps equal the formula; and it checks the
+// plan's geometry, grid and intermediate for those sizes.  Prints the number of plans and of axis walks checked; exit status 1
+// and a message on the first violation.
 #include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../sr-for-cfd_amd/csrc/tile_plan.h"
 
@@ -47,6 +52,53 @@ static void check(const TilePlanIn& in) {
   if (p.intermediate_bytes != (size_t)p.chunk * in.hh * in.hw * 4) fail(in, "intermediate bytes");
   if (p.cut_grid < 1 || p.cut_grid > (1u << 20)) fail(in, "cut grid");
   if (tile_plan_json(p).empty()) fail(in, "empty JSON");
+}
+
+// one axis of an overlapped tiling: lh coarse cells per tile, overlap o, integer scale s, T tiles
+static void check_axis(int lh, int o, int s, int T) {
+  auto bad = [&](const std::string& what) {
+    std::fprintf(stderr, "tile_plan_check: axis lh %d overlap %d scale %d T %d: %s\n", lh, o, s, T, what.c_str());
+    std::exit(1);
+  };
+  TilePlanIn in;
+  in.lh = lh; in.lw = lh; in.hh = lh * s; in.hw = lh * s; in.tiles_y = T; in.tiles_x = 1; in.channels = 3; in.model_chunk = 5;
+  in.overlap_y = o; in.overlap_x = 0;
+  const TilePlan p = tile_plan(in);
+  const int S = (lh - o) * s, O = o * s, hh = lh * s, rows = T * S + O;
+  if (p.stride_y != lh - o || p.stride_x != lh || p.field_h != T * (lh - o) + o || p.field_w != lh) fail(in, "coarse geometry");
+  if (o > 0) {
+    if (!p.blended || p.fine_stride_y != S || p.fine_overlap_y != O || p.out_h != rows || p.out_w != hh || p.fine_stride_x != hh || p.fine_overlap_x != 0) fail(in, "fine geometry");
+    if (p.intermediate_bytes != (size_t)p.n * hh * hh * 4) fail(in, "the intermediate does not hold all n samples");
+    if ((int64_t)p.blend_blocks_per_row * TILE_BLOCK < p.out_w || (int64_t)(p.blend_blocks_per_row - 1) * TILE_BLOCK >= p.out_w) fail(in, "blend blocks per row");
+    if ((int64_t)p.blend_grid != (int64_t)p.out_h * p.blend_blocks_per_row) fail(in, "blend grid");
+    if ((int)p.ramp_y.size() != O || !p.ramp_x.empty()) fail(in, "ramp lengths");
+    for (int j = 0; j < O; ++j) {
+      const float w = (float)((j + 0.5) / (double)O);
+      if (p.ramp_y[(size_t)j] != w || !(w > 0.f && w < 1.f) || (j && !(p.ramp_y[(size_t)j] > p.ramp_y[(size_t)j - 1]))) fail(in, "ramp " + std::to_string(j));
+    }
+    if (tile_plan_json_overlap(p).find("\"stitch\":null") == std::string::npos) fail(in, "JSON of a blended plan");
+  } else if (p.blended || p.blend_grid || !p.ramp_y.empty() || p.intermediate_bytes != (size_t)p.chunk * hh * hh * 4) {
+    fail(in, "overlap 0 is not today's plan");
+  }
+  std::vector<int> used((size_t)T * hh, 0);
+  int blended = 0;
+  for (int R = 0; R < rows; ++R) {
+    const TileAxisSrc a = tile_axis_src(R, T, S, O);
+    if (a.t1 < 0 || a.t1 >= T || a.r1 < 0 || a.r1 >= hh) bad("row " + std::to_string(R) + ": source outside the tiles");
+    ++used[(size_t)a.t1 * hh + a.r1];
+    if (a.t0 >= 0) {
+      if (a.t0 != a.t1 - 1 || a.r0 < 0 || a.r0 >= hh || a.j < 0 || a.j >= O) bad("row " + std::to_string(R) + ": blended source outside the tiles or the ramp");
+      if (a.t0 * S + a.r0 != R || a.t1 * S + a.r1 != R) bad("row " + std::to_string(R) + ": the two sources are not this row");
+      if (R < a.t1 * S || R >= a.t1 * S + O || a.j != R - a.t1 * S) bad("row " + std::to_string(R) + ": blended outside its zone");
+      ++used[(size_t)a.t0 * hh + a.r0];
+      ++blended;
+    } else if (a.j != -1 || a.t1 * S + a.r1 != R) {
+      bad("row " + std::to_string(R) + ": copied from another row");
+    }
+  }
+  for (size_t i = 0; i < used.size(); ++i)
+    if (used[i] != 1) bad("tile " + std::to_string(i / hh) + " row " + std::to_string(i % hh) + " is used " + std::to_string(used[i]) + " times");
+  if (blended != O * (T - 1)) bad(std::to_string(blended) + " blended rows, expected " + std::to_string(O * (T - 1)));
 }
 
 static void must_refuse(const TilePlanIn& in, const char* what) {
@@ -106,6 +158,21 @@ int main() {
   { TilePlanIn b = ok; b.hh = 0; must_refuse(b, "empty output"); }
   { TilePlanIn b = ok; b.hh = b.hw = 40000; must_refuse(b, "a tile of 1.6e9 elements"); }
   { TilePlanIn b = ok; b.model_chunk = 0; must_refuse(b, "no model chunk and no max_chunk"); }
-  std::printf("%ld\n", checked);
+  long axes = 0;
+  for (int lh = 1; lh <= 12; ++lh)
+    for (int o = 0; 2 * o <= lh; ++o)
+      for (int s = 1; s <= 4; ++s)
+        for (int T = 1; T <= 4; ++T) {
+          check_axis(lh, o, s, T);
+          ++axes;
+        }
+  { TilePlanIn b = ok; b.overlap_y = -1; must_refuse(b, "overlap -1"); }
+  { TilePlanIn b = ok; b.overlap_x = 6; must_refuse(b, "overlap above half a tile"); }
+  { TilePlanIn b = ok; b.overlap_y = INT_MAX; must_refuse(b, "overlap INT_MAX"); }
+  { TilePlanIn b = ok; b.overlap_y = 2; b.hh = 405; must_refuse(b, "an output that is no multiple of the input"); }
+  { TilePlanIn b = ok; b.overlap_y = 1; b.lh = 32768; b.hh = 65536; b.lw = 4; b.hw = 8; b.tiles_y = 40000; b.tiles_x = 1; must_refuse(b, "an output side above INT_MAX"); }
+  { TilePlanIn b = ok; b.overlap_y = b.overlap_x = 1; b.lh = b.lw = 4; b.tiles_y = b.tiles_x = 30000; b.channels = 1; must_refuse(b, "a blending stitch above one launch"); }
+  { TilePlanIn b = ok; b.overlap_y = 5; b.overlap_x = 5; check(b); ++checked; }   // half a tile; the chunk keys are today's
+  std::printf("%ld %ld\n", checked, axes);
   return 0;
 }

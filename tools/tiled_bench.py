@@ -8,6 +8,10 @@ Arms, alternating call by call, 3 warm-up rounds, then median [min - max] of 20 
      picks V = 4) and with `out` 8 and 4 bytes off that alignment (V = 2, V = 1): the evidence for the plan's choice of V.  The
      three take turns at going first (whoever follows another stitch finds y in the memory-side cache).  The same at 16x16 tiles
      (768 samples, 2 x 491 MB), where the kernel runs long enough for the rate to mean something.
+  o  the overlapped path, 34x34x3 with overlap 2: 4x4 tiles and 48 samples, the network work of config 5, a 1360x1360x3 result --
+     o_b numpy in / numpy out, o_c tensor in / tensor out (HIP events), o_d the blending stitch alone (HIP events) with its
+     bytes/s (all 48 planes read, the result written) beside the copy figure.  The host function with the same overlap is run
+     once, for the bit-for-bit check, and not timed.
 Prints one JSON object; --out writes it to a file as well.
 """
 import argparse
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", default="f16")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--skip-overlapped", action="store_true", help="arms a - d only: the loop of this tool before it had the overlapped arms")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("sr-for-cfd_amd")
@@ -65,6 +70,11 @@ def main():
     big = pkg.Tiler(model, 16, 16, C)
     y_big = torch.randn((big.n, 400, 400), dtype=torch.float32, device="cuda")
     outs_big = stitch_targets(big)
+    overlap = 2
+    field_o = np.random.default_rng(6).standard_normal((ty * (10 - overlap) + overlap, tx * (10 - overlap) + overlap, C)).astype(np.float32)
+    fo_dev = torch.from_numpy(field_o).cuda()
+    tiler_o = pkg.Tiler(model, ty, tx, C, overlap=overlap)
+    out_o = torch.empty(tiler_o.out_shape, dtype=torch.float32, device="cuda")
     stream = torch.cuda.current_stream()
 
     def timed_events(fn):
@@ -82,8 +92,10 @@ def main():
         dt = (time.perf_counter() - t0) * 1e3
         return dt, r
 
-    arms = {k: [] for k in ("a", "b", "c", "d_v4", "d_v2", "d_v1", "big_v4", "big_v2", "big_v1")}
+    arms = {k: [] for k in ("a", "b", "c", "d_v4", "d_v2", "d_v1", "big_v4", "big_v2", "big_v1", "o_b", "o_c", "o_d")}
     same = None
+    want_o = pl.tiled_super_resolution(field_o, model, 10, overlap=overlap)
+    same_o = None
     for it in range(args.warmup + args.rounds):
         ta, ya = timed_wall(lambda: pl.tiled_super_resolution(field, model, 10))
         tb, yb = timed_wall(lambda: pl.tiled_super_resolution_device(field, model, 10))
@@ -91,6 +103,17 @@ def main():
         order = [(4, 2, 1), (2, 1, 4), (1, 4, 2)][it % 3]
         td = {v: timed_events(lambda: tiler.stitch(y_dev, outs[v])) for v in order}
         tbig = {v: timed_events(lambda: big.stitch(y_big, outs_big[v])) for v in order}
+        if not args.skip_overlapped:
+            tob, yob = timed_wall(lambda: pl.tiled_super_resolution_device(field_o, model, 10, overlap=overlap))
+            toc = timed_events(lambda: pl.tiled_super_resolution_device(fo_dev, model, 10, out=out_o, overlap=overlap))
+            if same_o is None:
+                same_o = bool(np.array_equal(want_o.view(np.uint32), yob.view(np.uint32)) and np.array_equal(want_o.view(np.uint32), out_o.cpu().numpy().view(np.uint32)))
+            del yob
+            tod = timed_events(lambda: tiler_o.stitch(y_dev, out_o))
+        if it >= args.warmup and not args.skip_overlapped:
+            arms["o_b"].append(tob)
+            arms["o_c"].append(toc)
+            arms["o_d"].append(tod)
         if same is None:
             same = bool(np.array_equal(ya.view(np.uint32), yb.view(np.uint32)) and np.array_equal(ya.view(np.uint32), out_dev.cpu().numpy().view(np.uint32)))
         del ya, yb
@@ -115,6 +138,15 @@ def main():
         s["bytes_per_s_at_median"] = round(16 * stitch_bytes / (s["median_ms"] * 1e-3))
         s["fraction_of_copy_rate"] = round(s["bytes_per_s_at_median"] / COPY_RATE, 3)
         rec["stitch_alone_768_samples"][f"v{v}"] = s
+    if not args.skip_overlapped:
+        blend_bytes = (y_dev.numel() + out_o.numel()) * 4
+        sd = summary(arms["o_d"])
+        sd["bytes"] = blend_bytes
+        sd["bytes_per_s_at_median"] = round(blend_bytes / (sd["median_ms"] * 1e-3))
+        sd["fraction_of_copy_rate"] = round(sd["bytes_per_s_at_median"] / COPY_RATE, 3)
+        rec["overlapped"] = {"workload": f"34x34x3 -> 1360x1360x3 via 4x4 tiles of 10x10 with overlap {overlap}, 48 samples", "b_device_path_numpy": summary(arms["o_b"]),
+                             "c_device_path_tensor_events": summary(arms["o_c"]), "d_blending_stitch_alone": sd, "device_equals_host_bit_for_bit": same_o,
+                             "plan": tiler_o.plan()}
     a = rec["arms"]["a_host_path_numpy"]
     rec["bar"] = {"b_median_below_a_range": a["min_ms"] > rec["arms"]["b_device_path_numpy"]["median_ms"],
                   "c_median_below_a_range": a["min_ms"] > rec["arms"]["c_device_path_tensor_events"]["median_ms"]}
