@@ -12,6 +12,10 @@
  * A handle is not thread-safe; distinct handles may be used from distinct
  * threads.  Compute entry points fail with SRCFD_ENODEV when no HIP device is
  * present -- there is no CPU fallback.
+ * No entry point reads or writes caller memory outside the extents its comment
+ * states, and every element of an output extent is written unless the comment
+ * says otherwise (the stitch's "left as it was" for an index outside `y` is
+ * such an exception).
  */
 #ifndef SRCFD_H
 #define SRCFD_H
