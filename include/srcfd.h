@@ -16,6 +16,22 @@
  * states, and every element of an output extent is written unless the comment
  * says otherwise (the stitch's "left as it was" for an index outside `y` is
  * such an exception).
+ *
+ * Device pointers (every argument named *_dev).  Each is a DENSE, C-ordered array of the stated element type and
+ * shape on the handle's device.  No strides cross this ABI: a strided view (one channel of an interleaved tensor, a
+ * transposed view, every other row) is read or written as if it were dense, so a caller makes it contiguous first.
+ * Required alignment: that of the ELEMENT and nothing wider -- 4 bytes for float32 and int32, 2 bytes for a 16-bit
+ * y_dev, 8 bytes for float64 and int64.  That is what a contiguous view into a larger allocation has (a row slice, an
+ * offset into a flat buffer).  The kernels make 8- and 16-byte accesses at addresses derived from these pointers; all
+ * of them are plain global loads, stores or atomics, which the device takes at any element alignment, and no caller
+ * pointer goes into a buffer descriptor or an LDS-direct load.  No entry point returns SRCFD_EINVAL for an
+ * element-aligned pointer.  Two launchers take a narrower path, with the same bits, when the pointers they are handed
+ * share less than 16 bytes of alignment: srcfd_trainer_forward_backward[_ex] (two device-to-device copies instead of
+ * the 16-byte staging kernel) and the stitch of srcfd_tiles_stitch_device / srcfd_tiler_run (vector width V, the
+ * align_bytes of srcfd_tiled_plan).  Each entry point below repeats its own line.  The C side checks these pointers for
+ * NULL only: it cannot see dtype, shape, strides or device.  The Python binding checks all four on every tensor before
+ * it takes its address (_lib.device_ptr; ValueError, nothing enqueued).  Audit: DESIGN.md section 7; every entry point
+ * at 1, 2 and 3 elements behind a 256-byte boundary: tests/test_gpu_device_args.py.
  */
 #ifndef SRCFD_H
 #define SRCFD_H
@@ -165,6 +181,11 @@ void srcfd_host_free(void* p);
  * SRCFD_BF16 or SRCFD_F16), nonfinite_dev an optional device int64 counter
  * that is ADDED to.  Enqueues on hip_stream (a hipStream_t, NULL = default
  * stream) and returns without synchronising.
+ * Pointers: x_dev dense (n,h,w,c), 4-byte aligned; the affines dense (n,2), 4-byte aligned; y_dev dense (n,oh,ow,oc),
+ * aligned to its element (4 bytes, or 2 for the 16-bit types) although the last kernel stores 16 (f32) or 8 (16-bit) bytes
+ * per lane; nonfinite_dev 8-byte aligned (a 64-bit atomic add).  y_dev must hold all n samples: the library cannot see its
+ * size.  A call of more samples than srcfd_model_workspace reports runs in chunks at x_dev + i in_elems,
+ * y_dev + i out_elems, affine row i, into the same counter.
  * One handle, one stream at a time: the activation workspace, the split-K slabs
  * and the captured hipGraph belong to the handle, so two calls on the SAME handle
  * are ordered only when they are enqueued on the same stream.  A caller that moves
@@ -257,7 +278,8 @@ int srcfd_model_load_superres_h5(const char* superres_h5, int device, srcfd_mode
 int srcfd_resampler_create(int device, const double* Ry, const double* Rx, int in_h, int in_w, int out_h, int out_w,
                            srcfd_resampler** out);
 void srcfd_resampler_destroy(srcfd_resampler* r);
-/* in_dev float32 (n,in_h,in_w) -> out_dev float64 (n,out_h,out_w), enqueued on hip_stream. */
+/* in_dev float32 (n,in_h,in_w) -> out_dev float64 (n,out_h,out_w), enqueued on hip_stream.
+ * Pointers: both dense; in_dev 4-byte, out_dev 8-byte aligned (element-wise loads and stores only). */
 int srcfd_resample_device(srcfd_resampler* r, const float* in_dev, int n, double* out_dev, void* hip_stream);
 /* srcfd_predict followed by the resampling, without the float32 result leaving the device:
  * `predict` + inverse standardise + NaN guard (bfs_ml_accelerated.py:1109-1127) + resample back
@@ -272,7 +294,8 @@ int srcfd_predict_resampled(srcfd_model* m, srcfd_resampler* r, const float* x, 
  * blend of the training statistics with np.mean / np.std of the float32 field (:1091-1097; adaptive = 0: the training
  * statistics as they are).  fields_dev float64 (n,h,w); train_stats_dev float64 (n,2) = (mean, std) of each sample's
  * component; writes x_dev float32 (n,lr,lr) [or (n,h,w)] and in_affine_dev float32 (n,2), the arguments
- * srcfd_predict_device takes.  The statistics reproduce numpy's float32 arithmetic (pairwise sums, NumPy-2 scalar
+ * srcfd_predict_device takes.  Pointers: all dense; the float64 inputs (fields_dev, Ry_dev (lr,h), Rx_dev (lr,w), train_stats_dev)
+ * 8-byte, x_dev and in_affine_dev 4-byte aligned (element-wise loads and stores only).  The statistics reproduce numpy's float32 arithmetic (pairwise sums, NumPy-2 scalar
  * promotion) bit for bit.  Sides up to 32. */
 int srcfd_prepare_inputs_device(const double* fields_dev, int n, int h, int w, const double* Ry_dev, const double* Rx_dev, int lr,
                                 const double* train_stats_dev, int adaptive, double blend, float* x_dev, float* in_affine_dev,
@@ -369,6 +392,9 @@ int srcfd_evalset_destroy(srcfd_evalset* e);
  * s % C to sample s.  flags / nonfinite_dev: passed to every predict call (SRCFD_FLAG_NAN_GUARD; the counter is ADDED to).
  * srcfd_tiles_cut_device: the cut alone -- x_dev (N, lh, lw, 1), and for each (C, 2) array given the per-sample (N, 2) array.
  * srcfd_tiles_stitch_device: the stitch alone, of the samples [s0, s1) (multiples of C) of the tiler's grid: sample s is plane
+ * Pointers of the three calls: dense float32 / int32 arrays, 4-byte aligned.  The cut reads and writes element by element.  The
+ * stitch loads from y_dev and stores to out_dev V floats at a time and takes the narrower V itself when the two pointers share less
+ * than 4 V bytes of alignment (never SRCFD_EINVAL): the plan's align_bytes below.
  * src_index_dev[s] of y_dev (int32 device array of N entries, indexed by s) or, with NULL, plane s - s0; y_dev holds y_rows planes
  * of hh x hw float32.  Only the tiles of [s0, s1) are written.  A tile whose index lies outside [0, y_rows) is left as it was.
  *
@@ -577,6 +603,10 @@ int srcfd_trainer_get_plan(const srcfd_trainer* t, int* fused_tail, int* fused_e
  * gradients runs on a stream of the trainer's own that forks from and joins hip_stream inside the call.  From the second
  * call with the same params_dev / grads_dev / sse_dev / n / loss_scale the step is replayed as one hipGraph (x_dev and
  * y_dev are first copied to staging buffers, so they need not stay at one address).
+ * Pointers: x_dev, y_dev dense (n, ...) float32, params_dev / grads_dev dense float32 of srcfd_trainer_num_params elements, all
+ * 4-byte aligned; sse_dev 8-byte aligned.  The staging copy is one kernel of 16-byte accesses when x_dev and y_dev are both 16-byte
+ * aligned and both element counts are multiples of 4, else two device-to-device copies (the narrower path, same bits); params_dev
+ * is read and grads_dev written one element at a time through the trainer's index map.
  * One trainer, one stream at a time: the activations, gradient slabs, staging buffers and step graphs belong to the trainer, so
  * calls on the SAME trainer (this entry, the _ex one below) are ordered only when they are enqueued on the same stream; a caller
  * that changes streams between two calls orders them itself.  srcfd_adam_step keeps no state of its own: it is ordered by the
@@ -593,7 +623,8 @@ int srcfd_trainer_forward_backward(srcfd_trainer* t, const float* params_dev, co
 #define SRCFD_TRAIN_SAME_PARAMS 2
 int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev, const float* x_dev, const float* y_dev, int n,
                                       float loss_scale, float* grads_dev, double* sse_dev, int flags, void* hip_stream);
-/* Keras Adam update, step counted from 1: alpha_t = lr*sqrt(1-beta2^t)/(1-beta1^t); p -= alpha_t*m/(sqrt(v)+eps). */
+/* Keras Adam update, step counted from 1: alpha_t = lr*sqrt(1-beta2^t)/(1-beta1^t); p -= alpha_t*m/(sqrt(v)+eps).
+ * Pointers: four dense float32 arrays of n elements, 4-byte aligned (one element per lane). */
 int srcfd_adam_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n, int step, float lr,
                     float beta1, float beta2, float eps, void* hip_stream);
 

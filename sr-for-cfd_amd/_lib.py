@@ -218,3 +218,57 @@ def check(rc: int) -> int:
 
 def enc(path) -> bytes:
     return os.fsencode(path)
+
+
+def _squeezed(shape) -> tuple:
+    return tuple(int(d) for d in shape if int(d) != 1)
+
+
+def device_ptr(t, what: str, dtype=None, shape=None, device=None, optional: bool = False, exact: bool = False, min_numel: int = 0):
+    """The one place a torch CUDA tensor becomes the `void*` of a libsrcfd device entry (include/srcfd.h, "device pointers": every
+    device pointer is a dense C-ordered array of its element type, aligned to that element).  Returns the `c_void_p`; raises
+    ValueError that names `what` and the offending property when `t`
+      * is None and not `optional` (with `optional`, None gives None: the entry's "no such argument");
+      * is not a CUDA tensor, or is on a device other than index `device`;
+      * has a dtype other than `dtype` (one dtype or a tuple of accepted ones);
+      * has the wrong shape or is not contiguous.
+    shape = (n, *per_sample): the first dimension is n, the remaining ones equal the per-sample shape once dimensions of size 1 are
+    dropped on both sides -- `y.view(n, hr, hr)` for an (hr, hr, 1) output and `y[:n]` are legal, a channel slice or a transposed
+    view is not.  exact=True: the shape as it stands.  n == 0 with a zero-row tensor passes as it is: the entry launches nothing
+    and the pointer is never followed.  min_numel: for an argument without a shape (a counter), the fewest elements.
+    Only attributes are read (is_cuda, device.index, dtype, shape, is_contiguous(), data_ptr()): nothing is enqueued or synchronised."""
+    if t is None:
+        if optional:
+            return None
+        raise ValueError(f"{what} is required, got None")
+    if not getattr(t, "is_cuda", False):
+        raise ValueError(f"{what} must be a CUDA tensor, got {type(t).__name__}" + (f" on {t.device}" if hasattr(t, "device") else ""))
+    if device is not None and t.device.index != int(device):
+        raise ValueError(f"{what} is on device cuda:{t.device.index}, the handle is on cuda:{int(device)}")
+    if dtype is not None:
+        accepted = tuple(dtype) if isinstance(dtype, (tuple, list)) else (dtype,)
+        if t.dtype not in accepted:
+            raise ValueError(f"{what} has dtype {t.dtype}, expected {' or '.join(str(d) for d in accepted)}")
+    got = tuple(int(d) for d in t.shape)
+    if shape is not None:
+        shape = tuple(int(d) for d in shape)
+        if exact:
+            if got != shape:
+                raise ValueError(f"{what} has shape {got}, expected {shape}")
+        else:
+            if not got or got[0] != shape[0]:
+                raise ValueError(f"{what} has shape {got}: its first dimension must be n = {shape[0]} (expected (n, *{shape[1:]}))")
+            if shape[0] == 0:
+                return C.c_void_p(t.data_ptr())
+            if _squeezed(got[1:]) != _squeezed(shape[1:]):
+                raise ValueError(f"{what} has per-sample shape {got[1:]}, expected {shape[1:]} (dimensions of size 1 aside)")
+    if min_numel:
+        numel = 1
+        for d in got:
+            numel *= d
+        if numel < min_numel:
+            raise ValueError(f"{what} has {numel} element(s), needs at least {min_numel}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} is not contiguous (shape {got}, strides {tuple(t.stride())}): the library reads and writes dense "
+                         "C-ordered memory; pass t.contiguous()")
+    return C.c_void_p(t.data_ptr())

@@ -134,6 +134,7 @@ class SRModel:
         self._h = handle
         self.device = device
         self._keep = None
+        self._io_shapes = None   # (input_shape, output_shape), read once for the device-call checks: a handle's graph never changes
 
     # -- construction -------------------------------------------------------
     @staticmethod
@@ -408,19 +409,33 @@ class SRModel:
     def predict_device(self, x, y, in_affine=None, out_affine=None, nan_guard=False, nonfinite=None, stream=None):
         """Device-resident forward on torch CUDA tensors (plumbing only):
         x float32 (n,h,w,c); y float32/bfloat16/float16 (n,oh,ow,oc); affines
-        float32 (n,2).  Enqueues on ``stream`` (torch stream) or the current one."""
+        float32 (n,2); nonfinite int64, at least one element (added to).  Enqueues on ``stream`` (torch stream) or the current
+        one.  Every tensor is checked first (_lib.device_ptr: on the model's device, dtype, contiguous, n rows of the model's
+        shape); a ValueError leaves nothing enqueued."""
         import torch
 
-        if not (x.is_cuda and y.is_cuda and x.is_contiguous() and y.is_contiguous()):
-            raise ValueError("predict_device needs contiguous CUDA tensors")
-        if x.dtype != torch.float32:
-            raise ValueError("x must be float32")
-        dt = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}[y.dtype]
-        n = x.shape[0]
+        n, dt, px, py, pin, pout, pbad = self._device_args(x, y, in_affine, out_affine, nonfinite)
         st = stream if stream is not None else torch.cuda.current_stream(x.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        L.check(L.lib.srcfd_predict_device(self._h, p(x), n, p(in_affine), p(out_affine), p(y), dt,
-                                           L.FLAG_NAN_GUARD if nan_guard else 0, p(nonfinite), C.c_void_p(st.cuda_stream)))
+        L.check(L.lib.srcfd_predict_device(self._h, px, n, pin, pout, py, dt,
+                                           L.FLAG_NAN_GUARD if nan_guard else 0, pbad, C.c_void_p(st.cuda_stream)))
+
+    def _device_args(self, x, y, in_affine=None, out_affine=None, nonfinite=None, names=("x", "y")):
+        """(n, output dtype code, the five device pointers) of a `predict_device` call, or ValueError; launches nothing.
+        names: what x and y are called in the message (a caller that derived them from arguments of its own says which)."""
+        import torch
+
+        if self.device < 0:
+            raise L.NoDeviceError("predict_device needs a device handle")
+        if self._io_shapes is None:
+            self._io_shapes = (tuple(self.input_shape), tuple(self.output_shape))
+        n = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) else 0
+        px = L.device_ptr(x, names[0], torch.float32, (n,) + self._io_shapes[0], self.device)
+        py = L.device_ptr(y, names[1], (torch.float32, torch.bfloat16, torch.float16), (n,) + self._io_shapes[1], self.device)
+        dt = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}[y.dtype]
+        pin = L.device_ptr(in_affine, "in_affine", torch.float32, (n, 2), self.device, optional=True, exact=True)
+        pout = L.device_ptr(out_affine, "out_affine", torch.float32, (n, 2), self.device, optional=True, exact=True)
+        pbad = L.device_ptr(nonfinite, "nonfinite", torch.int64, None, self.device, optional=True, min_numel=1)
+        return n, dt, px, py, pin, pout, pbad
 
     def debug_activation(self, index: int, shape, dtype=np.uint16) -> np.ndarray:
         """Test hook (srcfd_model_debug_activation): raw 16-bit inter-kernel activations."""
@@ -539,15 +554,11 @@ class Tiler:
         return tiled_plan(self.model.input_shape, self.model.output_shape, self.tiles_y, self.tiles_x, self.channels, self.max_chunk, chunk, align_bytes,
                           self.overlap)
 
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _check(self, t, shape, what, dtype=None):
+    def _check(self, t, shape, what, dtype=None, optional=False):
+        """The device pointer of `t` (None for an absent optional one), or ValueError: a contiguous `dtype` (float32) tensor of exactly
+        `shape` on the model's device (_lib.device_ptr)."""
         import torch
-        dtype = dtype or torch.float32
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device.index == self.model.device):
-            raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{self.model.device}")
+        return L.device_ptr(t, what, dtype or torch.float32, shape, self.model.device, optional=optional, exact=True)
 
     def set_stream(self, stream=None):
         """Binds the torch stream (None: the current one) every later call of this tiler enqueues on."""
@@ -558,28 +569,30 @@ class Tiler:
     def run(self, field, out, in_affine=None, out_affine=None, nan_guard: bool = False, nonfinite=None, stream=None):
         """field (TY*lh, TX*lw, C) -> out (TY*hh, TX*hw, C), float32 CUDA tensors; affines (C, 2) CUDA tensors or None;
         `nonfinite`: optional int64 CUDA counter that is added to.  Enqueues on `stream` and returns without synchronising."""
-        self._check(field, self.in_shape, "field")
-        self._check(out, self.out_shape, "out")
-        for a, nm in ((in_affine, "in_affine"), (out_affine, "out_affine")):
-            if a is not None:
-                self._check(a, (self.channels, 2), nm)
+        import torch
+        pf = self._check(field, self.in_shape, "field")
+        po = self._check(out, self.out_shape, "out")
+        pin = self._check(in_affine, (self.channels, 2), "in_affine", optional=True)
+        pout = self._check(out_affine, (self.channels, 2), "out_affine", optional=True)
+        pbad = L.device_ptr(nonfinite, "nonfinite", torch.int64, None, self.model.device, optional=True, min_numel=1)
         self.set_stream(stream)
-        L.check(L.lib.srcfd_tiler_run(self._h, self._p(field), self._p(in_affine), self._p(out_affine), self._p(out),
-                                      L.FLAG_NAN_GUARD if nan_guard else 0, self._p(nonfinite)))
+        L.check(L.lib.srcfd_tiler_run(self._h, pf, pin, pout, po, L.FLAG_NAN_GUARD if nan_guard else 0, pbad))
         return out
 
     def cut(self, field, in_affine=None, out_affine=None, stream=None):
         """The cut alone: (x (n, lh, lw, 1), in_affine (n, 2) or None, out_affine (n, 2) or None), new CUDA tensors."""
         import torch
-        self._check(field, self.in_shape, "field")
+        pf = self._check(field, self.in_shape, "field")
         x = torch.empty((self.n, self.lh, self.lw, 1), dtype=torch.float32, device=field.device)
-        per = [None, None]
+        per, ptr = [None, None], [None, None]
         for i, (a, nm) in enumerate(((in_affine, "in_affine"), (out_affine, "out_affine"))):
+            ptr[i] = self._check(a, (self.channels, 2), nm, optional=True)
             if a is not None:
-                self._check(a, (self.channels, 2), nm)
                 per[i] = torch.empty((self.n, 2), dtype=torch.float32, device=field.device)
         self.set_stream(stream)
-        L.check(L.lib.srcfd_tiles_cut_device(self._h, self._p(field), self._p(in_affine), self._p(out_affine), self._p(x), self._p(per[0]), self._p(per[1])))
+        L.check(L.lib.srcfd_tiles_cut_device(self._h, pf, ptr[0], ptr[1], self._check(x, x.shape, "x"),
+                                             self._check(per[0], (self.n, 2), "in_affine rows", optional=True),
+                                             self._check(per[1], (self.n, 2), "out_affine rows", optional=True)))
         return x, per[0], per[1]
 
     def stitch(self, y, out, s0: int = 0, s1: Optional[int] = None, src_index=None, stream=None):
@@ -587,14 +600,12 @@ class Tiler:
         n entries (sample -> plane of y) or None (sample s is plane s - s0).  With an overlap: the whole range only."""
         import torch
         s1 = self.n if s1 is None else s1
-        if not (y.is_cuda and y.is_contiguous() and y.dtype == torch.float32 and y.dim() >= 3 and tuple(y.shape[1:3]) == (self.hh, self.hw)
-                and y.numel() == y.shape[0] * self.hh * self.hw):
+        if not (hasattr(y, "dim") and y.dim() >= 3 and tuple(y.shape[1:3]) == (self.hh, self.hw)):
             raise ValueError(f"y must be a contiguous float32 CUDA tensor (rows, {self.hh}, {self.hw})")
-        if src_index is not None:
-            self._check(src_index, (self.n,), "src_index", torch.int32)
+        py = L.device_ptr(y, "y", torch.float32, (int(y.shape[0]), self.hh, self.hw), self.model.device)
+        pidx = self._check(src_index, (self.n,), "src_index", torch.int32, optional=True)
         # out may be a view into a larger allocation: only its own extent is written
-        if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == self.out_shape):
-            raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {self.out_shape}")
+        po = self._check(out, self.out_shape, "out")
         self.set_stream(stream)
-        L.check(L.lib.srcfd_tiles_stitch_device(self._h, self._p(y), int(y.shape[0]), self._p(src_index), int(s0), int(s1), self._p(out)))
+        L.check(L.lib.srcfd_tiles_stitch_device(self._h, py, int(y.shape[0]), pidx, int(s0), int(s1), po))
         return out

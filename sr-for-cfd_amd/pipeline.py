@@ -265,11 +265,19 @@ def _super_resolution_batch_on_device(coarse_batch, n_f, model, dev, stats_lr, s
     side = lr_dim if resample else h
     x = torch.empty((3 * n_f, side, side, 1), dtype=torch.float32, device=dev)
     ain = torch.empty((3 * n_f, 2), dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    L.check(L.lib.srcfd_prepare_inputs_device(p(f_dev), 3 * n_f, h, w, p(Ry), p(Rx), lr_dim, p(train), int(bool(use_adaptive_normalization)),
-                                              float(blend_factor), p(x), p(ain), C.c_void_p(st.cuda_stream)))
     y = torch.empty((3 * n_f, hr_dim, hr_dim, 1), dtype=torch.float32, device=dev)
     bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    # every tensor of both device calls is checked before the first of them is enqueued: an lr_dim / hr_dim that is not the model's
+    # is refused here, not found by the forward after the preparation kernel ran (or, for hr_dim, by a store past the end of y)
+    model._device_args(x, y, ain, aout, bad, names=(f"x ({side}, {side}, 1), from lr_dim = {lr_dim} and the fields' size,",
+                                                    f"y ({hr_dim}, {hr_dim}, 1), from hr_dim = {hr_dim},"))
+    f64 = torch.float64
+    p = lambda t, what, shape: L.device_ptr(t, what, f64, shape, model.device, optional=True, exact=True)
+    L.check(L.lib.srcfd_prepare_inputs_device(p(f_dev, "fields", (3 * n_f, h, w)), 3 * n_f, h, w, p(Ry, "Ry", (lr_dim, h)), p(Rx, "Rx", (lr_dim, w)),
+                                              lr_dim, p(train, "train_stats", (3 * n_f, 2)), int(bool(use_adaptive_normalization)), float(blend_factor),
+                                              L.device_ptr(x, "x", torch.float32, (3 * n_f, side, side), model.device),
+                                              L.device_ptr(ain, "in_affine", torch.float32, (3 * n_f, 2), model.device, exact=True),
+                                              C.c_void_p(st.cuda_stream)))
     model.predict_device(x, y, in_affine=ain, out_affine=aout, nan_guard=True, nonfinite=bad)
     if resample:
         back = rs.square_to_rect_resampler(hr_dim, hr_dim, hr_dim, float(lx), float(ly), model.device)

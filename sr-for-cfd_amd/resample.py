@@ -68,13 +68,16 @@ class Resampler:
             pass
 
     def apply_device(self, x, out=None, stream=None):
-        """x: float32 CUDA tensor (n,in_h,in_w) -> float64 CUDA tensor (n,out_h,out_w)."""
+        """x: float32 CUDA tensor (n,in_h,in_w) -> float64 CUDA tensor (n,out_h,out_w).  Both are checked first (_lib.device_ptr:
+        contiguous, on this resampler's device, n samples of its sizes); a ValueError leaves nothing enqueued."""
         import torch
-        n = int(x.shape[0])
+        n = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) else 0
+        px = L.device_ptr(x, "x", torch.float32, (n, self.in_h, self.in_w), self.device)
         if out is None:
             out = torch.empty((n, self.out_h, self.out_w), dtype=torch.float64, device=x.device)
+        pout = L.device_ptr(out, "out", torch.float64, (n, self.out_h, self.out_w), self.device)
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.lib.srcfd_resample_device(self._h, C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(st)))
+        L.check(L.lib.srcfd_resample_device(self._h, px, n, pout, C.c_void_p(st)))
         return out
 
 

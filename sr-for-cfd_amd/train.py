@@ -81,6 +81,7 @@ class Trainer:
         self.max_batch = max_batch
         oh, ow, oc = model.output_shape
         self.out_elems = oh * ow * oc
+        self._in_shape, self._out_shape = tuple(model.input_shape), (oh, ow, oc)
         self._layout = [(d["name"], d["kernel"].shape, d["bias"].shape) for d in model.layers() if "kernel" in d]
 
     def close(self):
@@ -107,20 +108,29 @@ class Trainer:
         same_params=True: self.params has not changed since this trainer's previous call (later micro-batches of one
         optimiser step) -- the re-packing of the parameters is skipped (SRCFD_TRAIN_SAME_PARAMS)."""
         import torch
-        n = int(x.shape[0])
+        n = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) else 0
+        # x, y: n contiguous float32 samples of the model's shapes on its device (_lib.device_ptr) -- a channel slice such as
+        # fields[..., 0:1] has the right shape and the wrong memory; a ValueError leaves nothing enqueued
+        px = L.device_ptr(x, "x", torch.float32, (n,) + self._in_shape, self.model.device)
+        py = L.device_ptr(y, "y", torch.float32, (n,) + self._out_shape, self.model.device)
         gb = global_batch if global_batch is not None else n
         st = torch.cuda.current_stream(self.device)
         L.check(L.lib.srcfd_trainer_forward_backward_ex(
-            self._h, C.c_void_p(self.params.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), n,
-            C.c_float(1.0 / (gb * self.out_elems)), C.c_void_p(self.grads.data_ptr()), C.c_void_p(self.sse.data_ptr()),
+            self._h, self._flat("params"), px, py, n, C.c_float(1.0 / (gb * self.out_elems)), self._flat("grads"),
+            L.device_ptr(self.sse, "sse", torch.float64, (1,), self.model.device, exact=True),
             (L.TRAIN_OVERWRITE if overwrite else 0) | (L.TRAIN_SAME_PARAMS if same_params else 0), C.c_void_p(st.cuda_stream)))
+
+    def _flat(self, name):
+        """The device pointer of one of the trainer's own flat float32 arrays (params, grads, m, v), checked like a caller's."""
+        import torch
+        return L.device_ptr(getattr(self, name), name, torch.float32, (self.n_params,), self.model.device, exact=True)
 
     def apply_adam(self) -> None:
         import torch
+        ptrs = [self._flat(name) for name in ("params", "grads", "m", "v")]
         self.t += 1
         st = torch.cuda.current_stream(self.device)
-        L.check(L.lib.srcfd_adam_step(C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr()), C.c_void_p(self.m.data_ptr()),
-                                      C.c_void_p(self.v.data_ptr()), self.n_params, self.t, C.c_float(self.lr), C.c_float(self.beta1),
+        L.check(L.lib.srcfd_adam_step(*ptrs, self.n_params, self.t, C.c_float(self.lr), C.c_float(self.beta1),
                                       C.c_float(self.beta2), C.c_float(self.eps), C.c_void_p(st.cuda_stream)))
 
     def step(self, x, y, global_batch: Optional[int] = None, return_loss: bool = True):

@@ -14,7 +14,8 @@ Every guard lies inside the one allocation the test owns, so a defect shows as a
 than the guard is not seen (and is no more dangerous than with an exact-size tensor)."""
 import numpy as np
 
-ALIGN = 256          # bytes: the payload starts at a multiple of this inside its allocation, like a fresh device allocation
+ALIGN = 256          # bytes: the payload starts at a multiple of this inside its allocation, like a fresh device allocation,
+                     # or `skew` elements behind one (guarded / poisoned, skew=): what a contiguous view into a larger tensor gives
 SENTINEL32 = 0x7FA5A5A5            # float32 NaN payload
 SENTINEL16 = 0x7FA5                # a NaN in bfloat16 and in float16
 SENTINEL64 = 0x7FF5A5A5A5A5A5A5    # float64 NaN payload
@@ -53,22 +54,27 @@ def affine_guard():
     return round_guard(2, 4)
 
 
-def guarded(xp, shape, dtype, guard_elems, fill=None, device="cuda"):
+def guarded(xp, shape, dtype, guard_elems, fill=None, device="cuda", skew=0):
     """(big, view): `big` is the flat integer-word allocation [guard | payload | guard], every word = `fill` (default: the dtype's
-    sentinel); `view` is the contiguous payload as `dtype` and `shape`.  torch: on `device`."""
+    sentinel); `view` is the contiguous payload as `dtype` and `shape`.  torch: on `device`.
+    skew (elements, 0 <= skew < ALIGN / itemsize): the payload starts skew * itemsize bytes behind a multiple of ALIGN -- aligned to
+    its element and to nothing wider when skew is odd; the front guard grows by `skew` words, the rear guard keeps its size."""
     word, sentinel, itemsize = _kind(xp, dtype)
     fill = sentinel if fill is None else fill
     g = round_guard(guard_elems, itemsize)
+    skew = int(skew)
+    assert 0 <= skew < ALIGN // itemsize, skew
     size = int(np.prod(shape, dtype=np.int64)) if len(tuple(shape)) else 1
+    total = 2 * g + skew + size
     if _is_np(xp):
-        # over-allocate so that the payload itself starts at a multiple of ALIGN bytes
-        raw = np.empty((2 * g + size) * itemsize + ALIGN, np.uint8)
+        # over-allocate so that the payload itself starts at a multiple of ALIGN bytes (+ the skew)
+        raw = np.empty(total * itemsize + ALIGN, np.uint8)
         skip = (-raw.ctypes.data) % ALIGN
-        big = raw[skip:skip + (2 * g + size) * itemsize].view(word)
+        big = raw[skip:skip + total * itemsize].view(word)
         big[:] = fill
-        return big, big[g:g + size].view(dtype).reshape(shape)
-    big = xp.full((2 * g + size,), fill, dtype=word, device=device)
-    return big, big[g:g + size].view(dtype).view(tuple(shape))
+        return big, big[g + skew:g + skew + size].view(dtype).reshape(shape)
+    big = xp.full((total,), fill, dtype=word, device=device)
+    return big, big[g + skew:g + skew + size].view(dtype).view(tuple(shape))
 
 
 def refill(big, fill=None):
@@ -100,22 +106,26 @@ def guarded_nbytes(shape, dtype, guard_elems):
     return (2 * round_guard(guard_elems, itemsize) + int(np.prod(shape, dtype=np.int64))) * itemsize + ALIGN
 
 
-def poisoned(xp, array, guard_elems, device="cuda"):
-    """(big, view) for an INPUT: `array` (numpy, float32 or float64) sits in the payload, quiet NaNs fill both guards."""
+def poisoned(xp, array, guard_elems, device="cuda", skew=0):
+    """(big, view) for an INPUT: `array` (numpy, float32 or float64) sits in the payload, quiet NaNs fill both guards.
+    skew: as in `guarded`."""
     array = np.ascontiguousarray(array)
     assert array.dtype in (np.float32, np.float64), array.dtype
     itemsize = array.dtype.itemsize
     g = round_guard(guard_elems, itemsize)
-    flat = np.full(2 * g + array.size, np.nan, array.dtype)
-    flat[g:g + array.size] = array.ravel()
+    skew = int(skew)
+    assert 0 <= skew < ALIGN // itemsize, skew
+    lo = g + skew
+    flat = np.full(2 * g + skew + array.size, np.nan, array.dtype)
+    flat[lo:lo + array.size] = array.ravel()
     if _is_np(xp):
         raw = np.empty(flat.nbytes + ALIGN, np.uint8)
         skip = (-raw.ctypes.data) % ALIGN
         big = raw[skip:skip + flat.nbytes].view(array.dtype)
         big[:] = flat
-        return big, big[g:g + array.size].reshape(array.shape)
+        return big, big[lo:lo + array.size].reshape(array.shape)
     big = xp.from_numpy(flat).to(device)
-    return big, big[g:g + array.size].view(array.shape)
+    return big, big[lo:lo + array.size].view(array.shape)
 
 
 def _ptr(t):

@@ -60,6 +60,89 @@ def test_layout_and_sentinels(backend):
             gb.assert_fully_written(view)
 
 
+def _ptr(xp, t):
+    return t.ctypes.data if xp is np else t.data_ptr()
+
+
+@pytest.mark.parametrize("skew", [1, 2, 3])
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_skewed_layout_keeps_its_guards(backend, skew):
+    """skew elements behind a multiple of ALIGN: element-aligned, both guards whole (the front one `skew` words longer), and every
+    planted defect is still reported at its payload-relative index."""
+    xp = _xp(backend)
+    for dtype in _dtypes(xp):
+        big, view = _make_skewed(xp, (3, 5, 7), dtype, 35, skew)
+        itemsize = big.itemsize if xp is np else big.element_size()
+        g = gb.round_guard(35, itemsize)
+        lo = g + skew
+        assert _ptr(xp, view) - _ptr(xp, big) == lo * itemsize
+        if xp is np or _ptr(xp, big) % gb.ALIGN == 0:           # numpy: by construction; torch on the CPU: when the allocator gives it
+            assert _ptr(xp, view) % gb.ALIGN == skew * itemsize
+        assert _ptr(xp, view) % itemsize == 0
+        assert (big.size if xp is np else big.numel()) == 2 * g + skew + 105
+        assert (view.flags.c_contiguous if xp is np else view.is_contiguous()) and tuple(view.shape) == (3, 5, 7)
+        gb.assert_guards_intact(big, view)
+        with pytest.raises(AssertionError, match="105 output element"):
+            gb.assert_fully_written(view)
+        _fill_clean(xp, view)
+        gb.assert_guards_intact(big, view, what="clean")
+        gb.assert_fully_written(view, what="clean")
+        # the words next to the payload on both sides, and the far ends of both guards
+        for pos, rel, front in ((lo - 1, -1, True), (0, -lo, True), (lo + 105, 105, False), (2 * g + skew + 104, 105 + g - 1, False)):
+            old = int(big[pos])
+            big[pos] = 0
+            with pytest.raises(AssertionError, match=r"wrote outside its output extent") as e:
+                gb.assert_guards_intact(big, view, what="planted")
+            msg = str(e.value)
+            assert f"[{rel}]" in msg and (("1 word(s) in front" in msg and "0 behind" in msg) if front else ("0 word(s) in front" in msg and "1 behind" in msg)), msg
+            big[pos] = old
+        gb.assert_guards_intact(big, view)
+        # the first and the last payload element left unwritten
+        fill = {2: gb.SENTINEL16, 4: gb.SENTINEL32, 8: gb.SENTINEL64}[itemsize]
+        for pos, where in ((lo, r"\(0, 0, 0\)"), (lo + 104, r"\(2, 4, 6\)")):
+            old = int(big[pos])
+            big[pos] = fill
+            with pytest.raises(AssertionError, match=r"1 output element\(s\) were never written, the first at \[" + where):
+                gb.assert_fully_written(view, what="planted")
+            big[pos] = old
+
+
+def _make_skewed(xp, shape, dtype, guard, skew):
+    return gb.guarded(xp, shape, dtype, guard, skew=skew) if xp is np else gb.guarded(xp, shape, dtype, guard, device="cpu", skew=skew)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_skew_zero_is_the_old_layout_and_a_skew_of_a_whole_block_is_refused(backend):
+    xp = _xp(backend)
+    big0, view0 = _make(xp, (4, 9), xp.float32, 36)
+    big1, view1 = _make_skewed(xp, (4, 9), xp.float32, 36, 0)
+    assert (big0.size if xp is np else big0.numel()) == (big1.size if xp is np else big1.numel())
+    assert _ptr(xp, view0) - _ptr(xp, big0) == _ptr(xp, view1) - _ptr(xp, big1)
+    with pytest.raises(AssertionError):
+        _make_skewed(xp, (4, 9), xp.float32, 36, gb.ALIGN // 4)
+    with pytest.raises(AssertionError):
+        _make_skewed(xp, (4, 9), xp.float32, 36, -1)
+
+
+@pytest.mark.parametrize("skew", [1, 2, 3])
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_skewed_poisoned_inputs(backend, skew):
+    xp = _xp(backend)
+    rng = np.random.default_rng(skew)
+    for dt in (np.float32, np.float64):
+        a = rng.standard_normal((3, 5, 2)).astype(dt)
+        big, view = gb.poisoned(xp, a, 10, skew=skew) if xp is np else gb.poisoned(xp, a, 10, device="cpu", skew=skew)
+        g = gb.round_guard(10, a.itemsize)
+        got = view if xp is np else view.numpy()
+        flat = big if xp is np else big.numpy()
+        assert got.dtype == dt and np.array_equal(got, a)
+        assert flat.size == 2 * g + skew + a.size and np.isnan(flat[:g + skew]).all() and np.isnan(flat[g + skew + a.size:]).all()
+        assert flat[g + skew + a.size:].size == g
+        assert _ptr(xp, view) - _ptr(xp, big) == (g + skew) * a.itemsize
+        if xp is np:
+            assert view.ctypes.data % gb.ALIGN == skew * a.itemsize
+
+
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_a_clean_fill_passes(backend):
     xp = _xp(backend)
