@@ -281,6 +281,11 @@ void srcfd_resampler_destroy(srcfd_resampler* r);
 /* in_dev float32 (n,in_h,in_w) -> out_dev float64 (n,out_h,out_w), enqueued on hip_stream.
  * Pointers: both dense; in_dev 4-byte, out_dev 8-byte aligned (element-wise loads and stores only). */
 int srcfd_resample_device(srcfd_resampler* r, const float* in_dev, int n, double* out_dev, void* hip_stream);
+/* The same for float64 input (a solver's fields, srcfd_fine_batch_get_fields_device): in_dev float64 (n,in_h,in_w), enqueued on
+ * `stream` (a hipStream_t).  The same kernels instantiated for a float64 operand: the same two float64 products in the same
+ * summation order, so for input values that are exactly floats the output equals srcfd_resample_device's bit for bit.
+ * Pointers: both dense, 8-byte aligned. */
+int srcfd_resample_device_f64(srcfd_resampler* r, const double* in_dev, int n, double* out_dev, void* stream);
 /* srcfd_predict followed by the resampling, without the float32 result leaving the device:
  * `predict` + inverse standardise + NaN guard (bfs_ml_accelerated.py:1109-1127) + resample back
  * (:1130-1135).  y is float64 host (n,out_h,out_w), like scipy returns it. */
@@ -504,6 +509,10 @@ int srcfd_fine_solver_init(srcfd_fine_solver* s, const double* var);
  * srcfd_fine_batch_init_from_prediction on a batch of one. */
 int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m, srcfd_resampler* r, const float* x,
                                            const float* in_affine, const float* out_affine, int flags, int64_t* n_nonfinite);
+/* srcfd_fine_batch_init_from_fields_device and srcfd_fine_batch_get_fields_device on the batch of one that a srcfd_fine_solver
+ * is: fields_dev and out_dev are (3, h, w) and (3, ny, nx). */
+int srcfd_fine_solver_init_from_fields_device(srcfd_fine_solver* s, srcfd_resampler* r, const void* fields_dev, int dtype, void* stream);
+int srcfd_fine_solver_get_fields_device(srcfd_fine_solver* s, void* out_dev, int dtype, void* stream);
 /* Up to max_iterations more outer iterations (none once converged).  *iterations = outer iterations since init; rms = the
  * last _convergence_check's residuals; history [history_len][3] receives rms at every iteration count divisible by 100 that
  * this call reaches, in order (residual_history, :418-421).  run(N) then run(M) equals run(N+M) bit for bit.  NaN / Inf in
@@ -548,6 +557,28 @@ int srcfd_fine_batch_init(srcfd_fine_batch* b, const double* var);
 int srcfd_fine_batch_init_from_prediction(srcfd_fine_batch* b, srcfd_model* m, srcfd_resampler* r, const float* x, int n_warm,
                                           const int* cases, const float* in_affine, const float* out_affine, int flags,
                                           int64_t* n_nonfinite);
+/* srcfd_fine_batch_init_from_prediction without the network: fields that are already on the device -- a plainly interpolated
+ * coarse field (the control arm of a warm-start study), a torch tensor, another batch's srcfd_fine_batch_get_fields_device.
+ * fields_dev: (3*n_warm, h, w) of dtype SRCFD_F32 or SRCFD_F64, dense, aligned to its element; u, v, p of each field in the layout
+ * of the SR prediction and the coarse-field files, field[j, i] -> Var[k, 1+i, 1+j].  r NULL: (h, w) is the batch's (ny, nx).
+ * Otherwise (h, w) is the resampler's input, its output is the batch's (ny, nx), and the fields pass through it in float64
+ * (srcfd_resample_device[_f64]'s products) into the resampler's own scratch, sized from n_warm; nothing else is allocated.  The
+ * cases cases[0..n_warm) take the fields (NULL: case i takes field i, i < n_warm), every other case starts from zero fields, then
+ * the priming of srcfd_fine_batch_init: every case is RUNNING at iteration 0.  Values are taken as they are -- no NaN guard, as
+ * with a host var.  Ordering: the batch's own stream waits for everything enqueued on `stream` (a hipStream_t; NULL: the default
+ * stream) up to the call, so the caller does not synchronise first; the call returns when the state is primed, as
+ * srcfd_fine_batch_init does, and fields_dev is then no longer in use.  SRCFD_EINVAL, naming the argument: a dtype other than
+ * the two, n_warm outside 1..n_cases, a case index out of range or listed twice, a resampler whose output is not the batch's mesh
+ * or that lives on another device.  (The C side cannot see h and w of fields_dev; the Python binding checks them.)  Everything
+ * is checked before anything is enqueued: a refused call leaves the batch as it was. */
+int srcfd_fine_batch_init_from_fields_device(srcfd_fine_batch* b, srcfd_resampler* r, const void* fields_dev, int dtype, int n_warm,
+                                             const int* cases, void* stream);
+/* The inverse transposition: out_dev (3*n, ny, nx) of dtype SRCFD_F32 or SRCFD_F64, dense, aligned to its element, receives
+ * out[3c+k, j, i] = Var[k, 1+i, 1+j] of the cases cases[0..n) (NULL: n == n_cases, all cases in order) -- the fields of
+ * FineSolverBatch.fields(), without a host copy.  float64: an exact copy; float32: rounded to nearest.  Needs an initialised
+ * batch.  Ordering: the batch's stream waits for `stream` (a hipStream_t) as above, the copy is complete when the call returns,
+ * and `stream` is made to wait for it as well.  Counts one host synchronisation (counters[3]).  SRCFD_EINVAL as above. */
+int srcfd_fine_batch_get_fields_device(srcfd_fine_batch* b, int n, const int* cases, void* out_dev, int dtype, void* stream);
 /* Up to max_iterations more outer iterations of every case that is RUNNING; returns when none is, or when the budget is
  * spent.  Per case: iterations[n] (a frozen case keeps the count at which it froze), status[n] (SRCFD_CASE_*), rms[n][3] of
  * its last convergence check, history[n][history_len][3] = its rms at its iteration counts divisible by 100 that this call

@@ -118,6 +118,7 @@ _protos = {
     "srcfd_resampler_create": (C.c_int, [C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_p)]),
     "srcfd_resampler_destroy": (None, [_p]),
     "srcfd_resample_device": (C.c_int, [_p, _p, C.c_int, _p, _p]),
+    "srcfd_resample_device_f64": (C.c_int, [_p, _p, C.c_int, _p, _p]),
     "srcfd_predict_resampled": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_int, C.POINTER(C.c_int64)]),
     "srcfd_predict_into_solver_state": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(SolverBC), _p, C.c_int, C.POINTER(C.c_int64)]),
     "srcfd_trainer_create": (C.c_int, [_p, C.c_int, C.POINTER(_p)]),
@@ -142,6 +143,10 @@ _protos = {
     "srcfd_fine_batch_destroy": (None, [_p]),
     "srcfd_fine_batch_init": (C.c_int, [_p, _p]),
     "srcfd_fine_batch_init_from_prediction": (C.c_int, [_p, _p, _p, _p, C.c_int, C.POINTER(C.c_int), _p, _p, C.c_int, C.POINTER(C.c_int64)]),
+    "srcfd_fine_batch_init_from_fields_device": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.POINTER(C.c_int), _p]),
+    "srcfd_fine_batch_get_fields_device": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), _p, C.c_int, _p]),
+    "srcfd_fine_solver_init_from_fields_device": (C.c_int, [_p, _p, _p, C.c_int, _p]),
+    "srcfd_fine_solver_get_fields_device": (C.c_int, [_p, _p, C.c_int, _p]),
     "srcfd_fine_batch_run": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _p, _p, C.c_int]),
     "srcfd_fine_batch_get_state": (C.c_int, [_p, C.c_int, _p]),
     "srcfd_fine_batch_counters": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

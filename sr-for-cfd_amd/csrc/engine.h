@@ -184,4 +184,12 @@ int predict_solver_fields(Model* mm, srcfd_resampler* r, const float* x, int n_s
                           const std::string& who, const char* owner, int want_nx, int want_ny, int flags, int64_t* n_nonfinite,
                           const SolverFieldSink& write);
 
+// A resampler as the fine solver's hand-off from device fields sees it (resample.hip): input (in_h, in_w) -> output (out_h, out_w)
+// on `device`, and n planes of float or double resampled on `s` into the handle's own scratch, *out (n, out_h, out_w) float64.
+struct ResamplerGeometry {
+  int device, in_h, in_w, out_h, out_w;
+};
+ResamplerGeometry resampler_geometry(const srcfd_resampler* r);
+int resample_into_scratch(srcfd_resampler* r, const void* in_dev, bool f64, int n, hipStream_t s, const double** out);
+
 }  // namespace srcfd

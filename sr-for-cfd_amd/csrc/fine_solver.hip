@@ -32,6 +32,8 @@
 //
 // Warm starts.  srcfd_fine_batch_init_from_prediction super-resolves the coarse fields of any subset of the cases in one prediction
 // and handoff_kernel writes the result into those cases' Var; the other cases start from zero ("Warm starts").
+// srcfd_fine_batch_init_from_fields_device is the same hand-off fed from a caller's device fields, and
+// srcfd_fine_batch_get_fields_device (fields_kernel) returns them: DESIGN.md section 2c, "Device fields in and out".
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -397,6 +399,28 @@ __global__ void __launch_bounds__(NT) handoff_kernel(BDev bd, const T* __restric
   }
 }
 
+// Its mirror image, Var's interior back into fields:  field_k[j, i] = Var[k, 1+i, 1+j]  for plane s = 3 q + k of the output, the
+// case map.case_of[q]; float64 as it is, float32 rounded to nearest.  One workgroup per 32 x 32 tile of the nx x ny interior, through
+// LDS, so that the read runs along ny and the write along nx.  The ghost ring is not read.
+template <typename T>
+__global__ void __launch_bounds__(NT) fields_kernel(BDev bd, T* __restrict__ fields, WarmMap map) {
+  __shared__ double tile[HT][HT + 1];
+  const int s = blockIdx.z, k = s % 3;
+  T* f = fields + (size_t)s * bd.nx * bd.ny;
+  const double* V = bd.base + (size_t)map.case_of[s / 3] * bd.stride + (size_t)k * bd.sx;
+  const int i0 = blockIdx.x * HT, j0 = blockIdx.y * HT;
+  const int tx = threadIdx.x % HT, ty = threadIdx.x / HT;
+  for (int r = ty; r < HT; r += NT / HT) {
+    const int i = i0 + r, j = j0 + tx;
+    if (i < bd.nx && j < bd.ny) tile[r][tx] = V[(size_t)(i + 1) * bd.sy + (j + 1)];
+  }
+  __syncthreads();
+  for (int r = ty; r < HT; r += NT / HT) {
+    const int i = i0 + tx, j = j0 + r;
+    if (i < bd.nx && j < bd.ny) f[(size_t)j * bd.nx + i] = (T)tile[tx][r];
+  }
+}
+
 // ---------------------------------------------------------------- momentum: Jacobi sweep m of plane k, row blockIdx.x + 1 of case blockIdx.y
 template <bool QUICK>
 __global__ void __launch_bounds__(NT) momentum_sweep(BDev bd, int k, int m) {
@@ -711,6 +735,7 @@ struct FineBatch {
   ResRec* d_rec = nullptr;
   int mode = SRCFD_FINE_MODE_LAUNCHES;
   DevBuf<char> d_mem;
+  Event arrived, written;      // a caller's stream against this handle's: its work so far (join), the fields written for it (release)
   Stream stream;               // declared last: destroyed before the memory its work uses
   size_t state_bytes = 0;      // fields and status blocks: what init clears
   int count = 0;               // outer iterations of the live cases since the last init
@@ -783,6 +808,8 @@ struct FineBatch {
     HIPCHECK_F(hipMemset(mem, 0, s->state_bytes));
     HIPCHECK_F(hipMemcpy(mem + s->state_bytes, cp.data(), cp.size() * sizeof(CaseP), hipMemcpyHostToDevice));
     HIPCHECK_F(hipStreamCreateWithFlags(s->stream.out(), hipStreamNonBlocking));
+    HIPCHECK_F(hipEventCreateWithFlags(s->arrived.out(), hipEventDisableTiming));
+    HIPCHECK_F(hipEventCreateWithFlags(s->written.out(), hipEventDisableTiming));
     rc = s->host_mem.alloc((size_t)n_cases * (sizeof(Status) + sizeof(ResRec)));
     if (rc) return rc;
     std::memset(s->host_mem.get(), 0, s->host_mem.size());
@@ -865,28 +892,38 @@ struct FineBatch {
     return prime();
   }
 
+  // The case list of an entry point into map and listed[]: cases[0..count) must be distinct cases of this batch; nullptr is
+  // 0, 1, .. count - 1, and with every_case_if_null only the whole batch.  `what` names the count in the message.
+  int case_list(const std::string& who, const char* what, int count, const int* cases, bool every_case_if_null, WarmMap* map,
+                std::vector<char>* listed) const {
+    const bool must_be_all = !cases && every_case_if_null;
+    if (count < 1 || count > n || (must_be_all && count != n)) {
+      set_error(who + ": " + what + " " + std::to_string(count) + (must_be_all ? " without a case list is not the batch's " : " is outside 1..") + std::to_string(n));
+      return SRCFD_EINVAL;
+    }
+    for (int w = 0; w < count; ++w) {
+      const int c = cases ? cases[w] : w;
+      if (c < 0 || c >= n) { set_error(who + ": cases[" + std::to_string(w) + "] = " + std::to_string(c) + " is outside 0.." + std::to_string(n - 1)); return SRCFD_EINVAL; }
+      if ((*listed)[c]) { set_error(who + ": case " + std::to_string(c) + " is listed twice"); return SRCFD_EINVAL; }
+      (*listed)[c] = 1;
+      map->case_of[w] = (unsigned char)c;
+    }
+    return SRCFD_OK;
+  }
+
   // SR of n_warm coarse fields into the Var of the cases cases[0..n_warm) (nullptr: every case, in order), zero fields for the
   // others, then prime().  The prediction runs on the default stream, so this handle's stream is drained first and the
   // prediction drains its own before the memsets and prime() follow here.
   int init_from_prediction(const std::string& who, const char* owner, Model* mm, srcfd_resampler* r, const float* x, int n_warm,
                            const int* cases, const float* in_affine, const float* out_affine, int flags, int64_t* n_nonfinite) {
-    if (n_warm < 1 || n_warm > n || (!cases && n_warm != n)) {
-      set_error(who + ": n_warm " + std::to_string(n_warm) + (cases ? " is outside 1.." : " without a case list is not the batch's ") + std::to_string(n));
-      return SRCFD_EINVAL;
-    }
     WarmMap map{};
     std::vector<char> warm((size_t)n, 0);
-    for (int w = 0; w < n_warm; ++w) {
-      const int c = cases ? cases[w] : w;
-      if (c < 0 || c >= n) { set_error(who + ": cases[" + std::to_string(w) + "] = " + std::to_string(c) + " is outside 0.." + std::to_string(n - 1)); return SRCFD_EINVAL; }
-      if (warm[c]) { set_error(who + ": case " + std::to_string(c) + " is listed twice"); return SRCFD_EINVAL; }
-      warm[c] = 1;
-      map.case_of[w] = (unsigned char)c;
-    }
+    int rc = case_list(who, "n_warm", n_warm, cases, true, &map, &warm);
+    if (rc) return rc;
     if (mm->device != device) { set_error(who + ": model and " + owner + " are on different devices"); return SRCFD_EINVAL; }
     HIPCHECK_F(hipSetDevice(device));
     HIPCHECK_F(hipStreamSynchronize(stream));
-    int rc = predict_solver_fields(mm, r, x, 3 * n_warm, in_affine, out_affine, who, owner, g.nx, g.ny, flags, n_nonfinite,
+    rc = predict_solver_fields(mm, r, x, 3 * n_warm, in_affine, out_affine, who, owner, g.nx, g.ny, flags, n_nonfinite,
                                    [&](const void* fields, bool f64, int, int) -> int {
       const dim3 grid((unsigned)((g.nx + 2 + HT - 1) / HT), (unsigned)((g.ny + 2 + HT - 1) / HT), (unsigned)(3 * n_warm));
       if (f64) hipLaunchKernelGGL(handoff_kernel<double>, grid, dim3(NT), 0, nullptr, g, static_cast<const double*>(fields), map);
@@ -897,6 +934,80 @@ struct FineBatch {
     if (rc) return rc;
     if ((rc = reset(warm.data()))) return rc;
     return prime();
+  }
+
+  // This handle's stream waits for everything enqueued on the caller's so far (join); the caller's for this handle's (release).
+  int join(hipStream_t callers) {
+    HIPCHECK_F(hipEventRecord(arrived, callers));
+    HIPCHECK_F(hipStreamWaitEvent(stream, arrived, 0));
+    return SRCFD_OK;
+  }
+  int release(hipStream_t callers) {
+    HIPCHECK_F(hipEventRecord(written, stream));
+    HIPCHECK_F(hipStreamWaitEvent(callers, written, 0));
+    return SRCFD_OK;
+  }
+
+  // init_from_prediction without the network: the caller's device fields (3 n_warm planes of (h, w), float or double), through
+  // r when there is one, into the Var of the listed cases; zero fields for the others; prime().  All of it on this handle's
+  // stream, behind what the caller's stream holds at the call.  Everything is checked before anything is enqueued.
+  int init_from_fields(const std::string& who, const char* owner, srcfd_resampler* r, const void* fields, int dtype, int n_warm,
+                       const int* cases, hipStream_t callers) {
+    if (dtype != SRCFD_F32 && dtype != SRCFD_F64) {
+      set_error(who + ": dtype " + std::to_string(dtype) + " is neither SRCFD_F32 nor SRCFD_F64");
+      return SRCFD_EINVAL;
+    }
+    WarmMap map{};
+    std::vector<char> warm((size_t)n, 0);
+    int rc = case_list(who, "n_warm", n_warm, cases, false, &map, &warm);
+    if (rc) return rc;
+    if (r) {
+      const ResamplerGeometry q = resampler_geometry(r);
+      if (q.device != device) { set_error(who + ": resampler and " + owner + " are on different devices"); return SRCFD_EINVAL; }
+      if (q.out_w != g.nx || q.out_h != g.ny) {
+        set_error(who + ": the resampler's output mesh (" + std::to_string(q.out_w) + " x " + std::to_string(q.out_h) + ") is not the " + owner + "'s (" +
+                  std::to_string(g.nx) + " x " + std::to_string(g.ny) + ")");
+        return SRCFD_EINVAL;
+      }
+    }
+    const bool f64 = dtype == SRCFD_F64;
+    HIPCHECK_F(hipSetDevice(device));
+    if ((rc = join(callers))) return rc;
+    if ((rc = reset(warm.data()))) return rc;
+    const bool from_scratch = r != nullptr;
+    if (r) {
+      const double* resampled = nullptr;
+      if ((rc = resample_into_scratch(r, fields, f64, 3 * n_warm, stream, &resampled))) return rc;
+      fields = resampled;
+    }
+    const dim3 grid((unsigned)((g.nx + 2 + HT - 1) / HT), (unsigned)((g.ny + 2 + HT - 1) / HT), (unsigned)(3 * n_warm));
+    if (f64 || from_scratch) hipLaunchKernelGGL(handoff_kernel<double>, grid, dim3(NT), 0, stream, g, static_cast<const double*>(fields), map);
+    else hipLaunchKernelGGL(handoff_kernel<float>, grid, dim3(NT), 0, stream, g, static_cast<const float*>(fields), map);
+    if ((rc = launched())) return rc;
+    return prime();
+  }
+
+  // The interiors of the listed cases' Var as fields, (3 count, ny, nx) float or double on the device, behind what the caller's
+  // stream holds at the call; complete at return, and the caller's stream waits for it too.
+  int get_fields(const std::string& who, int count, const int* cases, void* out, int dtype, hipStream_t callers) {
+    if (dtype != SRCFD_F32 && dtype != SRCFD_F64) {
+      set_error(who + ": dtype " + std::to_string(dtype) + " is neither SRCFD_F32 nor SRCFD_F64");
+      return SRCFD_EINVAL;
+    }
+    WarmMap map{};
+    std::vector<char> listed((size_t)n, 0);
+    int rc = case_list(who, "n", count, cases, true, &map, &listed);
+    if (rc) return rc;
+    HIPCHECK_F(hipSetDevice(device));
+    if ((rc = join(callers))) return rc;
+    const dim3 grid((unsigned)((g.nx + HT - 1) / HT), (unsigned)((g.ny + HT - 1) / HT), (unsigned)(3 * count));
+    if (dtype == SRCFD_F64) hipLaunchKernelGGL(fields_kernel<double>, grid, dim3(NT), 0, stream, g, static_cast<double*>(out), map);
+    else hipLaunchKernelGGL(fields_kernel<float>, grid, dim3(NT), 0, stream, g, static_cast<float*>(out), map);
+    if ((rc = launched())) return rc;
+    if ((rc = release(callers))) return rc;
+    ++n_sync;
+    HIPCHECK_F(hipStreamSynchronize(stream));
+    return SRCFD_OK;
   }
 
   // One inner solve of every live case: chunks of sweep launches until each has stopped or the cap is reached.
@@ -1098,6 +1209,22 @@ int srcfd_fine_solver_init_from_prediction(srcfd_fine_solver* s, srcfd_model* m,
   });
 }
 
+int srcfd_fine_solver_init_from_fields_device(srcfd_fine_solver* s, srcfd_resampler* r, const void* fields_dev, int dtype, void* stream) {
+  return srcfd::abi_guard("srcfd_fine_solver_init_from_fields_device", [&]() -> int {
+    if (!s || !fields_dev) { set_error("srcfd_fine_solver_init_from_fields_device: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(s)->init_from_fields("srcfd_fine_solver_init_from_fields_device", "solver", r, fields_dev, dtype, 1, nullptr,
+                                         reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
+int srcfd_fine_solver_get_fields_device(srcfd_fine_solver* s, void* out_dev, int dtype, void* stream) {
+  return srcfd::abi_guard("srcfd_fine_solver_get_fields_device", [&]() -> int {
+    if (!s || !out_dev) { set_error("srcfd_fine_solver_get_fields_device: bad arguments"); return SRCFD_EINVAL; }
+    if (!batch_of(s)->primed) { set_error("srcfd_fine_solver_get_fields_device: call srcfd_fine_solver_init first"); return SRCFD_EINVAL; }
+    return batch_of(s)->get_fields("srcfd_fine_solver_get_fields_device", 1, nullptr, out_dev, dtype, reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
 int srcfd_fine_solver_run(srcfd_fine_solver* s, int max_iterations, int* iterations, double rms[3], double* history, int history_len) {
   return srcfd::abi_guard("srcfd_fine_solver_run", [&]() -> int {
     if (!s || max_iterations < 0 || history_len < 0 || (history_len > 0 && !history)) {
@@ -1204,6 +1331,23 @@ int srcfd_fine_batch_init_from_prediction(srcfd_fine_batch* b, srcfd_model* m, s
     if (!b || !m || !x) { set_error("srcfd_fine_batch_init_from_prediction: bad arguments"); return SRCFD_EINVAL; }
     return batch_of(b)->init_from_prediction("srcfd_fine_batch_init_from_prediction", "batch", reinterpret_cast<srcfd::Model*>(m), r, x, n_warm,
                                              cases, in_affine, out_affine, flags, n_nonfinite);
+  });
+}
+
+int srcfd_fine_batch_init_from_fields_device(srcfd_fine_batch* b, srcfd_resampler* r, const void* fields_dev, int dtype, int n_warm,
+                                             const int* cases, void* stream) {
+  return srcfd::abi_guard("srcfd_fine_batch_init_from_fields_device", [&]() -> int {
+    if (!b || !fields_dev) { set_error("srcfd_fine_batch_init_from_fields_device: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(b)->init_from_fields("srcfd_fine_batch_init_from_fields_device", "batch", r, fields_dev, dtype, n_warm, cases,
+                                         reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
+int srcfd_fine_batch_get_fields_device(srcfd_fine_batch* b, int n, const int* cases, void* out_dev, int dtype, void* stream) {
+  return srcfd::abi_guard("srcfd_fine_batch_get_fields_device", [&]() -> int {
+    if (!b || !out_dev) { set_error("srcfd_fine_batch_get_fields_device: bad arguments"); return SRCFD_EINVAL; }
+    if (!batch_of(b)->primed) { set_error("srcfd_fine_batch_get_fields_device: call srcfd_fine_batch_init first"); return SRCFD_EINVAL; }
+    return batch_of(b)->get_fields("srcfd_fine_batch_get_fields_device", n, cases, out_dev, dtype, reinterpret_cast<hipStream_t>(stream));
   });
 }
 

@@ -114,7 +114,8 @@ __global__ void __launch_bounds__(64) gemm_f64(const TA* __restrict__ A, int64_t
       }
 }
 
-__global__ void __launch_bounds__(256) widen_f64(const float* __restrict__ x, double* __restrict__ y, int64_t n) {
+template <typename T>
+__global__ void __launch_bounds__(256) widen_f64(const T* __restrict__ x, double* __restrict__ y, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) y[i] = (double)x[i];
 }
@@ -138,23 +139,25 @@ struct Resampler {
     return SRCFD_OK;
   }
   // out[z] = Ry * (in[z] * Rx^T) on `s`.  A factor that is the identity (the BFS case lx = max(lx, ly): the square and
-  // the rectangle share their x nodes) is skipped: one GEMM instead of two.
+  // the rectangle share their x nodes) is skipped: one GEMM instead of two.  T: the input's type, float (the network's output)
+  // or double (a solver's fields); the products and their order do not depend on it.
   bool rx_identity = false, ry_identity = false;
-  int run(const float* in_dev, int n, double* out_dev, hipStream_t s) {
+  template <typename T>
+  int run(const T* in_dev, int n, double* out_dev, hipStream_t s) {
     int rc = reserve(n);
     if (rc) return rc;
     const double *d_Ry = this->d_Ry.get(), *d_RxT = this->d_RxT.get();
     double* d_T = this->d_T.get();
     if (rx_identity && ry_identity) {
-      hipLaunchKernelGGL(widen_f64, dim3((unsigned)(((int64_t)n * H * W + 255) / 256)), dim3(256), 0, s, in_dev, out_dev, (int64_t)n * H * W);
+      hipLaunchKernelGGL(widen_f64<T>, dim3((unsigned)(((int64_t)n * H * W + 255) / 256)), dim3(256), 0, s, in_dev, out_dev, (int64_t)n * H * W);
     } else if (rx_identity) {
-      hipLaunchKernelGGL((gemm_f64<double, float>), dim3((W + 31) / 32, (OH + 31) / 32, n), dim3(64), 0, s, d_Ry, (int64_t)0, in_dev, (int64_t)H * W, out_dev,
+      hipLaunchKernelGGL((gemm_f64<double, T>), dim3((W + 31) / 32, (OH + 31) / 32, n), dim3(64), 0, s, d_Ry, (int64_t)0, in_dev, (int64_t)H * W, out_dev,
                          (int64_t)OH * W, OH, W, H);
     } else if (ry_identity) {
-      hipLaunchKernelGGL((gemm_f64<float, double>), dim3((OW + 31) / 32, (H + 31) / 32, n), dim3(64), 0, s, in_dev, (int64_t)H * W, d_RxT, (int64_t)0, out_dev,
+      hipLaunchKernelGGL((gemm_f64<T, double>), dim3((OW + 31) / 32, (H + 31) / 32, n), dim3(64), 0, s, in_dev, (int64_t)H * W, d_RxT, (int64_t)0, out_dev,
                          (int64_t)H * OW, H, OW, W);
     } else {
-      hipLaunchKernelGGL((gemm_f64<float, double>), dim3((OW + 31) / 32, (H + 31) / 32, n), dim3(64), 0, s, in_dev, (int64_t)H * W, d_RxT, (int64_t)0, d_T,
+      hipLaunchKernelGGL((gemm_f64<T, double>), dim3((OW + 31) / 32, (H + 31) / 32, n), dim3(64), 0, s, in_dev, (int64_t)H * W, d_RxT, (int64_t)0, d_T,
                          (int64_t)H * OW, H, OW, W);
       hipLaunchKernelGGL((gemm_f64<double, double>), dim3((OW + 31) / 32, (OH + 31) / 32, n), dim3(64), 0, s, d_Ry, (int64_t)0, d_T, (int64_t)H * OW, out_dev,
                          (int64_t)OH * OW, OH, OW, H);
@@ -163,6 +166,22 @@ struct Resampler {
     return SRCFD_OK;
   }
 };
+
+// What the fine solver's hand-off from device fields needs of a resampler (fine_solver.hip, init_from_fields): its geometry, and
+// the n planes at in_dev, float or double, resampled into the handle's own d_out on `s` -- the scratch of predict_solver_fields.
+ResamplerGeometry resampler_geometry(const srcfd_resampler* r) {
+  const Resampler* rr = reinterpret_cast<const Resampler*>(r);
+  return ResamplerGeometry{rr->device, rr->H, rr->W, rr->OH, rr->OW};
+}
+int resample_into_scratch(srcfd_resampler* r, const void* in_dev, bool f64, int n, hipStream_t s, const double** out) {
+  Resampler* rr = reinterpret_cast<Resampler*>(r);
+  int rc = rr->reserve(n);   // before d_out is named: growing it moves it
+  if (rc) return rc;
+  rc = f64 ? rr->run(static_cast<const double*>(in_dev), n, rr->d_out.get(), s) : rr->run(static_cast<const float*>(in_dev), n, rr->d_out.get(), s);
+  if (rc) return rc;
+  *out = rr->d_out.get();
+  return SRCFD_OK;
+}
 
 // ---------------------------------------------------------------------------
 // Hand-off into the solver state (PyCFD_ML_accelerated.py:936-943, bfs_ml_accelerated.py:1211-1218):
@@ -416,6 +435,16 @@ int srcfd_resample_device(srcfd_resampler* r, const float* in_dev, int n, double
     Resampler* rr = reinterpret_cast<Resampler*>(r);
     HIPCHECK(hipSetDevice(rr->device));
     return rr->run(in_dev, n, out_dev, reinterpret_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int srcfd_resample_device_f64(srcfd_resampler* r, const double* in_dev, int n, double* out_dev, void* stream) {
+  return srcfd::abi_guard("srcfd_resample_device_f64", [&]() -> int {
+    if (!r || n < 0 || (n > 0 && (!in_dev || !out_dev))) { set_error("srcfd_resample_device_f64: bad arguments"); return SRCFD_EINVAL; }
+    if (n == 0) return SRCFD_OK;
+    Resampler* rr = reinterpret_cast<Resampler*>(r);
+    HIPCHECK(hipSetDevice(rr->device));
+    return rr->run(in_dev, n, out_dev, reinterpret_cast<hipStream_t>(stream));
   });
 }
 

@@ -14,6 +14,10 @@ is a batch of one), each with the bits of a `FineSolver` of its own; `run_normal
 `FineSolverBatch.init_from_prediction` warm-starts any subset of a batch from one SR call (srcfd_fine_batch_init_from_prediction);
 `run_ml_accelerated_fine_simulations` / `run_bfs_ml_accelerated_fine_simulations` are the warm-started drop-ins for a sweep, and
 `compare_ml_and_normal_simulations` / `compare_bfs_ml_and_normal_simulations` run each Reynolds number warm and cold in one batch.
+`init_from_fields` / `fields_device` (both classes) start cases from fields that are on the device already and return them there
+(srcfd_fine_batch_init_from_fields_device / _get_fields_device); on them, `run_interpolated_fine_simulations` is the control arm of a
+warm-start study, `compare_warm_starts` runs the arms "ml", "interp" and "zero" in one batch, and `run_nested_simulations` is grid
+sequencing (`run_bfs_interpolated_fine_simulations`, `compare_bfs_warm_starts` for the step).
 
 `resident=` (False, True or "auto") on the solver classes and the sweep functions selects the resident mode for meshes of at most
 64 x 64 cells (`resident_supported`): one workgroup per case runs many outer iterations per launch, with the same bits.
@@ -88,12 +92,83 @@ def _resident_mode(resident, nx: int, ny: int) -> int:
     raise ValueError(f"resident must be False, True or 'auto', not {resident!r}")
 
 
+def _stream_handle(stream, device: int):
+    """The hipStream_t of `stream` -- a torch stream, a raw handle, or None for torch's current stream on `device`."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(torch.device("cuda", device))
+    return C.c_void_p(getattr(stream, "cuda_stream", stream))
+
+
+def _case_list(cases, n_cases: int):
+    """`cases` as a list of distinct ints (None stays None); ValueError before anything reaches the library."""
+    if cases is None:
+        return None
+    case_list = [int(c) for c in cases]
+    if not 1 <= len(case_list) <= n_cases:
+        raise ValueError(f"cases must name between 1 and {n_cases} cases, not {len(case_list)}")
+    if len(set(case_list)) != len(case_list):
+        raise ValueError(f"cases must not repeat a case: {case_list}")
+    return case_list
+
+
+def _fields_in(fields, n_cases: int, cases, hw, device: int):
+    """The `fields` of an init_from_fields call, checked: (tensor, pointer, srcfd dtype, n_warm, ctypes case list).  A torch
+    tensor must be a contiguous float32 or float64 CUDA tensor (3 * n_warm, h, w) on `device` (_lib.device_ptr); a numpy array of
+    that shape is uploaded once, float32 as it is and anything else as float64.  Every refusal is a ValueError raised before the
+    library is called; the returned tensor keeps the memory alive for the call."""
+    import torch
+    case_list = _case_list(cases, n_cases)
+    shape = tuple(int(d) for d in getattr(fields, "shape", ()))
+    if len(shape) != 3:
+        raise ValueError(f"fields must have shape (3 * n_warm, {hw[0]}, {hw[1]}): u, v, p of each field, not {shape}")
+    n_warm = len(case_list) if case_list is not None else shape[0] // 3
+    if not 1 <= n_warm <= n_cases:
+        raise ValueError(f"fields has shape {shape}: its first dimension must be 3 * n_warm for between 1 and {n_cases} warm cases")
+    if shape[0] != 3 * n_warm:
+        raise ValueError(f"fields has shape {shape}: its first dimension must be 3 * n_warm = {3 * n_warm} (u, v, p of each of "
+                         f"{n_warm} field(s))")
+    if isinstance(fields, np.ndarray):
+        if shape[1:] != tuple(hw):
+            raise ValueError(f"fields has per-field shape {shape[1:]}, expected {tuple(hw)}")
+        host = np.ascontiguousarray(fields, dtype=np.float32 if fields.dtype == np.float32 else np.float64)
+        fields = torch.from_numpy(host).to(torch.device("cuda", device))
+    ptr = L.device_ptr(fields, "fields", (torch.float32, torch.float64), (3 * n_warm,) + tuple(hw), device, exact=True)
+    idx = None if case_list is None else (C.c_int * n_warm)(*case_list)
+    return fields, ptr, L.F32 if fields.dtype == torch.float32 else L.F64, n_warm, idx
+
+
+def _fields_out(n: int, hw, dtype, out, device: int):
+    """The output of a fields_device call: (tensor, pointer, srcfd dtype).  dtype: torch.float64 (None) or torch.float32; `out`,
+    when given, is a contiguous CUDA tensor (3 * n, ny, nx) of that dtype on `device`, otherwise one is allocated."""
+    import torch
+    dtype = torch.float64 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float64 or torch.float32, not {dtype}")
+    shape = (3 * n,) + tuple(hw)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", device))
+    return out, L.device_ptr(out, "out", dtype, shape, device, exact=True), L.F32 if dtype == torch.float32 else L.F64
+
+
+def _resampler_fits(resampler, mesh, device: int):
+    """(h, w) of the fields a mesh takes through `resampler` (None: the mesh itself); ValueError when it does not end at the mesh."""
+    if resampler is None:
+        return (mesh.ny, mesh.nx)
+    if (resampler.out_h, resampler.out_w) != (mesh.ny, mesh.nx):
+        raise ValueError(f"resampler ends at ({resampler.out_h}, {resampler.out_w}), the mesh takes fields of ({mesh.ny}, {mesh.nx})")
+    if int(resampler.device) != int(device):
+        raise ValueError(f"resampler is on device cuda:{resampler.device}, the solver is on cuda:{device}")
+    return (resampler.in_h, resampler.in_w)
+
+
 class FineSolver:
     """Device-resident float64 solver state for one problem (srcfd_fine_solver_*).  Starts from `_initialize_fields`.
     `resident`: see `set_resident`."""
 
     def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0, resident=False):
         self.problem = pb
+        self.device = int(device)
         self.max_iterations = int(max_iterations)
         self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
         self.residual_history = {"u": [], "v": [], "p": []}
@@ -166,6 +241,21 @@ class FineSolver:
         self._reset()
         return int(bad.value)
 
+    def init_from_fields(self, fields, resampler=None, stream=None) -> None:
+        """`FineSolverBatch.init_from_fields` for the one case: `fields` (3, h, w), u, v, p
+        (srcfd_fine_solver_init_from_fields_device)."""
+        hw = _resampler_fits(resampler, self.mesh, self.device)
+        fields, ptr, code, _, _ = _fields_in(fields, 1, None, hw, self.device)
+        L.check(L.lib.srcfd_fine_solver_init_from_fields_device(self._h, resampler._h if resampler is not None else None, ptr, code,
+                                                                _stream_handle(stream, self.device)))
+        self._reset()
+
+    def fields_device(self, dtype=None, out=None, stream=None):
+        """`FineSolverBatch.fields_device` for the one case: a (3, ny, nx) CUDA tensor (srcfd_fine_solver_get_fields_device)."""
+        out, ptr, code = _fields_out(1, (self.mesh.ny, self.mesh.nx), dtype, out, self.device)
+        L.check(L.lib.srcfd_fine_solver_get_fields_device(self._h, ptr, code, _stream_handle(stream, self.device)))
+        return out
+
     def run(self, n: int) -> int:
         """Up to n more outer iterations; returns the outer iterations since init."""
         it = C.c_int(0)
@@ -218,6 +308,7 @@ class FineSolverBatch:
     def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0, resident=False):
         self.problems = list(problems)
         self.n_cases = len(self.problems)
+        self.device = int(device)
         self.max_iterations = int(max_iterations)
         arr = (L.CoarseProblem * max(self.n_cases, 1))(*self.problems)
         self._h = C.c_void_p()
@@ -296,6 +387,32 @@ class FineSolverBatch:
                                                             C.byref(bad)))
         self._reset()
         return int(bad.value)
+
+    def init_from_fields(self, fields, cases: Optional[Sequence[int]] = None, resampler=None, stream=None) -> None:
+        """Starts the cases `cases` (None: case i from field i) from fields that are on the device already, every other case
+        from zero fields, and every case again from iteration 0 (srcfd_fine_batch_init_from_fields_device).  `fields`:
+        (3 * n_warm, h, w), u, v, p of each field in the layout of the SR prediction and the coarse-field dicts (field[j, i] is
+        cell (i, j)); a contiguous float32 or float64 CUDA tensor, or a numpy array, which is uploaded once.  (h, w) is the
+        mesh's (ny, nx), or with `resampler` its input, and the fields go through it in float64.  Values are taken as they are:
+        there is no NaN guard.  `stream`: the torch stream the fields were produced on (None: the current one); the solver
+        waits for it on the device, so the caller does not synchronise first, and the call returns when the state is primed."""
+        hw = _resampler_fits(resampler, self.mesh, self.device)
+        fields, ptr, code, n_warm, idx = _fields_in(fields, self.n_cases, cases, hw, self.device)
+        L.check(L.lib.srcfd_fine_batch_init_from_fields_device(self._h, resampler._h if resampler is not None else None, ptr, code,
+                                                               n_warm, idx, _stream_handle(stream, self.device)))
+        self._reset()
+
+    def fields_device(self, cases: Optional[Sequence[int]] = None, dtype=None, out=None, stream=None):
+        """The fields of the cases `cases` (None: all, in order) as a (3 * n, ny, nx) CUDA tensor, u, v, p of each: what
+        `fields(i)` returns, without a host copy (srcfd_fine_batch_get_fields_device).  dtype: torch.float64 (the default, an exact
+        copy) or torch.float32 (rounded to nearest); `out`: a tensor to write into.  Complete at return, and `stream` (None: the
+        current torch stream) waits for it as well."""
+        case_list = _case_list(cases, self.n_cases)
+        n = self.n_cases if case_list is None else len(case_list)
+        out, ptr, code = _fields_out(n, (self.mesh.ny, self.mesh.nx), dtype, out, self.device)
+        idx = None if case_list is None else (C.c_int * n)(*case_list)
+        L.check(L.lib.srcfd_fine_batch_get_fields_device(self._h, n, idx, ptr, code, _stream_handle(stream, self.device)))
+        return out
 
     def _reset(self) -> None:
         self.residual_history: List[Dict[str, List[float]]] = [{"u": [], "v": [], "p": []} for _ in range(self.n_cases)]
@@ -505,14 +622,20 @@ def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch
         pipeline._warn_nonfinite(b.init_from_prediction(model, x, ain, aout, back, cases=cases))
 
     out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start, resident=resident)
-    if output_name is not None:
-        for i, (fields, _, _) in enumerate(out):
-            name = f"{output_name}_Re{problems[i].reynolds:g}{suffix_of(i)}"
-            d = os.path.dirname(name)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            save_coarse_fields(f"{name}.h5", fields, problems[i].reynolds, problems[i].lx, problems[i].ly, bfs_step_height=bfs_step_height)
+    _save_sweep(out, problems, output_name, suffix_of, bfs_step_height)
     return out
+
+
+def _save_sweep(out, problems, output_name, suffix_of, bfs_step_height=None):
+    """Each case's fields to `{output_name}_Re{Re}{suffix_of(i)}.h5` (output_name None: nothing is written)."""
+    if output_name is None:
+        return
+    for i, (fields, _, _) in enumerate(out):
+        name = f"{output_name}_Re{problems[i].reynolds:g}{suffix_of(i)}"
+        d = os.path.dirname(name)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        save_coarse_fields(f"{name}.h5", fields, problems[i].reynolds, problems[i].lx, problems[i].ly, bfs_step_height=bfs_step_height)
 
 
 def _paired(out, reynolds):
@@ -699,3 +822,244 @@ def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str,
                      stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 2, resident)
     return _paired(out, list(reynolds))
+
+
+# ---------------------------------------------------------------------------------------------- starts from device fields
+def interpolation_matrices(lr_h: int, lr_w: int, nx: int, ny: int, lx: float = 1.0, ly: float = 1.0):
+    """(Ry [ny][lr_h], Rx [nx][lr_w]) of the plainly interpolated start: fine = Ry @ coarse @ Rx.T is the interpolating bicubic
+    spline of a (lr_h, lr_w) field on the (ny, nx) mesh, with the reference's own node convention, linspace(0, L, n) on both
+    sides (resample.interp_matrix)."""
+    from . import resample as rs
+    return rs.interp_matrix(int(lr_h), float(ly), int(ny), float(ly)), rs.interp_matrix(int(lr_w), float(lx), int(nx), float(lx))
+
+
+def interpolation_resampler(lr_h: int, lr_w: int, nx: int, ny: int, lx: float = 1.0, ly: float = 1.0, device: int = 0):
+    """`interpolation_matrices` as a device `Resampler`."""
+    from . import resample as rs
+    Ry, Rx = interpolation_matrices(lr_h, lr_w, nx, ny, lx, ly)
+    return rs.Resampler(Ry, Rx, int(device))
+
+
+def _stack_fields(coarse_fields_list) -> np.ndarray:
+    """(3 * n, h, w) float64: u, v, p of each coarse-field dict."""
+    return np.stack([np.asarray(cf[c], dtype=np.float64) for cf in coarse_fields_list for c in COMPONENTS])
+
+
+def _interpolated_sweep(coarse_fields_list, reynolds, problems, lr_dim, max_iterations, output_name, max_batch, device, resident,
+                        bfs_step_height=None):
+    coarse_fields_list = list(coarse_fields_list)
+    if len(coarse_fields_list) != len(reynolds):
+        raise ValueError(f"coarse_fields_list must hold one set of coarse fields per Reynolds number ({len(reynolds)}), not {len(coarse_fields_list)}")
+    pb = problems[0]
+    interp = interpolation_resampler(lr_dim, lr_dim, pb.nx, pb.ny, pb.lx, pb.ly, device)
+    try:
+        warm_start = lambda b, a: b.init_from_fields(_stack_fields(coarse_fields_list[a:a + b.n_cases]), resampler=interp)
+        out = _solve_in_batches(problems, max_iterations, max_batch, device, warm_start, resident=resident)
+    finally:
+        interp.close()
+    _save_sweep(out, problems, output_name, lambda i: "_interpolated", bfs_step_height)
+    return out
+
+
+def run_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                      lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
+                                      convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                      output_name: Optional[str] = None, bc=None, resident=False, max_batch: int = 8,
+                                      device: int = 0) -> list:
+    """The control arm of a warm-start study: `run_ml_accelerated_fine_simulations` with the network replaced by plain bicubic
+    interpolation of each coarse field to the mesh (`interpolation_resampler`), on the device.  The arguments are those of that
+    function without the model and statistics files and the network's precision; the return value is the same list of (fields,
+    iterations, status).  `output_name`: each case's fields go to `{output_name}_Re{Re}_interpolated.h5`."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs)]
+    return _interpolated_sweep(coarse_fields_list, reynolds, pbs, lr_dim, max_iterations_fine, output_name, max_batch, device, resident)
+
+
+def run_bfs_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                                          lr_dim: int = 10, dt: float = 0.002, scheme: str = "UPWIND",
+                                          convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                                          output_name: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0,
+                                          Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
+                                          relaxation_factors: Optional[Dict[str, float]] = None, resident=False, max_batch: int = 8,
+                                          device: int = 0) -> list:
+    """`run_interpolated_fine_simulations` for the backward-facing step: `run_bfs_ml_accelerated_fine_simulations` without the
+    model, its files and its input options."""
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
+           for Re, b in zip(reynolds, bcs)]
+    return _interpolated_sweep(coarse_fields_list, reynolds, pbs, lr_dim, max_iterations_fine, output_name, max_batch, device, resident,
+                               bfs_step_height=step_height)
+
+
+ARMS = ("ml", "interp", "zero")
+
+
+def _warm_start_arms(coarse_fields_list, reynolds, problem_of, arms, lr_dim, files, default_files, prepare_of, max_iterations,
+                     output_name, max_batch, device, resident, bfs_step_height=None):
+    """The solve behind `compare_warm_starts` and its BFS form.  problem_of(i): the problem of Reynolds number i; prepare_of(files,
+    device): pipeline._prepare_batch for a list of coarse fields."""
+    from . import pipeline
+    reynolds, coarse_fields_list, arms = list(reynolds), list(coarse_fields_list), tuple(arms)
+    if not arms or len(set(arms)) != len(arms) or any(a not in ARMS for a in arms):
+        raise ValueError(f"arms must be distinct names out of {ARMS}, not {arms}")
+    if len(coarse_fields_list) != len(reynolds):
+        raise ValueError(f"coarse_fields_list must hold one set of coarse fields per Reynolds number ({len(reynolds)}), not {len(coarse_fields_list)}")
+    if "ml" in arms:
+        if all(f is None for f in files):
+            arms = tuple(a for a in arms if a != "ml")       # no model files: the arms that need none
+            if not arms:
+                raise ValueError("the 'ml' arm needs stats_file, encoder_file and decoder_file")
+        else:
+            files = tuple(f or d for f, d in zip(files, default_files))
+            _model_files(*files)
+    every = len(arms)
+    if max_batch < every:
+        raise ValueError(f"max_batch must be at least {every}, the number of arms")
+    problems = [problem_of(i) for i in range(len(reynolds)) for _ in arms]
+    prepare = model = None
+    if "ml" in arms:
+        prepare = prepare_of(files, device)
+        model = prepare([])[0]   # the handle is cached: this picks the device before any solver exists
+        device = model.device
+    device = 0 if device is None else int(device)
+    pb = problems[0] if problems else None
+    interp = interpolation_resampler(lr_dim, lr_dim, pb.nx, pb.ny, pb.lx, pb.ly, device) if "interp" in arms and pb is not None else None
+
+    def warm_start(b, a):
+        import torch
+        first, n_re = a // every, b.n_cases // every
+        coarse = coarse_fields_list[first:first + n_re]
+        parts, cases = [], []
+        if "ml" in arms:
+            # the prediction of these n_re fields goes into the state exactly as the ML sweep puts it there; its float64 copy then
+            # joins the other arms' fields, because every init call starts the cases it does not name from zero
+            ml_cases = [every * i + arms.index("ml") for i in range(n_re)]
+            _, x, ain, aout, back = prepare(coarse)
+            pipeline._warn_nonfinite(b.init_from_prediction(model, x, ain, aout, back, cases=ml_cases))
+            parts.append(b.fields_device(cases=ml_cases))
+            cases += ml_cases
+        if "interp" in arms:
+            lr = torch.from_numpy(_stack_fields(coarse)).to(torch.device("cuda", device))
+            parts.append(interp.apply_device_f64(lr))
+            cases += [every * i + arms.index("interp") for i in range(n_re)]
+        if cases:
+            b.init_from_fields(parts[0] if len(parts) == 1 else torch.cat(parts), cases=cases)
+
+    try:
+        out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, device, warm_start, resident=resident)
+    finally:
+        if interp is not None:
+            interp.close()
+    _save_sweep(out, problems, output_name, lambda i: f"_{arms[i % every]}", bfs_step_height)
+    res = []
+    for i, Re in enumerate(reynolds):
+        r = {"Re": Re}
+        for k, arm in enumerate(arms):
+            fields, it, st = out[every * i + k]
+            r[arm] = {"iterations": it, "status": st, "fields": fields}
+        r["iterations_saved"] = {arm: r["zero"]["iterations"] - r[arm]["iterations"] for arm in arms if arm != "zero"} if "zero" in arms else {}
+        res.append(r)
+    return res
+
+
+def compare_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                        arms: Sequence[str] = ARMS, lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
+                        convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                        output_name: Optional[str] = None, stats_file: Optional[str] = None, encoder_file: Optional[str] = None,
+                        decoder_file: Optional[str] = None, bc=None, precision: Optional[str] = None, resident=False,
+                        max_batch: int = 8, device: Optional[int] = None) -> list:
+    """`compare_ml_and_normal_simulations` with the control arm: every Reynolds number goes into the batch once per arm -- "ml"
+    warm-started from the network, "interp" from the plainly interpolated coarse field (`run_interpolated_fine_simulations`),
+    "zero" from zero fields -- under the same iteration cap; `max_batch` is rounded down to a multiple of the number of arms.
+    Without any of stats_file, encoder_file and decoder_file the "ml" arm is left out and the others run; with some of them
+    given, the missing ones take the defaults of `run_ml_accelerated_fine_simulations` and all three must exist.
+    Returns one dict per Reynolds number: Re, one {"iterations", "status", "fields"} per arm under the arm's name, and
+    iterations_saved[arm] = zero's iterations - the arm's, for every other arm when "zero" runs.  Each arm has the bits of its
+    own sweep function; the "ml" arm's prediction holds one field per Reynolds number of the batch (see
+    FineSolverBatch.init_from_prediction).  `output_name`: fields go to `{output_name}_Re{Re}_{arm}.h5`."""
+    from . import pipeline
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    defaults = (f"standardization_stats_{lr_dim}to{nx}.txt", f"vanilla_encoder{lr_dim}_to_{nx}.h5", f"vanilla_decoder{nx}_from_{lr_dim}.h5")
+    prepare_of = lambda files, dev: (lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, files[0], files[1], files[2], False, 1.0, 1.0,
+                                                                           False, 0.3, precision, dev))
+    return _warm_start_arms(coarse_fields_list, reynolds,
+                            lambda i: problem(reynolds[i], nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bcs[i]),
+                            arms, lr_dim, (stats_file, encoder_file, decoder_file), defaults, prepare_of, max_iterations_fine, output_name,
+                            max_batch, device, resident)
+
+
+def compare_bfs_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
+                            arms: Sequence[str] = ARMS, lr_dim: int = 10, dt: float = 0.002, scheme: str = "UPWIND",
+                            convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
+                            output_name: Optional[str] = None, stats_file: Optional[str] = None, encoder_file: Optional[str] = None,
+                            decoder_file: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0,
+                            lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None,
+                            use_aspect_ratio_correction: bool = False, use_adaptive_normalization: bool = True,
+                            blend_factor: float = 0.3, precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                            device: Optional[int] = None) -> list:
+    """`compare_warm_starts` for the backward-facing step (the arms of `run_bfs_ml_accelerated_fine_simulations`,
+    `run_bfs_interpolated_fine_simulations` and `run_bfs_normal_simulations`)."""
+    from . import pipeline
+    reynolds = list(reynolds)
+    bcs = _per_case(bc, len(reynolds))
+    tail = "_swish_trained_upto_700_multiBC"
+    defaults = (f"standardization_stats_{lr_dim}to{nx}{tail}.txt", f"vanilla_encoder{lr_dim}_to_{nx}{tail}.h5",
+                f"vanilla_decoder{nx}_from_{lr_dim}{tail}.h5")
+    prepare_of = lambda files, dev: (lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, files[0], files[1], files[2],
+                                                                           use_aspect_ratio_correction, lx, ly, use_adaptive_normalization,
+                                                                           blend_factor, precision, dev))
+    return _warm_start_arms(coarse_fields_list, reynolds,
+                            lambda i: _bfs_problem(reynolds[i], nx, ny, dt, scheme, convergence_criteria, bcs[i], step_height, h, Ub, lx, ly,
+                                                   relaxation_factors),
+                            arms, lr_dim, (stats_file, encoder_file, decoder_file), defaults, prepare_of, max_iterations_fine, output_name,
+                            max_batch, device, resident, bfs_step_height=step_height)
+
+
+def run_nested_simulations(reynolds: Sequence[float], meshes: Sequence, dt: float = 0.001, scheme: str = "QUICK",
+                           convergence_criteria: Optional[Dict[str, float]] = None, max_iterations=100000, bc=None, max_batch: int = 8,
+                           device: int = 0, resident=False) -> list:
+    """Grid sequencing (nested iteration) of the lid-driven cavity, the network-free accelerator: `meshes` lists (nx, ny) from
+    coarse to fine; level 0 starts from zero fields, and level l from level l - 1's result, interpolated to its mesh
+    (`interpolation_resampler`, float64) on the device -- `fields_device` -> `init_from_fields`; no field crosses to the host
+    between levels.  `max_iterations`: the cap of every level, or one cap per level.  `resident`: as
+    FineSolverBatch.set_resident, per level ("auto" runs the small levels resident).  Returns one dict per Reynolds number: Re,
+    fields (the last level's (ny, nx) u, v, p), and iterations and status, one entry per level.  A case that diverges on a
+    level passes its non-finite fields on and diverges on the next."""
+    reynolds, meshes = list(reynolds), [(int(m[0]), int(m[1])) for m in meshes]
+    if not meshes:
+        raise ValueError("meshes must list at least one (nx, ny)")
+    caps = [int(max_iterations)] * len(meshes) if np.isscalar(max_iterations) else [int(m) for m in max_iterations]
+    if len(caps) != len(meshes):
+        raise ValueError(f"max_iterations must be one cap or one per level ({len(meshes)}), not {len(caps)}")
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    bcs = _per_case(bc, len(reynolds))
+    res = [{"Re": Re, "fields": None, "iterations": [], "status": []} for Re in reynolds]
+    for a in range(0, len(reynolds), max_batch):
+        z = slice(a, a + max_batch)
+        prev, prev_mesh = None, None
+        for level, ((nx, ny), cap) in enumerate(zip(meshes, caps)):
+            pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds[z], bcs[z])]
+            b = FineSolverBatch(pbs, cap, device, resident=resident)
+            try:
+                if prev is not None:
+                    up = interpolation_resampler(prev_mesh[1], prev_mesh[0], nx, ny, 1.0, 1.0, device)
+                    try:
+                        b.init_from_fields(prev, resampler=up)
+                    finally:
+                        up.close()
+                b.solve()
+                for i, r in enumerate(res[z]):
+                    r["iterations"].append(int(b.iterations[i]))
+                    r["status"].append(int(b.status[i]))
+                if level + 1 < len(meshes):
+                    prev, prev_mesh = b.fields_device(), (nx, ny)
+                else:
+                    for i, r in enumerate(res[z]):
+                        r["fields"] = b.fields(i)
+            finally:
+                b.close()
+    return res

@@ -71,13 +71,23 @@ class Resampler:
         """x: float32 CUDA tensor (n,in_h,in_w) -> float64 CUDA tensor (n,out_h,out_w).  Both are checked first (_lib.device_ptr:
         contiguous, on this resampler's device, n samples of its sizes); a ValueError leaves nothing enqueued."""
         import torch
+        return self._apply(x, out, stream, torch.float32, L.lib.srcfd_resample_device)
+
+    def apply_device_f64(self, x, out=None, stream=None):
+        """`apply_device` for a float64 CUDA tensor, a solver's fields (srcfd_resample_device_f64): the same products in the same
+        order on a float64 operand, so float-valued input gives `apply_device`'s bits.  `stream`: a raw handle or a torch stream."""
+        import torch
+        return self._apply(x, out, getattr(stream, "cuda_stream", stream), torch.float64, L.lib.srcfd_resample_device_f64)
+
+    def _apply(self, x, out, stream, dtype, entry):
+        import torch
         n = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) else 0
-        px = L.device_ptr(x, "x", torch.float32, (n, self.in_h, self.in_w), self.device)
+        px = L.device_ptr(x, "x", dtype, (n, self.in_h, self.in_w), self.device)
         if out is None:
             out = torch.empty((n, self.out_h, self.out_w), dtype=torch.float64, device=x.device)
         pout = L.device_ptr(out, "out", torch.float64, (n, self.out_h, self.out_w), self.device)
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.lib.srcfd_resample_device(self._h, px, n, pout, C.c_void_p(st)))
+        L.check(entry(self._h, px, n, pout, C.c_void_p(st)))
         return out
 
 
