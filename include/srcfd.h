@@ -163,8 +163,10 @@ int srcfd_model_supports_precision(const srcfd_model* m, int precision);
  *   out_affine[2i..2i+1] = (mean, std): y := y * std + mean in float32
  *       (inverse_standardize, PyCFD_ML_accelerated.py:671-673).  SRCFD_PREC_FP32 (the parity path): two roundings,
  *       bit for bit numpy's float32 result; the 16-bit precisions fuse the two into ONE fma (<= 1 ulp from it)
- * flags: SRCFD_FLAG_NAN_GUARD zero-fills NaN/Inf in y and counts them in
- * *n_nonfinite (PyCFD_ML_accelerated.py:869-876). */
+ * flags: SRCFD_FLAG_NAN_GUARD zero-fills every element that is non-finite in y's own type and counts them in
+ * *n_nonfinite (PyCFD_ML_accelerated.py:869-876): NaN, +-Inf, and with a 16-bit y (srcfd_predict_device) a float32
+ * value that the round-to-nearest-even cast turns into +-Inf (|v| >= 65520 for float16).  A guarded call returns no
+ * non-finite element (tests/test_gpu_nonfinite_guard.py). */
 #define SRCFD_FLAG_NAN_GUARD 1
 int srcfd_predict(srcfd_model* m, const float* x, int n, const float* in_affine, const float* out_affine,
                   float* y, int flags, int64_t* n_nonfinite);

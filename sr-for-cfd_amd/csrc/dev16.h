@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/srcfd.h"
+#include "out_guard.h"
 
 namespace srcfd {
 

@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) outconv16(OutConv16Params p) {
     }
     float v = acc + p.bias;
     if (p.aff_out) v = __builtin_fmaf(v, p.aff_out[2 * img + 1], p.aff_out[2 * img]);   // one fma (srcfd.h, the 16-bit precisions)
-    if (p.nan_guard && !(fabsf(v) <= 3.402823466e38f)) { v = 0.f; bad = true; }
+    if (p.nan_guard && !out_finite<OUT>(v)) { v = 0.f; bad = true; }
     if (OUT == 0) reinterpret_cast<float*>(p.out)[idx] = v;
     else reinterpret_cast<uint16_t*>(p.out)[idx] = (uint16_t)(pack2<OUT == 2>(v, 0.f) & 0xffffu);
   }

@@ -633,13 +633,20 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
         if (p.nan_guard) {
           // ONE question of the four values first (0 * v summed is NaN iff one of them is not finite: 3 fma + 1 multiply + 1 compare);
           // the per-value zero-fill and count run only then
-          const float t = __builtin_fmaf(v[3], 0.f, __builtin_fmaf(v[2], 0.f, __builtin_fmaf(v[1], 0.f, v[0] * 0.f)));
-          if (__ballot(t != t) != 0ull) {
+          // (a 16-bit output asks its own threshold of each value: a value that is finite in f32 may round to Inf in y's type)
+          bool any_bad;
+          if (OUT == 0) {
+            const float t = __builtin_fmaf(v[3], 0.f, __builtin_fmaf(v[2], 0.f, __builtin_fmaf(v[1], 0.f, v[0] * 0.f)));
+            any_bad = t != t;
+          } else {
+            any_bad = !(out_finite<OUT>(v[0]) && out_finite<OUT>(v[1]) && out_finite<OUT>(v[2]) && out_finite<OUT>(v[3]));
+          }
+          if (__ballot(any_bad) != 0ull) {
             const unsigned long long on = __ballot(lane_on);
             unsigned nbad = 0;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-              const bool ok = fabsf(v[rr]) <= 3.402823466e38f;
+              const bool ok = out_finite<OUT>(v[rr]);
               nbad += (unsigned)__popcll(~__ballot(ok) & on);
               v[rr] = ok ? v[rr] : 0.f;
             }
@@ -712,7 +719,7 @@ __global__ void __launch_bounds__(1024) tail16(TailParams p) {
             if (txo + 4 * rr >= 50) continue;
             float v = acc[rr];
             if (p.aff_out) v = __builtin_fmaf(v, sdv, mean);   // one fma, as the fast path: every row of an image goes through the same arithmetic whatever the segmentation
-            if (p.nan_guard && !(fabsf(v) <= 3.402823466e38f)) { v = 0.f; ++bad_count; }
+            if (p.nan_guard && !out_finite<OUT>(v)) { v = 0.f; ++bad_count; }
             const size_t o = o0 + 32 * rr;
             if (OUT == 0) reinterpret_cast<float*>(p.out)[o] = v;
             else if (OUT == 1) reinterpret_cast<uint16_t*>(p.out)[o] = (uint16_t)(pack2<false>(v, 0.f) & 0xffff);

@@ -18,6 +18,7 @@
 #include "act_device.h"
 #include "gemm32_plan.h"
 #include "kernels.h"
+#include "out_guard.h"
 
 namespace srcfd {
 
@@ -496,7 +497,7 @@ __global__ void __launch_bounds__(256) conv_n1_tile_f32(GemmDesc d, const float*
     const int64_t o = ((int64_t)img * d.OH + y0 + ly) * d.OW + x0 + lx;
     if (!FIN) { Y[o] = v; continue; }
     if (fe.affine) v = __fadd_rn(__fmul_rn(v, f_std), f_mean);
-    if (fe.nan_guard && !(fabsf(v) <= 3.402823466e38f)) { ++nbad; v = 0.f; }
+    if (fe.nan_guard && !out_finite<(FIN > 0 ? FIN - 1 : 0)>(v)) { ++nbad; v = 0.f; }
     if (FIN == 1) reinterpret_cast<float*>(fe.out)[o] = v;
     else if (FIN == 2) reinterpret_cast<unsigned short*>(fe.out)[o] = f32_to_bf16_bits(v);
     else reinterpret_cast<_Float16*>(fe.out)[o] = (_Float16)v;
@@ -613,7 +614,7 @@ __global__ void __launch_bounds__(256) finalize_out(const float* __restrict__ y,
       int s = (int)(i / per_sample);
       v = __fadd_rn(__fmul_rn(v, affine[2 * s + 1]), affine[2 * s]);
     }
-    if (nan_guard && !(fabsf(v) <= 3.402823466e38f)) { bad = true; v = 0.f; }
+    if (nan_guard && !out_finite<OUT>(v)) { bad = true; v = 0.f; }
     if (OUT == 0) ((float*)out)[i] = v;
     else if (OUT == 1) ((unsigned short*)out)[i] = f32_to_bf16_bits(v);
     else ((_Float16*)out)[i] = (_Float16)v;

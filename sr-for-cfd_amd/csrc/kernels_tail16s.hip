@@ -199,14 +199,28 @@ __global__ void __launch_bounds__(512) tail16s(TailParams p) {
   auto d_finish = [&](const f32x4& acc, const int item, const float mean, const float sdv, float (&v)[4]) {
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) v[rr] = __builtin_fmaf(acc[rr], sdv, mean);   // without aff_out: std = 1, mean = 0 -> v exactly
+    // A float16 y is the float32 value rounded once more (srcfd.h; tail16 does the same).  Left alone, hipcc folds the fma and the
+    // cast below into one v_fma_mixlo_f16, which rounds the exact sum straight to float16: a different last bit for a handful of
+    // values per image, and a value the guard's threshold was not asked about.  The empty asm keeps the float32 value (no instruction).
+    if (OUT == 2) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) asm volatile("" : "+v"(v[rr]));
+    }
     if (p.nan_guard) {
-      const float t = __builtin_fmaf(v[3], 0.f, __builtin_fmaf(v[2], 0.f, __builtin_fmaf(v[1], 0.f, v[0] * 0.f)));
-      if (__ballot(t != t) != 0ull) {
+      // (a 16-bit output asks its own threshold of each value: a value that is finite in f32 may round to Inf in y's type)
+      bool any_bad;
+      if (OUT == 0) {
+        const float t = __builtin_fmaf(v[3], 0.f, __builtin_fmaf(v[2], 0.f, __builtin_fmaf(v[1], 0.f, v[0] * 0.f)));
+        any_bad = t != t;
+      } else {
+        any_bad = !(out_finite<OUT>(v[0]) && out_finite<OUT>(v[1]) && out_finite<OUT>(v[2]) && out_finite<OUT>(v[3]));
+      }
+      if (__ballot(any_bad) != 0ull) {
         const unsigned long long on = d_on_mask[(item & 3) == 3 ? 1 : 0];
         unsigned nbad = 0;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-          const bool ok = fabsf(v[rr]) <= 3.402823466e38f;
+          const bool ok = out_finite<OUT>(v[rr]);
           nbad += (unsigned)__popcll(~__ballot(ok) & on);
           v[rr] = ok ? v[rr] : 0.f;
         }
@@ -404,7 +418,8 @@ __global__ void __launch_bounds__(512) tail16s(TailParams p) {
         for (int rr = 0; rr < 4; ++rr) {
           if (txo + 4 * rr >= 50) continue;
           float v = __builtin_fmaf(acc[rr], sdv, mean);
-          if (p.nan_guard && !(fabsf(v) <= 3.402823466e38f)) { v = 0.f; ++bad_count; }
+          if (OUT == 2) asm volatile("" : "+v"(v));   // as in d_finish: the float32 value, then the cast
+          if (p.nan_guard && !out_finite<OUT>(v)) { v = 0.f; ++bad_count; }
           const size_t o = o0 + 32 * rr;
           if (OUT == 0) reinterpret_cast<float*>(p.out)[o] = v;
           else if (OUT == 1) reinterpret_cast<uint16_t*>(p.out)[o] = (uint16_t)(pack2<false>(v, 0.f) & 0xffff);

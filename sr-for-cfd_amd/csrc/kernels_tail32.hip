@@ -34,6 +34,7 @@
 #include "act_device.h"
 #include "kernels.h"
 #include "kernels16.h"  // lds_attr_once
+#include "out_guard.h"
 
 namespace srcfd {
 
@@ -402,7 +403,7 @@ __global__ void __launch_bounds__(512) tail32(Tail32Params p) {
         }
         if (!TRAIN && p.aff_out) t = __fadd_rn(__fmul_rn(t, d_sd), d_mean);
         if (!TRAIN && p.nan_guard) {
-          const bool bad = st_on && !(fabsf(t) <= 3.402823466e38f);
+          const bool bad = st_on && !out_finite<OUT>(t);
           bad_total += (unsigned)__popcll(__ballot(bad));
           t = bad ? 0.f : t;
         }
