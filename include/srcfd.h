@@ -656,6 +656,13 @@ int srcfd_trainer_forward_backward(srcfd_trainer* t, const float* params_dev, co
 #define SRCFD_TRAIN_SAME_PARAMS 2
 int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev, const float* x_dev, const float* y_dev, int n,
                                       float loss_scale, float* grads_dev, double* sse_dev, int flags, void* hip_stream);
+/* What the last successfully enqueued forward_backward call of this trainer ran with (read-only host state, no HIP call, no
+ * stream; all zero before the first call): *n its samples; *tail_seg the segments per sample of the fused tail's forward launch,
+ * *tail_blocks that launch's workgroups, *bwd_blocks the workgroups (= weight-gradient slabs) of the fused tail's backward launch,
+ * all three 0 when the tail is not fused (srcfd_trainer_get_plan); *launch 0 for plain launches, 1 for the call that captured the
+ * step graph and launched it, 2 for a replay of a captured graph.  A trainer holds at most 8 step graphs; calls with a further
+ * key run as plain launches.  Any pointer may be NULL. */
+int srcfd_trainer_last_step(const srcfd_trainer* t, int* n, int* tail_seg, int* tail_blocks, int* bwd_blocks, int* launch);
 /* Keras Adam update, step counted from 1: alpha_t = lr*sqrt(1-beta2^t)/(1-beta1^t); p -= alpha_t*m/(sqrt(v)+eps).
  * Pointers: four dense float32 arrays of n elements, 4-byte aligned (one element per lane). */
 int srcfd_adam_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n, int step, float lr,

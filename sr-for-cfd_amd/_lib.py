@@ -126,6 +126,7 @@ _protos = {
     "srcfd_trainer_num_params": (C.c_int64, [_p]),
     "srcfd_trainer_get_params": (C.c_int, [_p, _p]),
     "srcfd_trainer_get_plan": (C.c_int, [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "srcfd_trainer_last_step": (C.c_int, [_p] + [C.POINTER(C.c_int)] * 5),
     "srcfd_trainer_forward_backward": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_float, _p, _p, _p]),
     "srcfd_trainer_forward_backward_ex": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_float, _p, _p, C.c_int, _p]),
     "srcfd_model_save_superres_h5": (C.c_int, [_p, C.c_char_p]),

@@ -489,7 +489,11 @@ struct Trainer {
     const float* params = nullptr; float* grads = nullptr; double* sse = nullptr; int n = 0, flags = 0; float loss_scale = 0.f;
     bool operator==(const StepKey& o) const { return params == o.params && grads == o.grads && sse == o.sse && n == o.n && flags == o.flags && loss_scale == o.loss_scale; }
   };
-  struct StepGraph { StepKey key; int seen = 0; GraphExec exec; };
+  // What the last step that was issued ran with (srcfd_trainer_last_step): written by trainer_step from the numbers it launched with,
+  // kept per captured graph for its replays.  Host state only.
+  struct StepRecord { int n = 0, tail_seg = 0, tail_blocks = 0, bwd_blocks = 0, launch = 0; };
+  StepRecord last;
+  struct StepGraph { StepKey key; int seen = 0; GraphExec exec; StepRecord rec; };
   std::vector<StepGraph> graphs;                   // at most 8 keys (full batches, the ragged last batch, ...)
   // A replayed step graph runs its aux branch on a stream of the runtime's own: destroyed before the DEVICE had drained, it kept 56 MiB (measured).
   ~Trainer() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }   // then the members' destructors (device_mem.h)
@@ -633,6 +637,8 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   if (n <= 0 || n > t.max_batch) { set_error("training: batch outside [1, max_batch]"); return SRCFD_EINVAL; }
   HIPCHECK(hipSetDevice(t.device));
   const int overwrite = (flags & SRCFD_TRAIN_OVERWRITE) ? 1 : 0;
+  Trainer::StepRecord rec;   // the tail's launch sizes as they are issued below; stored once the whole step is enqueued
+  rec.n = n;
   auto grid = [](int64_t n_) { return dim3((unsigned)((n_ + 255) / 256)); };
   // 1. pack every operand of the step from the flat parameters: one launch (the data-gradient operands used to be packed on the
   //    second stream beside the forward pass -- a fork and a join of the replayed graph, ~10 us each, to hide a 12 us kernel)
@@ -698,6 +704,7 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
     q.target = y; q.two_scale = 2.0f * loss_scale; q.sse_partial = t.d_loss_partial.get();
     nb = tail32_blocks(n, q.seg, t.num_cus);
     HIPCHECK(launch_tail32(q, t.num_cus, s));
+    rec.tail_seg = q.seg; rec.tail_blocks = nb;
   } else {
     int64_t oe = (int64_t)n * t.layers[L - 1].out_elems;
     nb = (int)std::min<int64_t>(1024, (oe + 255) / 256);
@@ -708,7 +715,8 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   //    gradients of the layers from aux_from up, and the sum of the loss partials (nobody on the chain needs it).
   //    The weight-gradient grids and the slab-sum table are planned here in one go (plan_step: host integer arithmetic; a replayed
   //    graph never comes back here); trainer_build sized every op's slab space from the same plan.
-  const StepPlan plan = plan_step(t.ops, Lg, n, t.use_tail ? tail_bwd32_blocks(n, t.tail.H, t.tail.W, t.num_cus) : 0);
+  rec.bwd_blocks = t.use_tail ? tail_bwd32_blocks(n, t.tail.H, t.tail.W, t.num_cus) : 0;
+  const StepPlan plan = plan_step(t.ops, Lg, n, rec.bwd_blocks);
   FinishTable ftab;
   ftab.nops = (int)plan.sums.size(); ftab.overwrite = overwrite;
   for (int q = 0; q < ftab.nops; ++q) {
@@ -773,6 +781,7 @@ static int trainer_step(Trainer& t, const float* params, const float* x, const f
   // all slabs are written: ONE launch sums them into grads
   if (ftab.nops > 0) hipLaunchKernelGGL(wgrad_finish_all_f32, dim3((unsigned)plan.blocks), dim3(256), 0, s, ftab, grads);
   HIPCHECK(hipGetLastError());
+  t.last = rec;
   return SRCFD_OK;
 }
 
@@ -825,6 +834,19 @@ int srcfd_trainer_get_plan(const srcfd_trainer* t, int* fused_tail, int* fused_e
   });
 }
 
+int srcfd_trainer_last_step(const srcfd_trainer* t, int* n, int* tail_seg, int* tail_blocks, int* bwd_blocks, int* launch) {
+  return srcfd::abi_guard("srcfd_trainer_last_step", [&]() -> int {
+    if (!t) { set_error("srcfd_trainer_last_step: bad arguments"); return SRCFD_EINVAL; }
+    const Trainer::StepRecord& r = reinterpret_cast<const Trainer*>(t)->last;
+    if (n) *n = r.n;
+    if (tail_seg) *tail_seg = r.tail_seg;
+    if (tail_blocks) *tail_blocks = r.tail_blocks;
+    if (bwd_blocks) *bwd_blocks = r.bwd_blocks;
+    if (launch) *launch = r.launch;
+    return SRCFD_OK;
+  });
+}
+
 int srcfd_trainer_forward_backward(srcfd_trainer* t, const float* params_dev, const float* x_dev, const float* y_dev, int n, float loss_scale,
                                    float* grads_dev, double* sse_dev, void* hip_stream) {
   return srcfd::abi_guard("srcfd_trainer_forward_backward", [&]() -> int {
@@ -856,7 +878,7 @@ int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev,
     Trainer::StepGraph* slot = nullptr;
     for (auto& g : tt.graphs) if (g.key == key) slot = &g;
     if (!slot && tt.graphs.size() < 8) { tt.graphs.emplace_back(); slot = &tt.graphs.back(); slot->key = key; }
-    if (slot && slot->exec) { HIPCHECK(hipGraphLaunch(slot->exec, s)); return SRCFD_OK; }
+    if (slot && slot->exec) { HIPCHECK(hipGraphLaunch(slot->exec, s)); tt.last = slot->rec; tt.last.launch = 2; return SRCFD_OK; }
     if (slot && ++slot->seen == 2) {  // every one-time set-up (function attributes, ...) happened on the first, plain pass
       HIPCHECK(hipStreamBeginCapture(tt.cap_stream, hipStreamCaptureModeThreadLocal));
       int rc = srcfd::trainer_step(tt, params_dev, tt.d_xs.get(), tt.d_ys.get(), n, loss_scale, grads_dev, sse_dev, flags, tt.cap_stream);
@@ -865,7 +887,7 @@ int srcfd_trainer_forward_backward_ex(srcfd_trainer* t, const float* params_dev,
       if (rc == SRCFD_OK && e == hipSuccess && g) {
         e = hipGraphInstantiate(slot->exec.out(), g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
-        if (e == hipSuccess) { HIPCHECK(hipGraphLaunch(slot->exec, s)); return SRCFD_OK; }
+        if (e == hipSuccess) { HIPCHECK(hipGraphLaunch(slot->exec, s)); slot->rec = tt.last; tt.last.launch = 1; return SRCFD_OK; }
         slot->exec.reset();
       } else if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();  // capture not possible here: plain launches from now on for this key

@@ -102,6 +102,15 @@ class Trainer:
         L.check(L.lib.srcfd_trainer_get_plan(self._h, C.byref(tail), C.byref(enc)))
         return {"fused_tail": tail.value, "fused_encoder": enc.value}
 
+    def last_step(self) -> Dict[str, int]:
+        """What the last forward_backward call ran with (srcfd_trainer_last_step; host state, nothing is enqueued):
+        {"n", "tail_seg", "tail_blocks", "bwd_blocks" (the three 0 without the fused tail), "launch": 0 plain launches | 1 captured
+        and launched | 2 replayed}."""
+        keys = ("n", "tail_seg", "tail_blocks", "bwd_blocks", "launch")
+        v = [C.c_int(-1) for _ in keys]
+        L.check(L.lib.srcfd_trainer_last_step(self._h, *[C.byref(c) for c in v]))
+        return {k: c.value for k, c in zip(keys, v)}
+
     def forward_backward(self, x, y, global_batch: Optional[int] = None, overwrite: bool = False, same_params: bool = False) -> None:
         """Accumulates this rank's gradient of the GLOBAL mean-squared error into self.grads (and the squared-error sum into
         self.sse); overwrite=True stores them instead (SRCFD_TRAIN_OVERWRITE: no zero-fill launches in front of the step).

@@ -140,15 +140,18 @@ def batch(rng, n, in_shape, oshape):
 _SR_REFS = {}
 
 
-def _sr_case(srcfd, enc_weights, dec_weights, n):
+def _sr_case(srcfd, enc_weights, dec_weights, n, seed=None):
+    """seed: the batch's seed, 500 + n unless a caller's table names another for that n (tests/train_batches.py); one case per n"""
+    seed = 500 + n if seed is None else seed
     if n not in _SR_REFS:
         specs = srcfd.layers_from_weights(enc_weights, dec_weights)
-        rng = np.random.default_rng(500 + n)
+        rng = np.random.default_rng(seed)
         x, y = batch(rng, n, (10, 10, 1), (400, 400, 1))
         y[:, :2] += 3.0
         y[:, :, -2:] -= 3.0
-        _SR_REFS[n] = (specs, x, y, Ref(specs, (10, 10, 1), x, y))
-    return _SR_REFS[n]
+        _SR_REFS[n] = (seed, specs, x, y, Ref(specs, (10, 10, 1), x, y))
+    assert _SR_REFS[n][0] == seed, (n, seed, _SR_REFS[n][0])
+    return _SR_REFS[n][1:]
 
 
 @pytest.mark.gpu
@@ -419,23 +422,22 @@ def adam_m_v_f32(g, m, v, b1=0.9, b2=0.999):
     return b1 * m + (f(1) - b1) * g, b2 * v + (f(1) - b2) * g * g
 
 
-@pytest.mark.gpu
-def test_adam_five_steps_and_ragged_step_match_reference(srcfd, enc_weights, dec_weights):
-    """Five Trainer.steps on moving batches (8, 8, 7, 8, 8 samples): after each, the device's own gradient through the float64
-    Adam reference with float64 m / v carried forward -> params (rtol 2e-6, atol 2e-9), Trainer.m and Trainer.v (8x the error
-    of the float32 restatement of adam_f32, against float64).  The ragged step's loss and gradient against the oracle on its
-    7 samples (the 1 / (gb out_elems) scale)."""
-    require_gpu(srcfd)
+def adam_steps_match_reference(srcfd, enc_weights, dec_weights, max_batch=8, batches=(8, 8, 7, 8, 8)):
+    """Trainer.steps on moving batches of `batches` samples on a max_batch handle: after each, the device's own gradient through the
+    float64 Adam reference with float64 m / v carried forward -> params (rtol 2e-6, atol 2e-9), Trainer.m and Trainer.v (8x the
+    error of the float32 restatement of adam_f32, against float64).  Every ragged step's (fewer samples than max_batch) loss and
+    gradient against the oracle on its samples (the 1 / (gb out_elems) scale)."""
     import torch
     ag = _ag()
     specs = srcfd.layers_from_weights(enc_weights, dec_weights)
-    t = _tr().Trainer(srcfd.SRModel.from_layers(specs, (10, 10, 1), device=0), max_batch=8)
+    t = _tr().Trainer(srcfd.SRModel.from_layers(specs, (10, 10, 1), device=0), max_batch=max_batch)
     rng = np.random.default_rng(900)
     m64 = np.zeros(t.n_params)
     v64 = np.zeros(t.n_params)
     m32, v32 = m64.astype(np.float32), v64.astype(np.float32)
     keep = []
-    for step, n in enumerate((8, 8, 7, 8, 8), start=1):
+    assert any(n < max_batch for n in batches)
+    for step, n in enumerate(batches, start=1):
         x, y = batch(rng, n, (10, 10, 1), (400, 400, 1))
         xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
         keep.append((xd, yd))                      # later batches land at new addresses
@@ -443,7 +445,7 @@ def test_adam_five_steps_and_ragged_step_match_reference(srcfd, enc_weights, dec
         loss = t.step(xd, yd)
         torch.cuda.synchronize()
         g = t.grads.cpu().numpy().astype(np.float64)
-        if n == 7:
+        if n < max_batch:
             cur = [dict(s) for s in specs]
             off = 0
             for s in cur:
@@ -452,7 +454,7 @@ def test_adam_five_steps_and_ragged_step_match_reference(srcfd, enc_weights, dec
                     s["w"] = p0[off:off + kw].reshape(s["w"].shape).astype(np.float32); off += kw
                     s["b"] = p0[off:off + kb].reshape(s["b"].shape).astype(np.float32); off += kb
             assert off == t.n_params
-            check(f"adam ragged step {step} n=7", Ref(cur, (10, 10, 1), x, y), loss, g)
+            check(f"adam ragged step {step} n={n}", Ref(cur, (10, 10, 1), x, y), loss, g)
         p_ref, m64, v64 = ag.adam_reference(p0, g, m64, v64, step)
         m32, v32 = adam_m_v_f32(g, m32, v32)
         np.testing.assert_allclose(t.params.cpu().numpy(), p_ref, rtol=2e-6, atol=2e-9, err_msg=f"params after step {step}")
@@ -462,4 +464,14 @@ def test_adam_five_steps_and_ragged_step_match_reference(srcfd, enc_weights, dec
             ed = np.linalg.norm(dev.cpu().numpy().astype(np.float64) - r64) / nr
             print(f"[adam step {step}] {name}: device {ed:.2e}, float32 restatement {e32:.2e}")
             assert ed <= RATIO * max(e32, TINY), (step, name, ed, e32)
-    assert t.t == 5
+    steps = t.t
+    t.close()
+    assert steps == len(batches)
+    return steps
+
+
+@pytest.mark.gpu
+def test_adam_five_steps_and_ragged_step_match_reference(srcfd, enc_weights, dec_weights):
+    """Five Trainer.steps on moving batches (8, 8, 7, 8, 8 samples), max_batch 8: adam_steps_match_reference."""
+    require_gpu(srcfd)
+    assert adam_steps_match_reference(srcfd, enc_weights, dec_weights, max_batch=8, batches=(8, 8, 7, 8, 8)) == 5

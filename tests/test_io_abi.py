@@ -62,6 +62,9 @@ def test_every_declared_symbol_is_exported_and_bound(srcfd):
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/srcfd.h but not exported"
     assert set(names) == set(L.EXPORTED), set(names) ^ set(L.EXPORTED)
+    # the read-only record of the last training step: six pointers (the handle and five ints), and no stream among them
+    assert "srcfd_trainer_last_step" in names and len(L.lib.srcfd_trainer_last_step.argtypes) == 6
+    assert L.lib.srcfd_trainer_last_step(None, None, None, None, None, None) < 0   # a null handle is a status, and needs no device
 
 
 def test_library_is_in_tree_and_links_hip(srcfd):

@@ -60,6 +60,57 @@ def wgrad_slices(d, n):
     return max(1, -(-M // rps)), rps, M
 
 
+def short_last_slice(d, n):
+    """whether op d's last weight-gradient slice at batch n has fewer rows than the others"""
+    ns, rps, M = wgrad_slices(d, n)
+    return ns > 1 and M % rps != 0
+
+
+# ---------------------------------------------------------------------------
+# The three rules of the SR network's step that move with the batch n beside the slices above (tests/train_batches.py,
+# tests/test_gpu_train_batches.py: what Trainer.last_step() must report, and which batches reach which form)
+# ---------------------------------------------------------------------------
+def tail32_segments(n, H, cus):
+    """Segments per sample of the fused tail's forward launch (kernels_tail32.hip): a sample is 2H strips; the busiest workgroup
+    walks ceil(n S / cus) virtual samples of ceil(2H / S) + 1 strips, + 2 rounds of pipeline depth; a larger S is taken only
+    where it is more than 10 % cheaper than the best so far."""
+    strips = 2 * H
+    best, seg = -(-n // cus) * strips + 2, 1
+    for cand in range(2, strips + 1):
+        cost = -(-n * cand // cus) * (-(-strips // cand) + 1) + 2
+        if cost * 110 < best * 100:
+            best, seg = cost, cand
+    return seg
+
+
+def tail32_ragged(n, H, cus):
+    """the segment count does not divide the strip count: segments of two different lengths"""
+    return (2 * H) % tail32_segments(n, H, cus) != 0
+
+
+def tail32_blocks(n, seg, cus):
+    """workgroups of that launch: one per virtual sample, at most one per CU"""
+    return min(n * max(seg, 1), cus)
+
+
+def tail_bwd32_tiles(n, H, W):
+    """(16-pixel tiles of the fused tail's backward launch over the n H W pixels of its input level, pixels of the last tile,
+    pairs of tiles: a workgroup takes two tiles at a time)"""
+    px = n * H * W
+    tiles = -(-px // 16)
+    return tiles, px - 16 * (tiles - 1), (tiles + 1) // 2
+
+
+def tail_bwd32_blocks(n, H, W, cus):
+    """workgroups (= weight-gradient slabs) of that launch"""
+    return max(1, min(tail_bwd32_tiles(n, H, W)[2], cus))
+
+
+def train_enc_groups(n):
+    """(full groups of 16 samples, samples of the partial last group) of the fused encoder's first launch"""
+    return n // 16, n % 16
+
+
 def tier(slices):
     """finishing groups wgrad_finish_all_f32 uses for that many slabs"""
     return 32 if slices >= 256 else (8 if slices >= 64 else (4 if slices >= 8 else 1))

@@ -157,7 +157,7 @@ static void dump_train_plan(const std::string& tag, const std::vector<Op>& iops,
   if (!f) std::exit(2);
   for (int tail = 0; tail <= (tail_first >= 0 ? 1 : 0); ++tail) {
     const int Lg = tail ? tail_first : (int)layers.size();
-    for (int n : {1, 2, 3, 4, 5, 7, 8, 9, 32}) {
+    for (int n = 1; n <= 32; ++n) {   // every batch a max_batch = 32 trainer takes
       const int64_t pairs = (((int64_t)n * tail_hw + 15) / 16 + 1) / 2;
       const StepPlan P = plan_step(ops, Lg, n, tail ? (int)std::max<int64_t>(1, std::min<int64_t>(pairs, 256)) : 0);
       for (size_t q = 0; q < P.sums.size(); ++q) {
