@@ -613,6 +613,28 @@ int srcfd_fine_batch_set_mode(srcfd_fine_batch* b, int mode);
 /* Device bytes a batch allocates: n_cases x ((14 planes x (nx+2)(ny+2) + 9 nx) x 8 + one status block + one resident record +
  * one parameter block).  Needs no device. */
 int srcfd_fine_batch_footprint(int nx, int ny, int n_cases, int64_t* device_bytes);
+/* ---- direct pressure solve: four float64 matrix products in place of the red-black sweeps -------------
+ * The inner pressure solve keeps the ghost ring frozen, so it is a Dirichlet 5-point Poisson problem on the nx x ny interior for
+ * every case type and boundary condition, and the sine transform (DST-I) diagonalises it:
+ *   p = Sx [ (Sx g Sy) / Lambda ] Sy,  g = rhs - the ghost neighbours' terms,  Lambda[a][b] = volp (lambda_x[a]/dx^2 + lambda_y[b]/dy^2).
+ * SRCFD_PRESSURE_SWEEPS (the default) is the red-black solve with the launches and bits it always had.  SRCFD_PRESSURE_DIRECT
+ * replaces it, in launch mode, by those four products on the f64 matrix cores (csrc/poisson_direct.hip): four launches and no
+ * status read per pressure solve, the system solved to rounding where the sweeps stop at 1e-6 or at their cap of 1000.  Everything
+ * around the solve is unchanged.  A case's bits still depend on neither the batch size nor its place in the batch, but there is no
+ * numpy twin with equal bits: the mode is held by tolerance (tests/poisson_direct_ref.py).  It follows another trajectory to the
+ * same fixed point as the sweeps.  A direct solve counts as 1 in counters[1] and in last_sweeps[.][2].
+ * set_pressure_solver may be called between any two run calls.  The first switch to DIRECT allocates, per handle, the two bases
+ * (padded to multiples of 32) and two nx x ny float64 planes per case; a handle that never switches allocates nothing more.
+ * SRCFD_EINVAL, the handle unchanged: an unknown value; DIRECT on a handle in SRCFD_FINE_MODE_RESIDENT, and set_mode(RESIDENT) on a
+ * DIRECT handle -- the resident mode has no direct path; the message names both settings.
+ * srcfd_poisson_basis: S (n x n, row-major) and lambda (n) of one axis, either may be NULL -- S[a][b] = sqrt(2/(n+1)) sin(pi (a+1)(b+1)/(n+1)),
+ * exactly symmetric, lambda[a] = -4 sin^2(pi (a+1) / (2 (n+1))), every entry evaluated in long double and rounded once.  Needs no
+ * device.  SRCFD_EINVAL for n < 1. */
+#define SRCFD_PRESSURE_SWEEPS 0
+#define SRCFD_PRESSURE_DIRECT 1
+int srcfd_fine_batch_set_pressure_solver(srcfd_fine_batch* b, int solver);
+int srcfd_fine_solver_set_pressure_solver(srcfd_fine_solver* s, int solver);
+int srcfd_poisson_basis(int n, double* S, double* lambda);
 
 /* ---- training -----------------------------------------------------------
  * One optimisation step of SuperResolutionAE, split so that a data-parallel driver can put its

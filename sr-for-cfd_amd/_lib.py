@@ -22,6 +22,8 @@ ACT_LINEAR, ACT_SWISH, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
 FLAG_NAN_GUARD = 1
 CASE_RUNNING, CASE_CONVERGED, CASE_DIVERGED = 0, 1, 2
 FINE_MODE_LAUNCHES, FINE_MODE_RESIDENT = 0, 1
+PRESSURE_SWEEPS, PRESSURE_DIRECT = 0, 1
+PRESSURE_SOLVERS = {"sweeps": PRESSURE_SWEEPS, "direct": PRESSURE_DIRECT}
 SCORE_FIELDS = 8   # srcfd_score_fields / srcfd_evalset_score: float32 values per sample, in this order
 SCORE_NAMES = ("mae", "mse", "max_abs", "truth_min", "truth_max", "pred_min", "pred_max", "nonfinite")
 
@@ -155,6 +157,9 @@ _protos = {
     "srcfd_fine_resident_supported": (C.c_int, [C.c_int, C.c_int]),
     "srcfd_fine_batch_set_mode": (C.c_int, [_p, C.c_int]),
     "srcfd_fine_solver_set_mode": (C.c_int, [_p, C.c_int]),
+    "srcfd_fine_batch_set_pressure_solver": (C.c_int, [_p, C.c_int]),
+    "srcfd_fine_solver_set_pressure_solver": (C.c_int, [_p, C.c_int]),
+    "srcfd_poisson_basis": (C.c_int, [C.c_int, _p, _p]),
     "srcfd_adam_step": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _p]),
     "srcfd_stats_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "srcfd_stats_save": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),

@@ -34,6 +34,11 @@
 // and handoff_kernel writes the result into those cases' Var; the other cases start from zero ("Warm starts").
 // srcfd_fine_batch_init_from_fields_device is the same hand-off fed from a caller's device fields, and
 // srcfd_fine_batch_get_fields_device (fields_kernel) returns them: DESIGN.md section 2c, "Device fields in and out".
+//
+// The direct pressure solve (SRCFD_PRESSURE_DIRECT, set_pressure_solver).  The ghost ring is frozen during an inner pressure solve, so
+// the solve is a Dirichlet Poisson problem that the sine bases diagonalise: outer() then replaces inner(2, 2, ..) by the four matrix
+// products of poisson_direct.hip -- four launches, no status read -- and everything around them stays.  Launch mode only; the default,
+// SRCFD_PRESSURE_SWEEPS, is the path above with its launches and bits.  DESIGN.md section 2c, "Direct pressure solve".
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,6 +48,8 @@
 #include <vector>
 
 #include "engine.h"
+#include "fine_dev.h"
+#include "poisson_plan.h"
 
 namespace srcfd {
 
@@ -57,34 +64,6 @@ constexpr int MAX_CASES = 64;      // keeps the per-chunk status read small
 static_assert(3 * MAX_CASES <= Model::STAGE_SAMPLES, "the samples of a full batch must fit one staged chunk of Model::predict_host");
 static_assert(MAX_CASES <= 256, "WarmMap holds case indices in bytes");
 
-struct Status {      // one per case; written by the kernels with plain stores, read by the host once per chunk
-  int m_sweeps, m_stop;    // current momentum solve: sweeps executed, exit rule fired
-  int p_sweeps, p_stop;    // current pressure solve
-  int state;               // SRCFD_CASE_*, a case that is not RUNNING is frozen
-  int pad;
-  double rms[3];
-};
-
-struct Bc {
-  int type[4];
-  double value[4];
-  int bfs;
-  double step_h, h, Ub;
-};
-
-struct CaseP {       // what may differ between the cases of a batch
-  double dx, dy, volp, dt, rho, nu;
-  double tol[3], relax[3];
-  Bc bc[3];
-};
-
-struct BDev {        // the kernels' argument: the batch
-  int nx, ny, sx, sy;
-  size_t stride;     // doubles per case: Var, Old, Jb (3 planes each), Ff (4), rhs (1), partials (9 nx)
-  double* base;
-  const CaseP* cp;
-  Status* st;
-};
 constexpr size_t case_doubles(int nx, int ny) { return (size_t)14 * (nx + 2) * (ny + 2) + (size_t)9 * nx; }
 
 struct Dev {         // one case's view of it (case_dev)
@@ -735,6 +714,9 @@ struct FineBatch {
   ResRec* d_rec = nullptr;
   int mode = SRCFD_FINE_MODE_LAUNCHES;
   DevBuf<char> d_mem;
+  int pressure = SRCFD_PRESSURE_SWEEPS;
+  DevBuf<double> d_poisson;    // the direct pressure solve's bases, eigenvalues and workspace planes: allocated by the first switch to it
+  PoissonDev pd{};
   Event arrived, written;      // a caller's stream against this handle's: its work so far (join), the fields written for it (release)
   Stream stream;               // declared last: destroyed before the memory its work uses
   size_t state_bytes = 0;      // fields and status blocks: what init clears
@@ -1048,6 +1030,19 @@ struct FineBatch {
     return SRCFD_OK;
   }
 
+  // The pressure solve of every live case as four matrix products (poisson_direct.hip): no status is read, a solve counts as one sweep.
+  int direct_pressure() {
+    int rc;
+    for (int which = 0; which < 4; ++which) {
+      poisson_direct_product(which, g, pd, n, stream);
+      if ((rc = launched())) return rc;
+    }
+    for (int c = 0; c < n; ++c)
+      if (live(c)) last_sweeps[3 * c + 2] = 1;
+    n_p += 1;
+    return SRCFD_OK;
+  }
+
   // One outer iteration of every live case: _implicit_solve + _convergence_check (the order of srcfd_coarse_solve)
   int outer() {
     int rc;
@@ -1063,7 +1058,11 @@ struct FineBatch {
     if ((rc = launched())) return rc;
     hipLaunchKernelGGL(pressure_rhs, cells_grid(), dim3(NT), 0, stream, g);
     if ((rc = launched())) return rc;
-    if ((rc = inner(2, 2, &n_p))) return rc;
+    if (pressure == SRCFD_PRESSURE_DIRECT) {
+      if ((rc = direct_pressure())) return rc;
+    } else if ((rc = inner(2, 2, &n_p))) {
+      return rc;
+    }
     if (relax) {
       hipLaunchKernelGGL(under_relax, cells_grid(), dim3(NT), 0, stream, g, 2);
       if ((rc = launched())) return rc;
@@ -1088,7 +1087,40 @@ struct FineBatch {
                 std::to_string(g.nx) + " x " + std::to_string(g.ny));
       return SRCFD_EINVAL;
     }
+    if (m == SRCFD_FINE_MODE_RESIDENT && pressure == SRCFD_PRESSURE_DIRECT) {
+      set_error(who + ": SRCFD_FINE_MODE_RESIDENT has no direct pressure solve, and this handle is set to SRCFD_PRESSURE_DIRECT");
+      return SRCFD_EINVAL;
+    }
     mode = m;
+    return SRCFD_OK;
+  }
+
+  // SRCFD_PRESSURE_DIRECT: the first switch builds the bases of this mesh on the host, uploads them and allocates the two workspace
+  // planes per case; a handle that never asks keeps the footprint it had.
+  int set_pressure_solver(const std::string& who, int m) {
+    if (m != SRCFD_PRESSURE_SWEEPS && m != SRCFD_PRESSURE_DIRECT) { set_error(who + ": unknown pressure solver " + std::to_string(m)); return SRCFD_EINVAL; }
+    if (m == SRCFD_PRESSURE_DIRECT && mode == SRCFD_FINE_MODE_RESIDENT) {
+      set_error(who + ": SRCFD_PRESSURE_DIRECT has no resident path, and this handle is set to SRCFD_FINE_MODE_RESIDENT");
+      return SRCFD_EINVAL;
+    }
+    if (m == SRCFD_PRESSURE_DIRECT && !d_poisson) {
+      HIPCHECK_F(hipSetDevice(device));
+      const int ldx = poisson_ld(g.nx), ldy = poisson_ld(g.ny);
+      const size_t n_sx = (size_t)ldx * ldx, n_sy = (size_t)ldy * ldy, n_work = (size_t)2 * n * g.nx * g.ny;
+      std::vector<double> host(n_sx + n_sy + g.nx + g.ny);
+      poisson_basis(g.nx, ldx, host.data(), host.data() + n_sx + n_sy);
+      poisson_basis(g.ny, ldy, host.data() + n_sx, host.data() + n_sx + n_sy + g.nx);
+      DevBuf<double> mem;
+      int rc = mem.alloc(host.size() + n_work);
+      if (rc) return rc;
+      HIPCHECK_F(hipMemcpy(mem.get(), host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));   // the planes need no clearing: product 0 writes before anything reads
+      d_poisson = std::move(mem);
+      double* const b = d_poisson.get();
+      pd.Sx = b; pd.Sy = b + n_sx; pd.lx = b + n_sx + n_sy; pd.ly = pd.lx + g.nx;
+      pd.ldx = ldx; pd.ldy = ldy;
+      pd.work = b + host.size();
+    }
+    pressure = m;
     return SRCFD_OK;
   }
 
@@ -1270,6 +1302,22 @@ int srcfd_fine_solver_set_mode(srcfd_fine_solver* s, int mode) {
   });
 }
 
+int srcfd_fine_solver_set_pressure_solver(srcfd_fine_solver* s, int solver) {
+  return srcfd::abi_guard("srcfd_fine_solver_set_pressure_solver", [&]() -> int {
+    if (!s) { set_error("srcfd_fine_solver_set_pressure_solver: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(s)->set_pressure_solver("srcfd_fine_solver_set_pressure_solver", solver);
+  });
+}
+
+// ---------------------------------------------------------------- the direct pressure solve's basis (host-only: poisson_plan.cpp)
+int srcfd_poisson_basis(int n, double* S, double* lambda) {
+  return srcfd::abi_guard("srcfd_poisson_basis", [&]() -> int {
+    if (n < 1) { set_error("srcfd_poisson_basis: n " + std::to_string(n) + " is below 1"); return SRCFD_EINVAL; }
+    srcfd::poisson_basis(n, n, S, lambda);
+    return SRCFD_OK;
+  });
+}
+
 // ---------------------------------------------------------------- batches
 int srcfd_fine_resident_supported(int nx, int ny) { return srcfd::resident_mesh_ok(nx, ny) ? 1 : 0; }
 
@@ -1277,6 +1325,13 @@ int srcfd_fine_batch_set_mode(srcfd_fine_batch* b, int mode) {
   return srcfd::abi_guard("srcfd_fine_batch_set_mode", [&]() -> int {
     if (!b) { set_error("srcfd_fine_batch_set_mode: bad arguments"); return SRCFD_EINVAL; }
     return batch_of(b)->set_mode("srcfd_fine_batch_set_mode", mode);
+  });
+}
+
+int srcfd_fine_batch_set_pressure_solver(srcfd_fine_batch* b, int solver) {
+  return srcfd::abi_guard("srcfd_fine_batch_set_pressure_solver", [&]() -> int {
+    if (!b) { set_error("srcfd_fine_batch_set_pressure_solver: bad arguments"); return SRCFD_EINVAL; }
+    return batch_of(b)->set_pressure_solver("srcfd_fine_batch_set_pressure_solver", solver);
   });
 }
 

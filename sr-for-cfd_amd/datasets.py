@@ -242,7 +242,7 @@ def generate_simulation_file(path, reynolds_numbers: Iterable[int] = range(100, 
                              case_name: str = "double lid driven cavity", dt: float = 0.001, scheme: str = "QUICK",
                              convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
                              max_batch: int = 8, device: int = 0, solve: Optional[Callable] = None,
-                             resident=False) -> List[Tuple[int, int, int, int]]:
+                             resident=False, pressure: str = "sweeps") -> List[Tuple[int, int, int, int]]:
     """The data-creation notebook's sweep (sr-simulation-data-creation.ipynb cell 2): every Reynolds number on every n x n mesh
     from zero fields, one `Re{Re}_mesh{n}x{n}` group each in `path`, which `load_paired_reynolds_multi` reads.  Per mesh size
     the Reynolds numbers are solved `max_batch` at a time by `fine.run_normal_simulations` (or by `solve`, a callable of that
@@ -250,6 +250,7 @@ def generate_simulation_file(path, reynolds_numbers: Iterable[int] = range(100, 
     of the same name is replaced.  A diverged case is reported and not written; one that only reached `max_iterations` is
     written, like the notebook's.  `resident` (False, True or "auto", as fine.FineSolverBatch.set_resident) is handed to the
     solve as a keyword unless it is False; "auto" runs the small meshes of the sweep resident and the others as before.
+    `pressure` ("sweeps" or "direct", as fine.FineSolverBatch.set_pressure_solver) likewise, unless it is "sweeps".
     -> [(Re, n, iterations, status)] with fine.FineSolverBatch's status codes."""
     if max_batch < 1:
         raise ValueError("max_batch must be at least 1")
@@ -257,6 +258,8 @@ def generate_simulation_file(path, reynolds_numbers: Iterable[int] = range(100, 
         from .fine import run_normal_simulations as solve
     reynolds_numbers = list(reynolds_numbers)
     mode = {} if resident is False else {"resident": resident}
+    if pressure != "sweeps":
+        mode["pressure"] = pressure
     done: Dict[str, tuple] = {}           # group -> (Re, n, fields) of this call, in the order the file gets them
     record = []
     for n in mesh_sizes:

@@ -22,6 +22,10 @@ sequencing (`run_bfs_interpolated_fine_simulations`, `compare_bfs_warm_starts` f
 `resident=` (False, True or "auto") on the solver classes and the sweep functions selects the resident mode for meshes of at most
 64 x 64 cells (`resident_supported`): one workgroup per case runs many outer iterations per launch, with the same bits.
 `run_coarse_simulations` / `run_bfs_coarse_simulations` solve the coarse fields of a whole sweep as one resident batch.
+
+`pressure=` ("sweeps", the default, or "direct") on the solver classes and on every function here that runs a fine solve selects
+the inner pressure solver (`FineSolverBatch.set_pressure_solver`): "direct" replaces the red-black sweeps by an exact solve of four
+float64 matrix products, in launch mode only.
 """
 from __future__ import annotations
 
@@ -82,14 +86,22 @@ def resident_supported(nx: int, ny: int) -> bool:
     return bool(L.lib.srcfd_fine_resident_supported(int(nx), int(ny)))
 
 
-def _resident_mode(resident, nx: int, ny: int) -> int:
-    """The srcfd mode of a `resident=` keyword: False launches, True resident (the library refuses an unsupported mesh),
-    "auto" resident where `resident_supported` holds."""
+def _resident_mode(resident, nx: int, ny: int, pressure: str = "sweeps") -> int:
+    """The srcfd mode of a `resident=` keyword: False launches, True resident (the library refuses an unsupported mesh and a
+    handle whose pressure solver is "direct"), "auto" resident where `resident_supported` holds and the pressure solver is the
+    sweeps -- the resident mode has no direct path."""
     if resident == "auto":
-        return L.FINE_MODE_RESIDENT if resident_supported(nx, ny) else L.FINE_MODE_LAUNCHES
+        return L.FINE_MODE_RESIDENT if resident_supported(nx, ny) and pressure != "direct" else L.FINE_MODE_LAUNCHES
     if resident is True or resident is False:
         return L.FINE_MODE_RESIDENT if resident else L.FINE_MODE_LAUNCHES
     raise ValueError(f"resident must be False, True or 'auto', not {resident!r}")
+
+
+def _pressure_code(name) -> int:
+    """The srcfd constant of a `pressure=` keyword, "sweeps" or "direct"."""
+    if not isinstance(name, str) or name not in L.PRESSURE_SOLVERS:
+        raise ValueError(f"pressure must be one of {tuple(L.PRESSURE_SOLVERS)}, not {name!r}")
+    return L.PRESSURE_SOLVERS[name]
 
 
 def _stream_handle(stream, device: int):
@@ -164,9 +176,9 @@ def _resampler_fits(resampler, mesh, device: int):
 
 class FineSolver:
     """Device-resident float64 solver state for one problem (srcfd_fine_solver_*).  Starts from `_initialize_fields`.
-    `resident`: see `set_resident`."""
+    `resident`: see `set_resident`; `pressure`: see `set_pressure_solver`."""
 
-    def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0, resident=False):
+    def __init__(self, pb: L.CoarseProblem, max_iterations: int = 100000, device: int = 0, resident=False, pressure: str = "sweeps"):
         self.problem = pb
         self.device = int(device)
         self.max_iterations = int(max_iterations)
@@ -177,7 +189,9 @@ class FineSolver:
         self._h = C.c_void_p()
         L.check(L.lib.srcfd_fine_solver_create(C.byref(pb), int(device), C.byref(self._h)))
         self.resident = False
+        self.pressure = "sweeps"
         try:
+            self.set_pressure_solver(pressure)
             self.set_resident(resident)
         except ValueError:
             self.close()
@@ -197,10 +211,16 @@ class FineSolver:
         outer iterations per launch; ValueError on a mesh that `resident_supported` refuses, and the solver keeps its mode.
         "auto": resident where supported.  The bits are the same, and the mode may change between any two `run` calls.
         Returns whether the solver is now resident."""
-        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny)
+        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny, self.pressure)
         L.check(L.lib.srcfd_fine_solver_set_mode(self._h, mode))
         self.resident = mode == L.FINE_MODE_RESIDENT
         return self.resident
+
+    def set_pressure_solver(self, name: str) -> str:
+        """`FineSolverBatch.set_pressure_solver` for the one case (srcfd_fine_solver_set_pressure_solver)."""
+        L.check(L.lib.srcfd_fine_solver_set_pressure_solver(self._h, _pressure_code(name)))
+        self.pressure = name
+        return self.pressure
 
     @property
     def shape(self):
@@ -290,7 +310,8 @@ class FineSolver:
         c = (C.c_int64 * 4)()
         s = (C.c_int * 3)()
         L.check(L.lib.srcfd_fine_solver_counters(self._h, c, s))
-        return {"momentum_sweeps": c[0], "pressure_sweeps": c[1], "launches": c[2], "host_syncs": c[3], "last_sweeps": list(s)}
+        return {"momentum_sweeps": c[0], "pressure_sweeps": c[1], "launches": c[2], "host_syncs": c[3], "last_sweeps": list(s),
+                "pressure_solver": self.pressure}
 
     def fields(self) -> Dict[str, np.ndarray]:
         V = self.Var
@@ -303,9 +324,11 @@ class FineSolver:
 class FineSolverBatch:
     """B cases of one mesh, scheme and case type in one set of launches (srcfd_fine_batch_*): each case computes what a
     `FineSolver` of its own computes, bit for bit.  `status[i]` is 0 while case i runs (or only the iteration budget ended),
-    1 converged, 2 diverged (non-finite residuals; the other cases go on, nothing is raised).  `resident`: see `set_resident`."""
+    1 converged, 2 diverged (non-finite residuals; the other cases go on, nothing is raised).  `resident`: see `set_resident`;
+    `pressure`: see `set_pressure_solver`."""
 
-    def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0, resident=False):
+    def __init__(self, problems: Sequence[L.CoarseProblem], max_iterations: int = 100000, device: int = 0, resident=False,
+                 pressure: str = "sweeps"):
         self.problems = list(problems)
         self.n_cases = len(self.problems)
         self.device = int(device)
@@ -316,7 +339,9 @@ class FineSolverBatch:
         pb = self.problems[0]
         self.mesh = MeshParameters(pb.nx, pb.ny, pb.lx, pb.ly)
         self.resident = False
+        self.pressure = "sweeps"
         try:
+            self.set_pressure_solver(pressure)
             self.set_resident(resident)
         except ValueError:
             self.close()
@@ -328,10 +353,22 @@ class FineSolverBatch:
         and up to 100 outer iterations per launch, so that no case waits for another's inner solves; ValueError on a mesh that
         `resident_supported` refuses, and the batch keeps its mode.  "auto": resident where supported.  The bits are the same,
         and the mode may change between any two `run` calls.  Returns whether the batch is now resident."""
-        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny)
+        mode = _resident_mode(resident, self.mesh.nx, self.mesh.ny, self.pressure)
         L.check(L.lib.srcfd_fine_batch_set_mode(self._h, mode))
         self.resident = mode == L.FINE_MODE_RESIDENT
         return self.resident
+
+    def set_pressure_solver(self, name: str) -> str:
+        """"sweeps" (the default): the red-black pressure sweeps, the bits of tests/fine_solver_spec.py.  "direct": every inner
+        pressure solve is solved exactly by four float64 matrix products on the sine bases of the mesh (csrc/poisson_direct.hip;
+        srcfd_fine_batch_set_pressure_solver): four launches and no status read in place of up to 1 000 sweeps, counted as one sweep.
+        The direct mode reaches the sweeps' fixed point along its own trajectory, has no numpy twin with equal bits, and runs in
+        launch mode only: ValueError on a resident handle (and from `set_resident(True)` on a direct one), the handle unchanged;
+        `resident="auto"` resolves to launches.  ValueError for any other name.  May change between any two `run` calls.
+        Returns the name now in force."""
+        L.check(L.lib.srcfd_fine_batch_set_pressure_solver(self._h, _pressure_code(name)))
+        self.pressure = name
+        return self.pressure
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -461,7 +498,7 @@ class FineSolverBatch:
         s = (C.c_int * (3 * self.n_cases))()
         L.check(L.lib.srcfd_fine_batch_counters(self._h, c, s))
         return {"momentum_sweeps": c[0], "pressure_sweeps": c[1], "launches": c[2], "host_syncs": c[3],
-                "last_sweeps": [list(s[3 * i:3 * i + 3]) for i in range(self.n_cases)]}
+                "last_sweeps": [list(s[3 * i:3 * i + 3]) for i in range(self.n_cases)], "pressure_solver": self.pressure}
 
 
 def _finish(solver: FineSolver, Re, output_name, suffix, bfs_step_height=None):
@@ -480,18 +517,19 @@ def _finish(solver: FineSolver, Re, output_name, suffix, bfs_step_height=None):
 # ---------------------------------------------------------------------------------------------- lid-driven cavity
 def run_fine_simulation_with_ml_init(Re: float, nx: int, ny: int, ml_initial_fields: Dict[str, np.ndarray], dt: float = 0.001,
                                      scheme: str = "QUICK", convergence_criteria: Optional[Dict[str, float]] = None,
-                                     max_iterations: int = 100000, output_name: Optional[str] = "cavity_accelerated", bc=None) -> tuple:
+                                     max_iterations: int = 100000, output_name: Optional[str] = "cavity_accelerated", bc=None,
+                                     pressure: str = "sweeps") -> tuple:
     """PyCFD_ML_accelerated.py:882-963: (solver, iterations, time_elapsed); fields (ny, nx) are injected transposed."""
-    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations)
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations, pressure=pressure)
     s.init_fields(ml_initial_fields)
     return _finish(s, Re, output_name, "_accelerated")
 
 
 def run_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.001, scheme: str = "QUICK",
                           convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
-                          output_name: Optional[str] = "cavity_normal", bc=None) -> tuple:
+                          output_name: Optional[str] = "cavity_normal", bc=None, pressure: str = "sweeps") -> tuple:
     """PyCFD_ML_accelerated.py:1126-1184: the same solve from zero fields."""
-    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations)
+    s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations, pressure=pressure)
     return _finish(s, Re, output_name, "_normal")
 
 
@@ -504,13 +542,13 @@ def _per_case(bc, n):
     return [bc] * n
 
 
-def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=None, resident=False):
+def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=None, resident=False, pressure="sweeps"):
     """warm_start(batch, a): starts the batch of problems[a : a + batch.n_cases] (default: from zero fields, as created)."""
     if max_batch < 1:
         raise ValueError("max_batch must be at least 1")
     out = []
     for a in range(0, len(problems), max_batch):
-        b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device, resident=resident)
+        b = FineSolverBatch(problems[a:a + max_batch], max_iterations, device, resident=resident, pressure=pressure)
         try:
             if warm_start is not None:
                 warm_start(b, a)
@@ -523,14 +561,14 @@ def _solve_in_batches(problems, max_iterations, max_batch, device, warm_start=No
 
 def run_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: float = 0.001, scheme: str = "QUICK",
                            convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
-                           max_batch: int = 8, device: int = 0, resident=False) -> list:
+                           max_batch: int = 8, device: int = 0, resident=False, pressure: str = "sweeps") -> list:
     """`run_normal_simulation` for a list of Reynolds numbers, `max_batch` cases at a time on the batched device solver:
     a list of (fields, iterations, status) in input order; fields are the (ny, nx) u, v, p, status as FineSolverBatch's.
     `bc`: one boundary-condition set or a list with one per Reynolds number.  `resident`: as FineSolverBatch.set_resident."""
     reynolds = list(reynolds)
     bcs = _per_case(bc, len(reynolds))
     pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs)]
-    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident)
+    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident, pressure=pressure)
 
 
 def _coarse_sweep(problems, reynolds, max_iterations, max_batch, device, output_dir, name_of, bfs_step_height=None):
@@ -588,7 +626,7 @@ def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re:
                                        dt: float = 0.001, scheme: str = "QUICK", convergence_criteria: Optional[Dict[str, float]] = None,
                                        max_iterations_fine: int = 100000, output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                        encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                       precision: Optional[str] = None, resident=False) -> tuple:
+                                       precision: Optional[str] = None, resident=False, pressure: str = "sweeps") -> tuple:
     """PyCFD_ML_accelerated.py:1024-1123: coarse fields -> SR straight into the device solver state -> fine solve.  The only
     400x400 field that crosses to the host is the result (`solver.Var`, on demand).  `resident`: as FineSolver.set_resident."""
     from . import pipeline
@@ -600,13 +638,13 @@ def run_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re:
     model, x, ain, aout, back, _ = pipeline._prepare(coarse_fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0,
                                                      False, 0.3, precision, pipeline._quiet)
     s = FineSolver(problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bc), max_iterations_fine, model.device,
-                   resident=resident)
+                   resident=resident, pressure=pressure)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated")
 
 
 def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch, output_name, suffix_of, bfs_step_height=None,
-                every=1, resident=False):
+                every=1, resident=False, pressure: str = "sweeps"):
     """The batched warm-started solve behind the sweep drop-ins.  `problems` holds `every` consecutive cases per coarse field,
     of which the first is warm-started from it and the others start from zero; prepare(fields) is pipeline._prepare_batch for
     a list of coarse fields.  The prediction of a batch holds the fields of that batch's warm cases only."""
@@ -621,7 +659,7 @@ def _warm_sweep(coarse_fields_list, problems, prepare, max_iterations, max_batch
         cases = None if every == 1 else [every * i for i in range(n_warm)]
         pipeline._warn_nonfinite(b.init_from_prediction(model, x, ain, aout, back, cases=cases))
 
-    out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start, resident=resident)
+    out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, model.device, warm_start, resident=resident, pressure=pressure)
     _save_sweep(out, problems, output_name, suffix_of, bfs_step_height)
     return out
 
@@ -651,7 +689,7 @@ def _paired(out, reynolds):
 
 
 def _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
-               encoder_file, decoder_file, bc, precision, max_batch, device, every, resident=False):
+               encoder_file, decoder_file, bc, precision, max_batch, device, every, resident=False, pressure: str = "sweeps"):
     from . import pipeline
     reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
     if len(coarse_fields_list) != len(reynolds):
@@ -665,7 +703,7 @@ def _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, converg
     prepare = lambda fields: pipeline._prepare_batch(fields, lr_dim, nx, stats_file, encoder_file, decoder_file, False, 1.0, 1.0, False, 0.3,
                                                      precision, device)
     return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
-                       lambda i: "_accelerated" if i % every == 0 else "_normal", every=every, resident=resident)
+                       lambda i: "_accelerated" if i % every == 0 else "_normal", every=every, resident=resident, pressure=pressure)
 
 
 def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -673,7 +711,7 @@ def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, n
                                         convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                                         output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                         encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                        precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                        precision: Optional[str] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                         device: Optional[int] = None) -> list:
     """`run_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, `max_batch` cases at a time:
     one SR call per batch straight into the batched device solver, then the batched solve.  Returns a list of (fields,
@@ -683,7 +721,7 @@ def run_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, n
     FineSolverBatch.init_from_prediction); with max_batch=1 every case equals the single-case function bit for bit.
     `resident`: as FineSolverBatch.set_resident."""
     return _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
-                      stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 1, resident)
+                      stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 1, resident, pressure)
 
 
 def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -691,7 +729,7 @@ def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.
                                       convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                                       output_name: Optional[str] = None, stats_file: Optional[str] = None,
                                       encoder_file: Optional[str] = None, decoder_file: Optional[str] = None, bc=None,
-                                      precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                      precision: Optional[str] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                       device: Optional[int] = None) -> list:
     """The reference's headline experiment (PyCFD_ML_accelerated.py:1431-1499) for a sweep: every Reynolds number goes into the
     batch twice, case 2i warm-started from its coarse field and case 2i + 1 from zero fields, under the same iteration cap.
@@ -699,7 +737,7 @@ def compare_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.
     (normal - ml), ratio (normal / ml) and both results' fields.  Whether iterations are saved depends on the decoder's
     weights; the function only reports the counts."""
     out = _ldc_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
-                     stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 2, resident)
+                     stats_file, encoder_file, decoder_file, bc, precision, max_batch, device, 2, resident, pressure)
     return _paired(out, list(reynolds))
 
 
@@ -713,10 +751,10 @@ def run_bfs_fine_simulation_with_ml_init(Re: float, nx: int, ny: int, ml_initial
                                          scheme: str = "UPWIND", convergence_criteria: Optional[Dict[str, float]] = None,
                                          max_iterations: int = 100000, output_name: Optional[str] = "bfs_accelerated", bc=None,
                                          step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
-                                         relaxation_factors: Optional[Dict[str, float]] = None) -> tuple:
+                                         relaxation_factors: Optional[Dict[str, float]] = None, pressure: str = "sweeps") -> tuple:
     """bfs_ml_accelerated.py:1140-1234."""
     s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
-                   max_iterations)
+                   max_iterations, pressure=pressure)
     s.init_fields(ml_initial_fields)
     return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
 
@@ -724,10 +762,11 @@ def run_bfs_fine_simulation_with_ml_init(Re: float, nx: int, ny: int, ml_initial
 def run_bfs_normal_simulation(Re: float, nx: int, ny: int, dt: float = 0.002, scheme: str = "UPWIND",
                               convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000,
                               output_name: Optional[str] = "bfs_normal", bc=None, step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0,
-                              lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None) -> tuple:
+                              lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None,
+                              pressure: str = "sweeps") -> tuple:
     """bfs_ml_accelerated.py:1237-1307."""
     s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
-                   max_iterations)
+                   max_iterations, pressure=pressure)
     return _finish(s, Re, output_name, "_normal", bfs_step_height=step_height)
 
 
@@ -735,13 +774,13 @@ def run_bfs_normal_simulations(reynolds: Sequence[float], nx: int, ny: int, dt: 
                                convergence_criteria: Optional[Dict[str, float]] = None, max_iterations: int = 100000, bc=None,
                                step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                relaxation_factors: Optional[Dict[str, float]] = None, max_batch: int = 8, device: int = 0,
-                               resident=False) -> list:
+                               resident=False, pressure: str = "sweeps") -> list:
     """`run_bfs_normal_simulation` for a list of Reynolds numbers, batched as `run_normal_simulations`."""
     reynolds = list(reynolds)
     bcs = _per_case(bc, len(reynolds))
     pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
            for Re, b in zip(reynolds, bcs)]
-    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident)
+    return _solve_in_batches(pbs, max_iterations, max_batch, device, resident=resident, pressure=pressure)
 
 
 def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray], Re: float, nx: int, ny: int, lr_dim: int = 10,
@@ -752,7 +791,7 @@ def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray],
                                            Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                            relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                            use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                           precision: Optional[str] = None, resident=False) -> tuple:
+                                           precision: Optional[str] = None, resident=False, pressure: str = "sweeps") -> tuple:
     """bfs_ml_accelerated.py:1384-1518 (the BFS `ml_super_resolution`: adaptive normalisation, optional aspect-ratio resampling)."""
     from . import pipeline
     stats_file = stats_file or f"standardization_stats_{lr_dim}to{nx}_swish_trained_upto_700_multiBC.txt"
@@ -764,14 +803,14 @@ def run_bfs_ml_accelerated_fine_simulation(coarse_fields: Dict[str, np.ndarray],
                                                      use_aspect_ratio_correction, lx, ly, use_adaptive_normalization, blend_factor, precision,
                                                      pipeline._quiet)
     s = FineSolver(_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, bc, step_height, h, Ub, lx, ly, relaxation_factors),
-                   max_iterations_fine, model.device, resident=resident)
+                   max_iterations_fine, model.device, resident=resident, pressure=pressure)
     pipeline._warn_nonfinite(s.init_from_prediction(model, x, ain, aout, back))
     return _finish(s, Re, output_name, "_accelerated", bfs_step_height=step_height)
 
 
 def _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name, stats_file,
                encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-               use_adaptive_normalization, blend_factor, precision, max_batch, device, every, resident=False):
+               use_adaptive_normalization, blend_factor, precision, max_batch, device, every, resident=False, pressure: str = "sweeps"):
     from . import pipeline
     reynolds, coarse_fields_list = list(reynolds), list(coarse_fields_list)
     if len(coarse_fields_list) != len(reynolds):
@@ -787,7 +826,7 @@ def _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, converg
                                                      lx, ly, use_adaptive_normalization, blend_factor, precision, device)
     return _warm_sweep(coarse_fields_list, pbs, prepare, max_iterations_fine, max_batch, output_name,
                        lambda i: "_accelerated" if i % every == 0 else "_normal", bfs_step_height=step_height, every=every,
-                       resident=resident)
+                       resident=resident, pressure=pressure)
 
 
 def run_bfs_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -798,13 +837,13 @@ def run_bfs_ml_accelerated_fine_simulations(coarse_fields_list: Sequence[Dict[st
                                             step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                             relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                             use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                            precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                            precision: Optional[str] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                             device: Optional[int] = None) -> list:
     """`run_bfs_ml_accelerated_fine_simulation` for a list of coarse fields and their Reynolds numbers, batched as
     `run_ml_accelerated_fine_simulations`."""
     return _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
                       stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 1, resident)
+                      use_adaptive_normalization, blend_factor, precision, max_batch, device, 1, resident, pressure)
 
 
 def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -815,12 +854,12 @@ def compare_bfs_ml_and_normal_simulations(coarse_fields_list: Sequence[Dict[str,
                                           step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
                                           relaxation_factors: Optional[Dict[str, float]] = None, use_aspect_ratio_correction: bool = False,
                                           use_adaptive_normalization: bool = True, blend_factor: float = 0.3,
-                                          precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                                          precision: Optional[str] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                           device: Optional[int] = None) -> list:
     """`compare_ml_and_normal_simulations` for the backward-facing step (bfs_ml_accelerated.py main)."""
     out = _bfs_sweep(coarse_fields_list, reynolds, nx, ny, lr_dim, dt, scheme, convergence_criteria, max_iterations_fine, output_name,
                      stats_file, encoder_file, decoder_file, bc, step_height, h, Ub, lx, ly, relaxation_factors, use_aspect_ratio_correction,
-                     use_adaptive_normalization, blend_factor, precision, max_batch, device, 2, resident)
+                     use_adaptive_normalization, blend_factor, precision, max_batch, device, 2, resident, pressure)
     return _paired(out, list(reynolds))
 
 
@@ -846,7 +885,7 @@ def _stack_fields(coarse_fields_list) -> np.ndarray:
 
 
 def _interpolated_sweep(coarse_fields_list, reynolds, problems, lr_dim, max_iterations, output_name, max_batch, device, resident,
-                        bfs_step_height=None):
+                        bfs_step_height=None, pressure="sweeps"):
     coarse_fields_list = list(coarse_fields_list)
     if len(coarse_fields_list) != len(reynolds):
         raise ValueError(f"coarse_fields_list must hold one set of coarse fields per Reynolds number ({len(reynolds)}), not {len(coarse_fields_list)}")
@@ -854,7 +893,7 @@ def _interpolated_sweep(coarse_fields_list, reynolds, problems, lr_dim, max_iter
     interp = interpolation_resampler(lr_dim, lr_dim, pb.nx, pb.ny, pb.lx, pb.ly, device)
     try:
         warm_start = lambda b, a: b.init_from_fields(_stack_fields(coarse_fields_list[a:a + b.n_cases]), resampler=interp)
-        out = _solve_in_batches(problems, max_iterations, max_batch, device, warm_start, resident=resident)
+        out = _solve_in_batches(problems, max_iterations, max_batch, device, warm_start, resident=resident, pressure=pressure)
     finally:
         interp.close()
     _save_sweep(out, problems, output_name, lambda i: "_interpolated", bfs_step_height)
@@ -864,7 +903,7 @@ def _interpolated_sweep(coarse_fields_list, reynolds, problems, lr_dim, max_iter
 def run_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
                                       lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
                                       convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
-                                      output_name: Optional[str] = None, bc=None, resident=False, max_batch: int = 8,
+                                      output_name: Optional[str] = None, bc=None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                       device: int = 0) -> list:
     """The control arm of a warm-start study: `run_ml_accelerated_fine_simulations` with the network replaced by plain bicubic
     interpolation of each coarse field to the mesh (`interpolation_resampler`), on the device.  The arguments are those of that
@@ -873,7 +912,7 @@ def run_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.
     reynolds = list(reynolds)
     bcs = _per_case(bc, len(reynolds))
     pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds, bcs)]
-    return _interpolated_sweep(coarse_fields_list, reynolds, pbs, lr_dim, max_iterations_fine, output_name, max_batch, device, resident)
+    return _interpolated_sweep(coarse_fields_list, reynolds, pbs, lr_dim, max_iterations_fine, output_name, max_batch, device, resident, pressure=pressure)
 
 
 def run_bfs_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -881,7 +920,7 @@ def run_bfs_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str,
                                           convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                                           output_name: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0,
                                           Ub: float = 1.0, lx: float = 10.0, ly: float = 3.0,
-                                          relaxation_factors: Optional[Dict[str, float]] = None, resident=False, max_batch: int = 8,
+                                          relaxation_factors: Optional[Dict[str, float]] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                                           device: int = 0) -> list:
     """`run_interpolated_fine_simulations` for the backward-facing step: `run_bfs_ml_accelerated_fine_simulations` without the
     model, its files and its input options."""
@@ -890,14 +929,14 @@ def run_bfs_interpolated_fine_simulations(coarse_fields_list: Sequence[Dict[str,
     pbs = [_bfs_problem(Re, nx, ny, dt, scheme, convergence_criteria, b, step_height, h, Ub, lx, ly, relaxation_factors)
            for Re, b in zip(reynolds, bcs)]
     return _interpolated_sweep(coarse_fields_list, reynolds, pbs, lr_dim, max_iterations_fine, output_name, max_batch, device, resident,
-                               bfs_step_height=step_height)
+                               bfs_step_height=step_height, pressure=pressure)
 
 
 ARMS = ("ml", "interp", "zero")
 
 
 def _warm_start_arms(coarse_fields_list, reynolds, problem_of, arms, lr_dim, files, default_files, prepare_of, max_iterations,
-                     output_name, max_batch, device, resident, bfs_step_height=None):
+                     output_name, max_batch, device, resident, bfs_step_height=None, pressure="sweeps"):
     """The solve behind `compare_warm_starts` and its BFS form.  problem_of(i): the problem of Reynolds number i; prepare_of(files,
     device): pipeline._prepare_batch for a list of coarse fields."""
     from . import pipeline
@@ -948,7 +987,7 @@ def _warm_start_arms(coarse_fields_list, reynolds, problem_of, arms, lr_dim, fil
             b.init_from_fields(parts[0] if len(parts) == 1 else torch.cat(parts), cases=cases)
 
     try:
-        out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, device, warm_start, resident=resident)
+        out = _solve_in_batches(problems, max_iterations, max_batch - max_batch % every, device, warm_start, resident=resident, pressure=pressure)
     finally:
         if interp is not None:
             interp.close()
@@ -968,7 +1007,7 @@ def compare_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]], rey
                         arms: Sequence[str] = ARMS, lr_dim: int = 10, dt: float = 0.001, scheme: str = "QUICK",
                         convergence_criteria: Optional[Dict[str, float]] = None, max_iterations_fine: int = 100000,
                         output_name: Optional[str] = None, stats_file: Optional[str] = None, encoder_file: Optional[str] = None,
-                        decoder_file: Optional[str] = None, bc=None, precision: Optional[str] = None, resident=False,
+                        decoder_file: Optional[str] = None, bc=None, precision: Optional[str] = None, resident=False, pressure: str = "sweeps",
                         max_batch: int = 8, device: Optional[int] = None) -> list:
     """`compare_ml_and_normal_simulations` with the control arm: every Reynolds number goes into the batch once per arm -- "ml"
     warm-started from the network, "interp" from the plainly interpolated coarse field (`run_interpolated_fine_simulations`),
@@ -988,7 +1027,7 @@ def compare_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]], rey
     return _warm_start_arms(coarse_fields_list, reynolds,
                             lambda i: problem(reynolds[i], nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, bcs[i]),
                             arms, lr_dim, (stats_file, encoder_file, decoder_file), defaults, prepare_of, max_iterations_fine, output_name,
-                            max_batch, device, resident)
+                            max_batch, device, resident, pressure=pressure)
 
 
 def compare_bfs_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]], reynolds: Sequence[float], nx: int, ny: int,
@@ -998,7 +1037,7 @@ def compare_bfs_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]],
                             decoder_file: Optional[str] = None, bc=None, step_height: float = 1.0, h: float = 2.0, Ub: float = 1.0,
                             lx: float = 10.0, ly: float = 3.0, relaxation_factors: Optional[Dict[str, float]] = None,
                             use_aspect_ratio_correction: bool = False, use_adaptive_normalization: bool = True,
-                            blend_factor: float = 0.3, precision: Optional[str] = None, resident=False, max_batch: int = 8,
+                            blend_factor: float = 0.3, precision: Optional[str] = None, resident=False, pressure: str = "sweeps", max_batch: int = 8,
                             device: Optional[int] = None) -> list:
     """`compare_warm_starts` for the backward-facing step (the arms of `run_bfs_ml_accelerated_fine_simulations`,
     `run_bfs_interpolated_fine_simulations` and `run_bfs_normal_simulations`)."""
@@ -1015,12 +1054,12 @@ def compare_bfs_warm_starts(coarse_fields_list: Sequence[Dict[str, np.ndarray]],
                             lambda i: _bfs_problem(reynolds[i], nx, ny, dt, scheme, convergence_criteria, bcs[i], step_height, h, Ub, lx, ly,
                                                    relaxation_factors),
                             arms, lr_dim, (stats_file, encoder_file, decoder_file), defaults, prepare_of, max_iterations_fine, output_name,
-                            max_batch, device, resident, bfs_step_height=step_height)
+                            max_batch, device, resident, bfs_step_height=step_height, pressure=pressure)
 
 
 def run_nested_simulations(reynolds: Sequence[float], meshes: Sequence, dt: float = 0.001, scheme: str = "QUICK",
                            convergence_criteria: Optional[Dict[str, float]] = None, max_iterations=100000, bc=None, max_batch: int = 8,
-                           device: int = 0, resident=False) -> list:
+                           device: int = 0, resident=False, pressure: str = "sweeps") -> list:
     """Grid sequencing (nested iteration) of the lid-driven cavity, the network-free accelerator: `meshes` lists (nx, ny) from
     coarse to fine; level 0 starts from zero fields, and level l from level l - 1's result, interpolated to its mesh
     (`interpolation_resampler`, float64) on the device -- `fields_device` -> `init_from_fields`; no field crosses to the host
@@ -1043,7 +1082,7 @@ def run_nested_simulations(reynolds: Sequence[float], meshes: Sequence, dt: floa
         prev, prev_mesh = None, None
         for level, ((nx, ny), cap) in enumerate(zip(meshes, caps)):
             pbs = [problem(Re, nx, ny, 1.0, 1.0, dt, scheme, convergence_criteria or _DEFAULT_CC, b) for Re, b in zip(reynolds[z], bcs[z])]
-            b = FineSolverBatch(pbs, cap, device, resident=resident)
+            b = FineSolverBatch(pbs, cap, device, resident=resident, pressure=pressure)
             try:
                 if prev is not None:
                     up = interpolation_resampler(prev_mesh[1], prev_mesh[0], nx, ny, 1.0, 1.0, device)

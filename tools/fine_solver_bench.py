@@ -32,6 +32,15 @@ ranges, and whether the resident median lies below the whole range of the launch
 59 765-iteration 10x10 Re 800 run of tests/test_gpu_fine_solver.py in both modes.
 
     python tools/fine_solver_bench.py --resident --mesh 10,20,30,40,50,64 --batch 1,8 --iters 10 --warmup 2 [--pinned]
+
+With --pressure sweeps|direct it times one inner pressure solver (FineSolverBatch.set_pressure_solver) on both configurations at
+n x n instead: per configuration and batch size of --batch (default 1,8,16; B copies of the configuration as one batch, from zero),
+--repeats times on a fresh handle, --warmup untimed iterations and then --iters timed ones.  One JSON line: every repeat's ms per
+outer iteration of the batch, the median and range, and per repeat the operations enqueued and the host synchronisations of the
+timed iterations.  One arm per invocation, so that arms of different libraries (SRCFD_LIB, or another checkout) can alternate;
+`--pressure sweeps` passes no keyword to the solver, so the same file also runs in a tree that has no direct mode.
+
+    python tools/fine_solver_bench.py --pressure direct --batch 1,8,16 --iters 10 --warmup 2 [--repeats 3]
 """
 import argparse
 import importlib
@@ -87,6 +96,33 @@ def batch_bench(a, fine, coarse):
                 "host_syncs": c["host_syncs"],
             })
         out["batch"][str(B)] = {"reynolds": res, "repeats": rows}
+    print(json.dumps(out))
+
+
+def pressure_bench(a, fine, coarse):
+    n = a.n
+    bfs = {"step_height": 1.0, "h": 2.0, "Ub": 1.0}
+    configs = {
+        "ldc_quick_re1000_double_lid": lambda: fine.problem(1000.0, n, n, 1.0, 1.0, 0.001, "QUICK", None, coarse.LDC_DOUBLE_LID),
+        "bfs_upwind_re400": lambda: fine.problem(400.0, n, n, 10.0, 3.0, 0.002, "UPWIND", None, None, bfs=bfs),
+    }
+    mode = {} if a.pressure == "sweeps" else {"pressure": a.pressure}
+    out = {"mesh": f"{n}x{n}", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "pressure": a.pressure,
+           "unit": "ms per outer iteration of the batch", "configs": {}}
+    for name, make in configs.items():
+        out["configs"][name] = {}
+        for B in [int(b) for b in (a.batch or "1,8,16").split(",")]:
+            ms, launches, syncs, sweeps = [], [], [], []
+            for _ in range(a.repeats):
+                b = fine.FineSolverBatch([make() for _ in range(B)], **mode)
+                dt_s, c = _timed(b, a.warmup, a.iters)
+                b.close()
+                ms.append(round(1e3 * dt_s / a.iters, 4))
+                launches.append(c["launches"])
+                syncs.append(c["host_syncs"])
+                sweeps.append(c["pressure_sweeps"])
+            out["configs"][name][str(B)] = {"ms": ms, "median": float(np.median(ms)), "range": [min(ms), max(ms)],
+                                            "launches_issued": launches, "host_syncs": syncs, "pressure_sweeps": sweeps}
     print(json.dumps(out))
 
 
@@ -207,11 +243,15 @@ def main():
     ap.add_argument("--resident", action="store_true", help="time the resident mode against the launch mode on the meshes of --mesh")
     ap.add_argument("--mesh", default="10,20,30,40,50,64", help="with --resident: comma-separated square mesh sizes")
     ap.add_argument("--pinned", action="store_true", help="with --resident: also the 59 765-iteration 10x10 run in both modes")
+    ap.add_argument("--pressure", default=None, choices=("sweeps", "direct"),
+                    help="time this inner pressure solver on both configurations at the batch sizes of --batch (default 1,8,16)")
     ap.add_argument("--golden", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"),
                     help="directory of the encoder, statistics and coarse-field files --handoff reads")
     a = ap.parse_args()
     fine = importlib.import_module("sr-for-cfd_amd.fine")
     coarse = importlib.import_module("sr-for-cfd_amd.coarse")
+    if a.pressure:
+        return pressure_bench(a, fine, coarse)
     if a.resident:
         return resident_bench(a, fine, coarse)
     if a.batch:
